@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- composited Gaussians/s (fwd+bwd) @1080p of the MI355X rasterizer (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]        (N>1: launched by torch.distributed.run, one rank per GPU)
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+                                                              (N>1: launched by torch.distributed.run, one rank per GPU)
 
 A step = one pass of the hot path over one view: the C-ABI forward (bags_forward_prepare + bags_forward_finish) and
 backward (bags_backward) of BASELINE config 2 -- synth(500 000 Gaussians, seed 0, sm 0.5), one pinhole camera at
@@ -9,9 +10,11 @@ backward (bags_backward) of BASELINE config 2 -- synth(500 000 Gaussians, seed 0
 the views are sharded (rank r renders its own perturbed-pose view of the same replicated scene) and the step ends
 with the RCCL all-reduce of the Gaussian-parameter gradients (59 floats per Gaussian), the path's one exchange step;
 value = N * V * P * K / max-over-ranks time ("weak" scaling: per-GPU work is fixed; V = 1 view per rank per exchange at every N,
-the 4-view figure is a second leg of the same run, "v4").
+the 4-view figure is a second leg of the same run of --full, "v4").
 
-Extra objects on the JSON line:
+A plain run sets up, runs the settle and warm-up steps, times the K steps (ms_per_step = their mean) and prints the line; with
+--dump-outputs DIR it also writes what the last timed step computed as DIR/<name>.npy.  Extra objects on the JSON line of a
+--full run (which also times the cold leg first: ms_per_step_cold):
   roofline      dominant kernel (blend_bwd): algorithmic bytes per launch / mean launch time, timed with hipEvents attached to the
                 kernel's dispatch on the launch stream inside the timed region (bags_profile_*), against the 8 TB/s HBM peak
   op_roofline   the same for the whole fwd+bwd with SURVEY.md 8d's B_alg = G*850 + (P-G)*28 + I*168 + H*W*40
@@ -53,9 +56,10 @@ def build_case(P, W, H, sm, rank, dev):
     return scene, cam
 
 
-def make_step(scene, cam, dev, pose_grads=True, tile_bounds="opacity", leaves=None, binning="auto"):
+def make_step(scene, cam, dev, pose_grads=True, tile_bounds="opacity", leaves=None, binning="auto", keep=None):
     """One view's fwd+bwd closure.  ``leaves``: the (shared, replicated) Gaussian parameter tensors of an earlier view, in
-    scene order -- every view of a rank differentiates the same parameters, only the camera tensors are its own."""
+    scene order -- every view of a rank differentiates the same parameters, only the camera tensors are its own.
+    ``keep``: a dict the step fills with its forward outputs and its per-view leaves (--dump-outputs); None: nothing kept."""
     from bags_raster import GaussianRasterizationSettings, GaussianRasterizer
     from scenes import camera_tensors
     P = scene["means3D"].shape[0]
@@ -80,11 +84,14 @@ def make_step(scene, cam, dev, pose_grads=True, tile_bounds="opacity", leaves=No
     def step(reset_params=True):
         for t in (per_view + params) if reset_params else per_view:
             t.grad = None
-        img, radii, _, _, _ = rast(means3D=lv["means3D"], means2D=means2D, means2D_densify=densify,
-                                   shift_factors=shift, shs=lv["shs"], colors_precomp=None,
-                                   opacities=lv["opacities"], scales=lv["scales"], rotations=lv["rotations"],
-                                   cov3D_precomp=None)
+        img, radii, depth, weights, mean2D = rast(means3D=lv["means3D"], means2D=means2D, means2D_densify=densify,
+                                                  shift_factors=shift, shs=lv["shs"], colors_precomp=None,
+                                                  opacities=lv["opacities"], scales=lv["scales"], rotations=lv["rotations"],
+                                                  cov3D_precomp=None)
         img.backward(cot)
+        if keep is not None:      # detached: the step's autograd graph (and the op's forward state) is not kept alive
+            keep.update(image=img.detach(), radii=radii, depth=depth, weights=weights, mean2D=mean2D,
+                        per_view=dict(ct, means2D=means2D, means2D_densify=densify, shift_factors=shift))
         return radii
 
     return step, params, ct
@@ -201,6 +208,40 @@ def pose_grad_rel_err(P, W, H, sm, n_tiles=96):
                     "(oracle/raster_oracle.py header); tolerance of the tests: 1e-4 vs the fp32 oracle"}
 
 
+DUMP_GAUSSIAN_ROWS = 65536     # --dump-outputs: per-Gaussian arrays keep a fixed seeded sample of this many rows above it
+DUMP_PIXELS = 1 << 21          # ... and per-pixel arrays this many pixels (all of a 1080p image): <= 60 MB in all at any size
+
+
+def dump_outputs(path, keep, names, params, P, H, W):
+    """--dump-outputs: what the timed path handed its caller in its last step -- the forward's outputs (image, depth, weights,
+    radii, mean2D) and the gradients of every input that asked for one -- as float32 <path>/<name>.npy.  Per-Gaussian arrays
+    above DUMP_GAUSSIAN_ROWS rows and per-pixel arrays above DUMP_PIXELS pixels are cut to the same seeded sample of rows /
+    pixels in every run (pixels then as (channels, n))."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    rows = pix = None
+    if P > DUMP_GAUSSIAN_ROWS:
+        rows = torch.randperm(P, generator=torch.Generator().manual_seed(7))[:DUMP_GAUSSIAN_ROWS].sort().values
+    if H * W > DUMP_PIXELS:
+        pix = torch.randperm(H * W, generator=torch.Generator().manual_seed(8))[:DUMP_PIXELS].sort().values
+
+    def per_gaussian(t):
+        return t if rows is None else t[rows.to(t.device)]
+
+    def per_pixel(t):
+        return t if pix is None else t.reshape(t.shape[0], H * W)[:, pix.to(t.device)]
+
+    arrays = {k: per_pixel(keep[k]) for k in ("image", "depth", "weights")}
+    arrays.update({k: per_gaussian(keep[k]) for k in ("radii", "mean2D")})
+    grads = list(zip(names, params)) + list(keep["per_view"].items())
+    for k, t in grads:
+        if t.grad is not None:
+            arrays["grad_" + k] = per_gaussian(t.grad) if t.shape[0] == P else t.grad
+    for k, t in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), t.detach().to(torch.float32).cpu().numpy())
+    return sorted(arrays)
+
+
 def spawn_ranks(n, argv):
     """`python bench.py --gpus N` without a launcher: start the N ranks as a CHILD torch.distributed.run (never exec: this
     process may not be replaced once anything touched the GPU, and it has not touched it yet), relay rank 0's JSON line and
@@ -295,6 +336,13 @@ def main():
                          "second bucket (gradients arrive one step late)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for self-tests "
                                                       "of the multi-rank path on a single GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline as well: the cold leg, the stage profiler (roofline blocks, stage_ms), the "
+                         "v4, median, other host-wait and aabb legs, the CPU baseline and the pose-gradient parity (the --no-* "
+                         "options above switch single ones off).  Without it a run times the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (forward outputs, gradients) as "
+                         "DIR/<name>.npy, float32 (rank 0)")
     args = ap.parse_args()
 
     env_world = os.environ.get("WORLD_SIZE")
@@ -366,18 +414,18 @@ def main():
             return [cam0]
         return [sphere_views(world * v_per_rank, W, H, noise=0.05)[rank + world * j] for j in range(v_per_rank)]
 
-    def make_views(cams, tile_bounds, leaves=None):
+    def make_views(cams, tile_bounds, leaves=None, keep=None):
         fns, params = [], leaves
         for c in cams:
             st_, params_, _ = make_step(scene, c, dev, pose_grads=not args.fixed_pose, tile_bounds=tile_bounds, leaves=params,
-                                        binning=args.binning)
+                                        binning=args.binning, keep=keep)
             params = params if params is not None else params_
             fns.append(st_)
         return fns, params
 
-    def make_leg(v_per_rank, leaves=None, overlap=False):
+    def make_leg(v_per_rank, leaves=None, overlap=False, keep=None):
         """(full_step, finish, reducer-or-pipe, exchange event list, params) of a leg with v_per_rank views behind one exchange."""
-        fns, params = make_views(views_of(v_per_rank), args.tile_bounds, leaves)
+        fns, params = make_views(views_of(v_per_rank), args.tile_bounds, leaves, keep)
         leaf_of = dict(zip(scene.keys(), params))
         red = pip = None
         if world > 1 or v_per_rank > 1:
@@ -436,21 +484,25 @@ def main():
             return radii_
         return full_step, (pip.drain if pip is not None else None), (red or pip), evs, params
 
-    full_step, finish, exch, ex_events, params = make_leg(V, overlap=args.overlap)
+    keep = {} if (args.dump_outputs and rank == 0) else None
+    full_step, finish, exch, ex_events, params = make_leg(V, overlap=args.overlap, keep=keep)
     pipe = exch if args.overlap else None
+    profiled = args.full and not args.no_profile              # the stage profiler feeds the --full blocks alone
 
-    # Cold leg: the contract as written -- W warm-up steps from an idle device, then K timed steps.  After an idle gap an
-    # MI355X runs the same kernel ~14 % slower for its first ~30 launches (tools/trace_order.sh, profiles/r02/trace_order.txt),
-    # so this figure is the clock ramp, reported as ms_per_step_cold.
     (radii0 := full_step())
     torch.cuda.synchronize()
     G = int((radii0 > 0).sum())                               # also loads torch's reduction kernels now, not later
-    time.sleep(0.05)
-    for _ in range(max(1, args.warmup)):
-        full_step()
-    if finish is not None:
-        finish()
-    cold = timed_leg(full_step, args.steps, dist, dev, finish=finish)
+    cold = None
+    if args.full:
+        # Cold leg: the contract as written -- W warm-up steps from an idle device, then K timed steps.  After an idle gap an
+        # MI355X runs the same kernel ~14 % slower for its first ~30 launches (tools/trace_order.sh, profiles/r02/trace_order.txt),
+        # so this figure is the clock ramp, reported as ms_per_step_cold.
+        time.sleep(0.05)
+        for _ in range(max(1, args.warmup)):
+            full_step()
+        if finish is not None:
+            finish()
+        cold = timed_leg(full_step, args.steps, dist, dev, finish=finish)
     # Steady leg (the headline): the device is kept busy from the settle steps through the warm-up into the timed region --
     # nothing that syncs or loads code in between -- so the K timed steps run at the clocks a training loop sees.
     for _ in range(max(0, args.settle_steps) // max(1, V)):
@@ -459,20 +511,22 @@ def main():
         radii = full_step()
     if finish is not None:
         finish()
-    _lib.profile_read()
-    # timed region: only the dominant kernel (blend_bwd) is timed, by hipEvents ATTACHED TO ITS OWN DISPATCH (hipExtLaunchKernelGGL in
-    # csrc/blend.hip: start / stop ride on the kernel's completion signal, on the stream it is launched on) -- no event packet sits
-    # between the step's launches.  (Until round 6 two hipEventRecord calls bracketed it: 10-25 us of bubbles per step inside the very
-    # region they measured.)  A full per-stage breakdown (~14 bracketing records per step) is taken in a separate short pass below.
-    _lib.profile_stride(max(1, args.profile_stride))
-    _lib.profile_enable(0 if args.no_profile else 1)
+    if profiled:
+        _lib.profile_read()
+        # timed region: only the dominant kernel (blend_bwd) is timed, by hipEvents ATTACHED TO ITS OWN DISPATCH (hipExtLaunchKernelGGL in
+        # csrc/blend.hip: start / stop ride on the kernel's completion signal, on the stream it is launched on) -- no event packet sits
+        # between the step's launches.  (Until round 6 two hipEventRecord calls bracketed it: 10-25 us of bubbles per step inside the very
+        # region they measured.)  A full per-stage breakdown (~14 bracketing records per step) is taken in a separate short pass below.
+        _lib.profile_stride(max(1, args.profile_stride))
+        _lib.profile_enable(1)
     ex_events.clear()
     elapsed = timed_leg(full_step, args.steps, dist, dev, finish=finish)
     _lib.profile_enable(0)
     exchange_ms = (sum(a.elapsed_time(b) for a, b in ex_events) / len(ex_events)) if ex_events else 0.0
-    prof_dom = _lib.profile_read()
+    dumped = dump_outputs(args.dump_outputs, keep, list(scene.keys()), params, P, H, W) if keep is not None else None
+    prof_dom = _lib.profile_read() if profiled else {}
     prof = prof_dom
-    if not args.no_profile:
+    if profiled:
         _lib.profile_enable(2)
         for _ in range(min(args.steps, 10)):
             full_step()
@@ -487,7 +541,7 @@ def main():
     # second leg, every N: 4 views per rank behind ONE exchange (gradients accumulate in the flat bucket; at N = 1 the
     # "exchange" is the bucket alone), same parameters, same timed-region rules
     v4 = None
-    if not args.no_v4_leg and V != 4:
+    if args.full and not args.no_v4_leg and V != 4:
         # views 2-4 add their Gaussian gradients into the first view's inside the backward kernel (rasterizer.ACCUMULATE_IN_PLACE,
         # an opt-in of the operator: BagsBackwardArgs.accumulate) instead of through one autograd add pass per tensor and view
         R.ACCUMULATE_IN_PLACE = not args.bucket_always
@@ -515,7 +569,7 @@ def main():
     # on the launch stream (no host sync inside the leg); each event costs a few microseconds of stream bubble, so this figure
     # sits slightly ABOVE the mean of the event-free timed region.
     median50 = None
-    if world == 1 and V == 1 and not args.no_median_leg:
+    if args.full and world == 1 and V == 1 and not args.no_median_leg:
         settle(full_step, max(10, min(60, args.settle_steps)))
         evs_m = [torch.cuda.Event(enable_timing=True) for _ in range(51)]
         evs_m[0].record()
@@ -528,7 +582,7 @@ def main():
                     "note": "50 steps after >= 10 warm-ups, one hipEvent per step boundary on the launch stream (SURVEY 8d protocol)"}
     # the other host-wait mode, same workload and timed-region rules
     other_wait = None
-    if world == 1 and V == 1 and not args.no_lazy_leg:
+    if args.full and world == 1 and V == 1 and not args.no_lazy_leg:
         R.HOST_WAIT = "lazy" if args.host_wait == "forward" else "forward"
         settle(full_step, max(10, min(60, args.settle_steps)))
         el = timed_leg(full_step, args.steps, None, dev)
@@ -536,7 +590,7 @@ def main():
         R.HOST_WAIT = args.host_wait
     # third leg, rank-0 single-GPU runs only: the same workload with the stock 3-sigma tile rule, i.e. upstream's instance list
     aabb = None
-    if world == 1 and V == 1 and args.tile_bounds == "opacity" and not args.no_aabb_leg:
+    if args.full and world == 1 and V == 1 and args.tile_bounds == "opacity" and not args.no_aabb_leg:
         fns_a, _ = make_views([cam0], "aabb")
         settle(lambda: fns_a[0](True), max(3, min(60, args.settle_steps)))   # the setup above left the device idle: settle again
         _lib.profile_read()
@@ -601,12 +655,15 @@ def main():
                             f"{' (pipelined, one step late)' if args.overlap else ''}") if world > 1 else "")},
             "instances_per_s": world * V * I * args.steps / elapsed,
             "ms_per_view": ms_step / V,
-            "ms_per_step_cold": cold / args.steps * 1e3,    # W warm-up + K timed steps from an idle device: no settle steps
             "rccl_ranks": ranks_seen if (world > 1 and args.backend == "nccl") else 0,   # counted by an all-reduce at start-up
             "exchange_ms": exchange_ms,                    # per step, hipEvents around the collective on the launch stream (rank 0)
             "compute_ms": ms_step - exchange_ms,
             "exchange_bytes": ((exch.exchanges[0] if args.overlap else exch).bucket.numel * 4) if exch is not None else 0,
         }
+        if cold is not None:
+            out["ms_per_step_cold"] = cold / args.steps * 1e3   # W warm-up + K timed steps from an idle device: no settle steps
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if v4 is not None:
             out["v4"] = v4
         if world > 1:
@@ -713,7 +770,7 @@ def main():
                                   "frac": b_alg / (dev_ms * 1e-3) / HBM_PEAK,
                                   "frac_wall": b_alg / (ms_step / V * 1e-3) / HBM_PEAK}
             out["stage_ms"] = {k: round(v, 4) for k, v in stages.items()}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(P, W, H, args.sm)
             try:                                               # BASELINE.json metric, second half
                 pg = pose_grad_rel_err(P, W, H, args.sm)

@@ -7,7 +7,7 @@ cd "$(dirname "$0")/.."
 CS=bundle-adjusting-gaussian-splatting_amd/csrc
 ALT=$1; shift
 run() {
-  timeout -k 10 150 python bench.py --no-cpu-baseline --no-aabb-leg --no-v4-leg --no-lazy-leg --no-median-leg --steps ${STEPS:-40} --warmup 5 "$@" 2>/dev/null | python -c "
+  timeout -k 10 150 python bench.py --full --no-cpu-baseline --no-aabb-leg --no-v4-leg --no-lazy-leg --no-median-leg --steps ${STEPS:-40} --warmup 5 "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); s=d['stage_ms']
 print('  ms/step %.4f  cold %.4f  stages:'%(d['ms_per_step'], d['ms_per_step_cold']), s)"

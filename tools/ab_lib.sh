@@ -6,7 +6,7 @@
 cd "$(dirname "$0")/.."
 ALT=$(readlink -f $1); shift
 run() {
-  timeout -k 10 200 python bench.py --no-cpu-baseline --no-aabb-leg --no-v4-leg --no-lazy-leg --no-median-leg --steps ${STEPS:-40} --warmup 5 "$@" 2>/dev/null | python -c "
+  timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-aabb-leg --no-v4-leg --no-lazy-leg --no-median-leg --steps ${STEPS:-40} --warmup 5 "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); s=d['stage_ms']
 print('  ms/step %.4f  K1 %.4f binning %.4f blend_fwd %.4f blend_bwd %.4f pre_bwd %.4f pose_reduce %.4f  I %s'%(d['ms_per_step'], s.get('preprocess_fwd',0), s.get('offsets_scan',0)+s.get('tile_sort',0), s['blend_fwd'], s['blend_bwd'], s['preprocess_bwd'], s.get('pose_reduce',0), d['config'].get('instances_I')))"

@@ -3,7 +3,7 @@
 cd "$(dirname "$0")/.."
 CS=bundle-adjusting-gaussian-splatting_amd/csrc
 run() {
-  timeout -k 10 150 python bench.py --no-cpu-baseline --no-aabb-leg --steps ${STEPS:-40} --warmup 5 "$@" 2>/dev/null | python -c "
+  timeout -k 10 150 python bench.py --full --no-cpu-baseline --no-aabb-leg --steps ${STEPS:-40} --warmup 5 "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); s=d['stage_ms']
 print('  ms/step %.4f  I %d  stages:'%(d['ms_per_step'], d['config']['instances_I']), s)"

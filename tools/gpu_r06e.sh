@@ -3,7 +3,7 @@
 # exercise the operator's allocation paths (retain_graph / overflow / accumulate / two streams / frozen camera)
 cd "$(dirname "$0")/.."
 O=gpurun_out/r06e; mkdir -p $O
-run() { timeout -k 10 200 python bench.py --no-cpu-baseline --no-aabb-leg --no-v4-leg --steps 60 --warmup 5 "$@" 2>/dev/null | python -c "
+run() { timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-aabb-leg --no-v4-leg --steps 60 --warmup 5 "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); s=d['stage_ms']
 print('  ms/step %.4f median %.4f lazy %.4f | K1 %.4f blend_fwd %.4f blend_bwd %.4f pre_bwd %.4f sum %.4f'%(d['ms_per_step'], d.get('ms_per_step_median',0), d['config']['other_host_wait']['ms_per_step'], s.get('preprocess_fwd',0), s['blend_fwd'], s['blend_bwd'], s['preprocess_bwd'], sum(s.values())))"; }

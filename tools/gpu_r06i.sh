@@ -3,11 +3,11 @@
 # time against rocprofv3's average of the same library in the same call
 cd "$(dirname "$0")/.."
 O=gpurun_out/r06i; mkdir -p $O
-run() { timeout -k 10 200 python bench.py --no-cpu-baseline --no-v4-leg --steps 60 --warmup 5 "$@" 2>/dev/null | python -c "
+run() { timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-v4-leg --steps 60 --warmup 5 "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); s=d['stage_ms']
 print('  ms/step %.4f  median-leg mean %.4f  lazy %.4f  aabb %.4f | blend_bwd %.4f (aabb %.4f)  blend_fwd %.4f'%(d['ms_per_step'], d['median_leg']['mean_ms'], d['config']['other_host_wait']['ms_per_step'], d['config']['aabb']['ms_per_step'], s['blend_bwd'], d['config']['aabb']['roofline']['mean_launch_ms'], s['blend_fwd']))"; }
-for rep in 1 2 3; do echo "== default (rep $rep)"; run; echo "== --no-profile (rep $rep)"; timeout -k 10 200 python bench.py --no-cpu-baseline --no-v4-leg --no-aabb-leg --no-lazy-leg --no-median-leg --no-profile --steps 60 --warmup 5 2>/dev/null | python -c "
+for rep in 1 2 3; do echo "== default (rep $rep)"; run; echo "== --no-profile (rep $rep)"; timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-v4-leg --no-aabb-leg --no-lazy-leg --no-median-leg --no-profile --steps 60 --warmup 5 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('  ms/step %.4f'%d['ms_per_step'])"; done 2>&1 | tee $O/ab_ext_events_raw.txt
 cd /tmp && export TMPDIR=/tmp

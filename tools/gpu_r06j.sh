@@ -2,7 +2,7 @@
 # round 6: timing events on the dominant kernel's dispatch -- stride 1 / 4 / none, same device; event-derived launch time against rocprofv3
 cd "$(dirname "$0")/.."
 O=gpurun_out/r06j; mkdir -p $O
-run() { timeout -k 10 200 python bench.py --no-cpu-baseline --no-v4-leg --no-aabb-leg --no-lazy-leg --no-median-leg --steps 60 --warmup 5 "$@" 2>/dev/null | python -c "
+run() { timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-v4-leg --no-aabb-leg --no-lazy-leg --no-median-leg --steps 60 --warmup 5 "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); s=d.get('stage_ms',{})
 print('  ms/step %.4f  blend_bwd %.4f  timed %s'%(d['ms_per_step'], s.get('blend_bwd',0), d.get('roofline',{}).get('launches_timed')))"; }

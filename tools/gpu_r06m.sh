@@ -2,7 +2,8 @@
 # round 6: THE final profile round (library src=432a2a5b05a6 commit=7d518e4) + the default bench a second time
 cd "$(dirname "$0")/.."
 bash tools/profile_round.sh r06f 2>&1 | tail -3
-python bench.py > gpurun_out/prof_r06f/bench_b.json 2> gpurun_out/prof_r06f/bench_b.err
+P=$(dirname "$(ls -d */prof_r06f/bench.json | head -1)")     # the directory profile_round.sh just wrote
+python bench.py --full > "$P/bench_b.json" 2> "$P/bench_b.err"
 python - <<'PY'
 import json, csv
 for f in ('bench.json','bench_b.json'):

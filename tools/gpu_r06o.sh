@@ -3,7 +3,7 @@
 cd "$(dirname "$0")/.."
 O=gpurun_out/r06o; mkdir -p $O
 timeout -k 10 500 python -m pytest tests/test_flat_grads_gpu.py tests/test_parity_gpu.py -x -q -m gpu -k "factored or accumulate or several_streams or split_sh or synthetic or bitwise" > $O/tests.log 2>&1; tail -5 $O/tests.log
-run() { timeout -k 10 300 python bench.py --no-cpu-baseline --no-aabb-leg --no-lazy-leg --no-median-leg --steps 60 --warmup 5 "$@" 2>/dev/null | python -c "
+run() { timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-aabb-leg --no-lazy-leg --no-median-leg --steps 60 --warmup 5 "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); s=d['stage_ms']
 print('  ms/step %.4f | v4 ms/view %.4f (factored_sh %s) | pre_bwd %.4f'%(d['ms_per_step'], d['v4']['ms_per_view'], d['v4'].get('factored_sh'), s['preprocess_bwd']))"; }

@@ -1,6 +1,6 @@
 #!/bin/bash
 # One call on the GPU box that produces everything profiles/ holds for a version tag, all from the library that is in the tree:
-#   bench JSON (default bench.py run), rocprofv3 --kernel-trace --stats summary of the same workload (without the second,
+#   bench JSON (bench.py --full), rocprofv3 --kernel-trace --stats summary of the same workload (without the second,
 #   tile_bounds="aabb" leg: it launches the same kernels on a longer list and would be averaged into them), and traffic.json --
 #   PMC passes of every kernel (FETCH_SIZE, WRITE_SIZE, SQ instruction / busy / LDS counters; separate passes as the guide
 #   prescribes), stamped with the library's build string (tools/make_traffic.py).  bench.py runs LAST once more so that its
@@ -24,5 +24,5 @@ tail -2 $OUT/traffic.log
 python3 tools/make_traffic.py --out $OUT/traffic_aabb.json --tile-bounds aabb > $OUT/traffic_aabb.log 2>&1 || true
 # the bench reads profiles/rNN/traffic.json: put the fresh one there for this run (the caller commits it)
 mkdir -p profiles/$RND && cp $OUT/traffic.json profiles/$RND/traffic.json
-python3 bench.py > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; tail -5 $OUT/bench.err; exit 1; }
+python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; tail -5 $OUT/bench.err; exit 1; }
 echo "bench done: $(cut -c1-300 $OUT/bench.json)"

@@ -2,7 +2,7 @@
 # GPU box: per-launch durations of blend_bwd in launch order (clock behaviour over a run)
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd /tmp && export TMPDIR=/tmp
-rm -rf /tmp/trc && rocprofv3 --kernel-trace --output-format csv -d /tmp/trc -- python3 $ROOT/bench.py --steps 300 --warmup 5 --settle-steps 0 --no-cpu-baseline --no-profile --no-aabb-leg > /tmp/trc.log 2>&1
+rm -rf /tmp/trc && rocprofv3 --kernel-trace --output-format csv -d /tmp/trc -- python3 $ROOT/bench.py --full --steps 300 --warmup 5 --settle-steps 0 --no-cpu-baseline --no-profile --no-aabb-leg > /tmp/trc.log 2>&1
 f=$(find /tmp/trc -name "*kernel_trace.csv" | head -1)
 python3 - "$f" <<'PY'
 import csv, sys
