@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # tests).  Not a fallback: a missing file still raises.
 LIB_PATH = os.environ.get("BAGS_RASTER_LIB") or os.path.join(_HERE, "libbags_raster.so")
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 TILES_AABB, TILES_OPACITY = 0, 1
 DEPTH_Z, DEPTH_DISTANCE = 0, 1
 BINNING_AUTO, BINNING_RADIX = 0, 1
@@ -53,6 +53,10 @@ class BagsBackwardArgs(C.Structure):
                 ("grad_intrinsic", c_fp), ("grad_campos", c_fp), ("grad_shift_factors", c_fp),
                 ("binning_capacity", C.c_int64), ("accumulate", C.c_int32), ("dense_per_tile", C.c_int32), ("grad_shs_rest", c_fp),
                 ("phase", C.c_int32), ("reserved2", C.c_int32), ("grad_dldc", c_fp)]
+
+
+class BagsExtraGrads(C.Structure):          # (ABI 11) cotangents of the depth and weights maps; either may be NULL
+    _fields_ = [("grad_depth", c_fp), ("grad_weights", c_fp)]
 
 
 class BagsDebugViews(C.Structure):
@@ -98,6 +102,8 @@ SYMBOLS = {
                                                   C.POINTER(BagsForwardOut), C.c_int64, C.c_void_p]),
     "bags_backward": (C.c_int, [C.POINTER(BagsSettings), C.POINTER(BagsInputs), C.POINTER(BagsState),
                                 C.POINTER(BagsBackwardArgs), C.c_void_p]),
+    "bags_backward_ex": (C.c_int, [C.POINTER(BagsSettings), C.POINTER(BagsInputs), C.POINTER(BagsState),
+                                   C.POINTER(BagsBackwardArgs), C.POINTER(BagsExtraGrads), C.c_void_p]),
     "bags_sh_gradient_from_views": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(BagsShViews), C.c_void_p, C.c_void_p,
                                               C.c_int32, C.c_void_p]),
     "bags_debug_views": (C.c_int, [C.POINTER(BagsSettings), C.POINTER(BagsInputs), C.POINTER(BagsState), C.c_int64,

@@ -56,6 +56,9 @@ class GaussianRasterizationSettings(NamedTuple):
     # backward of conic = cov2D^-1: "stock" = upstream's computeCov2DCUDA, which divides by det^2 + 1e-7 (the fork inherits it;
     # default since round 5); "exact" = det^2.  At most 1.2e-5 relative on one Gaussian's dL/dcov2D (det >= 0.09)
     conic_grad: str = "stock"
+    # True: the depth (1,H,W) = sum w z and weights (1,H,W) = 1 - T_final outputs are differentiable too (decision D5 of DESIGN.md:
+    # depth-prior and alpha / mask losses; the depth term reaches the pose).  False (default): only the image is, as in the reference
+    depth_weights_grad: bool = False
 
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
@@ -144,6 +147,9 @@ class _Packed:
             raise ValueError("clamp_grad must be 'stock' or 'exact'")
         if settings.conic_grad not in ("stock", "exact"):
             raise ValueError("conic_grad must be 'stock' or 'exact'")
+        if not isinstance(settings.depth_weights_grad, bool):
+            raise ValueError("depth_weights_grad must be True or False")
+        self.depth_weights_grad = settings.depth_weights_grad
         self.settings = L.BagsSettings(
             int(settings.image_height), int(settings.image_width), float(settings.tanfovx), float(settings.tanfovy),
             float(settings.scale_modifier), int(settings.sh_degree), int(M),
@@ -618,23 +624,34 @@ class _RasterizeGaussians(torch.autograd.Function):
                       if ACCUMULATE_IN_PLACE else None)
         ctx.shapes = shapes
         color, radii, depth, weights, mean2D = outs
-        ctx.mark_non_differentiable(radii, depth, weights, mean2D)
-        ctx.set_materialize_grads(False)     # no zero-fill kernels for the four outputs nobody differentiates
+        if pk.depth_weights_grad:            # (decision D5: opt-in)
+            ctx.mark_non_differentiable(radii, mean2D)
+        else:
+            ctx.mark_non_differentiable(radii, depth, weights, mean2D)
+        ctx.set_materialize_grads(False)     # no zero-fill kernels for the outputs nobody differentiates (None reaches backward)
         _finish_wait(lib, fw)                # (HOST_WAIT = "forward": the count is read last, when nothing else is left to do here)
         return color, radii, depth, weights, mean2D
 
     @staticmethod
-    def backward(ctx, grad_color, _g_radii, _g_depth, _g_weights, _g_mean2D):
+    def backward(ctx, grad_color, _g_radii, grad_depth, grad_weights, _g_mean2D):
         lib = L.load()
         fw: _Forwarded = ctx.fw
         pk, dev, P = fw.packed, fw.packed.device, fw.packed.P
         need = ctx.needs_input_grad
-        if grad_color is None:
+        if not pk.depth_weights_grad:
+            grad_depth = grad_weights = None
+        if grad_color is None and grad_depth is None and grad_weights is None:
             return (None,) * 16
+
+        def f32(g):
+            if g is None:
+                return None
+            g = g.detach()
+            return g if (g.dtype == torch.float32 and g.is_contiguous()) else g.to(torch.float32).contiguous()
         with torch.cuda.device(dev):
-            gc = grad_color.detach()
-            if gc.dtype != torch.float32 or not gc.is_contiguous():
-                gc = gc.to(torch.float32).contiguous()
+            # (a missing cotangent is a NULL pointer: the library reads it as zeros)
+            gc, gd, gw = f32(grad_color), f32(grad_depth), f32(grad_weights)
+            extra = L.BagsExtraGrads(_ptr(gd), _ptr(gw)) if (gd is not None or gw is not None) else None
 
             k = pk.keep
             want = _wanted(need, k, ctx.shapes, P)
@@ -690,7 +707,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             _resolve(lib, fw)
             if fw.num_rendered > ws_for:                         # overflow: the exact redo found more instances than the capacity
                 ws = _bytes(lib.bags_backward_workspace_size(P, fw.num_rendered), dev)
-            args = L.BagsBackwardArgs(gc.data_ptr(), fw.num_rendered, ws.data_ptr(), ws.numel(), _ptr(g_means3D),
+            args = L.BagsBackwardArgs(_ptr(gc), fw.num_rendered, ws.data_ptr(), ws.numel(), _ptr(g_means3D),
                                       _ptr(g_means2D), _ptr(g_densify), _ptr(g_sh), _ptr(g_col), _ptr(g_opac),
                                       _ptr(g_scales), _ptr(g_rot), _ptr(g_cov), _ptr(g_view), _ptr(g_proj),
                                       _ptr(g_intr), _ptr(g_campos), _ptr(g_shift), fw.capacity, 1 if in_place is not None else 0, int(DENSE_PER_TILE),
@@ -698,21 +715,25 @@ class _RasterizeGaussians(torch.autograd.Function):
             args.grad_dldc = _ptr(g_dldc)
             state = _state_of(fw)
             gate = ACCUMULATION_GATE
+
+            def backward_call(what):                          # bags_backward, or with the depth / weights cotangents bags_backward_ex
+                if extra is None:
+                    L.check(lib.bags_backward(C.byref(pk.settings), C.byref(pk.inputs), C.byref(state), C.byref(args), stream), what)
+                else:
+                    L.check(lib.bags_backward_ex(C.byref(pk.settings), C.byref(pk.inputs), C.byref(state), C.byref(args),
+                                                 C.byref(extra), stream), what.replace("bags_backward", "bags_backward_ex"))
             if gate is None:
-                L.check(lib.bags_backward(C.byref(pk.settings), C.byref(pk.inputs), C.byref(state), C.byref(args), stream),
-                        "bags_backward")
+                backward_call("bags_backward")
             else:
                 # views of one step on several streams (AccumulationGate): the per-tile half now, the per-Gaussian half -- the one
                 # that adds into the shared gradient buffers -- behind the previous backward's
                 ts = torch.cuda.current_stream(dev)
                 args.phase = L.BWD_BLEND
-                L.check(lib.bags_backward(C.byref(pk.settings), C.byref(pk.inputs), C.byref(state), C.byref(args), stream),
-                        "bags_backward (blend half)")
+                backward_call("bags_backward (blend half)")
                 if gate.event is not None:
                     ts.wait_event(gate.event)
                 args.phase = L.BWD_PREPROCESS
-                L.check(lib.bags_backward(C.byref(pk.settings), C.byref(pk.inputs), C.byref(state), C.byref(args), stream),
-                        "bags_backward (per-Gaussian half)")
+                backward_call("bags_backward (per-Gaussian half)")
                 gate.event = torch.cuda.Event()
                 gate.event.record(ts)
         if g_dldc is not None:                                # (the op's campos tensor is kept alive by the entry: finish reads it)

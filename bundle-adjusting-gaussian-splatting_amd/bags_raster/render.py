@@ -7,7 +7,8 @@ arguments, same choice of covariance path (``pipe.compute_cov3D_python``) and co
   * tensors are created on the device of ``pc.get_xyz`` instead of a hard-coded ``"cuda"``;
   * the camera chain (three calls in the reference, :57,58,61) is evaluated once per tensor, not once per use;
   * ``global_alignment`` may be ``None`` (the reference always passes a pair, ``train.py:250``);
-  * ``shift_factors`` may be ``None`` (= zeros(3)); one extra keyword, ``depth_key`` (decision D6 of DESIGN.md);
+  * ``shift_factors`` may be ``None`` (= zeros(3)); two extra keywords, ``depth_key`` (decision D6 of DESIGN.md) and
+    ``depth_weights_grad`` (the returned ``depth`` / ``weights`` maps carry gradients; decision D5);
   * the two screen-space gradient sinks are leaf tensors (the reference: ``zeros + 0`` with ``retain_grad()``, :37-44).
 """
 from __future__ import annotations
@@ -53,7 +54,7 @@ def _python_colors(pc, xyz, feats, campos: torch.Tensor, mlp_color) -> torch.Ten
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, mlp_color, shift_factors, hybrid: bool = True,
            scaling_modifier: float = 1.0, override_color: Optional[torch.Tensor] = None, iteration: Optional[int] = None,
-           global_alignment=None, depth_key: str = "z"):
+           global_alignment=None, depth_key: str = "z", depth_weights_grad: bool = False):
     """Signature and defaults of gaussian_renderer/__init__.py:30: ``mlp_color`` and ``shift_factors`` are positional and
     required, ``hybrid`` defaults to True (Python-side SH colours + ``mlp_color``).  ``shift_factors=None`` stands for the
     zero vector the reference keeps (train.py:125-126: its optimizer is never stepped)."""
@@ -100,6 +101,7 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, mlp_color, shift_
         debug=pipe.debug,
         debug_iter=iteration,
         depth_key=depth_key,
+        depth_weights_grad=depth_weights_grad,
     )
     rasterizer = GaussianRasterizer(raster_settings=raster_settings)
 

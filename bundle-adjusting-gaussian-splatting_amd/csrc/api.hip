@@ -420,9 +420,20 @@ int bags_forward_finish_speculative(const BagsSettings* s, const BagsInputs* in,
 
 int bags_backward(const BagsSettings* s, const BagsInputs* in, const BagsState* stt, const BagsBackwardArgs* a, void* stream)
 {
+    return bags_backward_ex(s, in, stt, a, nullptr, stream);
+}
+
+int bags_backward_ex(const BagsSettings* s, const BagsInputs* in, const BagsState* stt, const BagsBackwardArgs* a, const BagsExtraGrads* x,
+                     void* stream)
+{
     int rc = check_common(s, in, stt);
     if (rc) return rc;
-    if (!a || !a->grad_color) return fail(BAGS_ERR_ARG, "grad_color must be given");
+    // (ABI 11) the depth / weights cotangents: both null is the plain backward
+    const float* grad_depth = x ? x->grad_depth : nullptr;
+    const float* grad_weights = x ? x->grad_weights : nullptr;
+    const bool extra = grad_depth != nullptr || grad_weights != nullptr;
+    if (!a) return fail(BAGS_ERR_ARG, "grad_color must be given");
+    if (!a->grad_color && !extra) return fail(BAGS_ERR_ARG, "grad_color must be given (or, with bags_backward_ex, grad_depth / grad_weights)");
     const int W = s->image_width, H = s->image_height;
     const int64_t I = a->num_rendered;
     if (I < 0) return fail(BAGS_ERR_ARG, "num_rendered < 0");
@@ -454,13 +465,14 @@ int bags_backward(const BagsSettings* s, const BagsInputs* in, const BagsState* 
         hipEvent_t ea = nullptr, eb = nullptr;
         if (g_prof_mode == 1 && (g_prof_seq.fetch_add(1, std::memory_order_relaxed) % (unsigned long long)g_prof_stride) == 0ull) { ea = prof_event(); eb = prof_event(); }
         { ProfScope ps(ST_BLEND_BWD, st, true); HIP_TRY(launch_blend_bwd(*s, g, b, im, a->grad_color, partials, a->grad_means2D_densify != nullptr, use_binned(s, in->P), st,
-                                                                  I, dense ? live_map : nullptr, ea, eb)); }
+                                                                  I, dense ? live_map : nullptr, ea, eb, grad_depth, grad_weights)); }
         if (ea) { std::lock_guard<std::mutex> lk(g_prof_mutex); g_prof_pending.push_back({ST_BLEND_BWD, ea, eb}); }
         DEBUG_SYNC(s, st, "blend_bwd");
     }
     if (a->phase == BAGS_BWD_BLEND) return BAGS_OK;          // the per-Gaussian half comes with a second call (BAGS_BWD_PREPROCESS)
     int nblocks = 0;
-    { ProfScope ps(ST_PRE_BWD, st, true); HIP_TRY(launch_preprocess_bwd(*s, *in, g, nullptr, partials, slab, &nblocks, *a, st, use_binned(s, in->P), dense ? live_map : nullptr)); }
+    { ProfScope ps(ST_PRE_BWD, st, true); HIP_TRY(launch_preprocess_bwd(*s, *in, g, nullptr, partials, slab, &nblocks, *a, st, use_binned(s, in->P), dense ? live_map : nullptr,
+                                                                     extra)); }
     DEBUG_SYNC(s, st, "preprocess_bwd");
     { ProfScope ps(ST_POSE_REDUCE, st, true); HIP_TRY(launch_pose_reduce(slab, nblocks, *a, st)); }
     DEBUG_SYNC(s, st, "pose_reduce");

@@ -195,11 +195,13 @@ hipError_t launch_blend_bwd(const BagsSettings& s, const GeomView& g, const BinV
                             const float* grad_color, float* partials, bool want_abs, bool binned, hipStream_t st,
                             long long n_records = 0,                      // instance count
                             unsigned char* live_map = nullptr,            // one byte per record (dense-scene mode: the caller's decision), or null
-                            hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);   // attached to the kernel's dispatch when given
+                            hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr,   // attached to the kernel's dispatch when given
+                            const float* grad_depth = nullptr, const float* grad_weights = nullptr);   // BagsExtraGrads (ABI 11)
 bool bwd_dense_mode(long long n_records, int T, int dense_per_tile);      // does a backward of this size run in dense-scene mode?
+// extra: the records carry dL/dz in their twelfth float (blend_bwd ran with BagsExtraGrads): it is summed and added to dL/dtzs
 hipError_t launch_preprocess_bwd(const BagsSettings& s, const BagsInputs& in, const GeomView& g, const int32_t* radii_or_null,
                                  const float* partials, float* pose_slab, int* nblocks_out, const BagsBackwardArgs& a, hipStream_t st,
-                                 bool binned, const unsigned char* live_map = nullptr);
+                                 bool binned, const unsigned char* live_map = nullptr, bool extra = false);
 hipError_t launch_pose_reduce(const float* pose_slab, int nblocks, const BagsBackwardArgs& a, hipStream_t st);
 hipError_t launch_sh_grad_from_views(int P, int M, int deg, const float* means3D, const BagsShViews& views, float* g_shs, float* g_shs_rest,
                                      int accumulate, hipStream_t st);

@@ -173,6 +173,15 @@ struct __attribute__((aligned(16))) ChunkRec {
 //   TF_FOLD: [g0A g0B g1A g1B] [g2A g2B ncA ncB] [AcA AcB RcA RcB]                 (Ac starts at 1 / T_final)
 //   + PIX_NARROW: [g0A g0B g1A g1B] [g2A g2B AcA AcB] [RcA RcB ncA ncB]
 //   else:    [g0A g0B g1A g1B] [g2A g2B TfA TfB] [ -    -   ncA ncB] [AcA AcB RcA RcB]     (Ac, Rc: carries behind the group)
+//   EXTRA (the depth / weights cotangents, BagsExtraGrads) appends a fourth float4 [gDA gDB gAA gAB].
+//
+// EXTRA: depth = sum w_i z_i and weights = sum w_i = 1 - T_final composite like two more colour channels (colours z_i and 1,
+// background 0), so with g_D = dL/ddepth, g_A = dL/dweights the scan is unchanged but for the per-pair value it composites,
+//   x_i = c_i . g + z_i g_D + g_A,
+// and the one new per-splat sum is dL/dz_i = sum over pixels of w_i g_D, in the record's spare twelfth float (s[11]).
+// The two per-pixel floats (2 KB) and the staged z (1 KB) are paid for with 16 fewer slots per wave copy of the sums (3 KB): the
+// chunk geometry is the default's, only a chunk with more than SL - 16 splats reaching one quadrant runs its group phase in two halves.
+#define EXTRA_SLOTS 16
 
 // blocks of the tile a splat can reach with alpha >= 1/255 (conservative; exactness comes from the per-pixel test).
 // Branch-free: one thread evaluates all 16 blocks (the lanes of a wave hold unrelated splats, so early-outs would only
@@ -269,14 +278,15 @@ struct TileRef { int tx, ty; u32 rx, n, maxc; bool early, needle; };   // early:
 // COMPACT (stock tile rule on the tile-binned path): the chunks are staged from the forward's compacted list of record-holding
 // positions (tile_aux, cpos) instead of from consecutive list positions; everything that needs a list POSITION (the pos <=
 // n_contrib test, the per-block "behind the last contributor" filter) takes it from the compacted entry.
-template <bool ABS, bool COMPACT, bool SPARSE>
+template <bool ABS, bool COMPACT, bool SPARSE, bool EXTRA>
 __global__ void __launch_bounds__(256, SCAN_WG_PER_CU)
 blend_bwd_scan_kernel(int W, int H, int grid_x, int T, const uint4* __restrict__ tile_desc,
                       const u32* __restrict__ point_list, const unsigned char* __restrict__ reach_mask, const u32 rm_stride,
                       const float4* __restrict__ g2d, const u32* __restrict__ inst_off, const u32* __restrict__ block_base,
                       const float* __restrict__ bg, const float* __restrict__ final_T, const u32* __restrict__ n_contrib,
                       const float* __restrict__ grad_color, float* __restrict__ partials,
-                      const int test_keep, const uint4* __restrict__ tile_aux, unsigned char* __restrict__ live_map)
+                      const int test_keep, const uint4* __restrict__ tile_aux, unsigned char* __restrict__ live_map,
+                      const float* __restrict__ grad_depth, const float* __restrict__ grad_weights)   // (EXTRA: each, and grad_color, may be null)
 {
     // One workgroup per tile that holds at least one instance, heavy tiles first (slot_of_vblock).  Tried and dropped:
     // persistent workgroups that run the chunk pipeline over the flattened (tile, chunk) sequence, with the next tile's
@@ -285,7 +295,9 @@ blend_bwd_scan_kernel(int W, int H, int grid_x, int T, const uint4* __restrict__
     // the wave timeline: the hardware dispatcher refills a CU as soon as any workgroup leaves, while a persistent
     // workgroup keeps its four waves coupled at two barriers per chunk for the whole launch.
     constexpr int CH = SPARSE ? WCHUNK : BCHUNK;                              // splats staged per chunk
-    constexpr int SL = (SPARSE ? WSLOTS : BSLOTS) - (COMPACT ? 8 : 0);        // slots per wave copy of the sums (COMPACT: chunk_pos needs the LDS of two slots x 4)
+    constexpr int SL = (SPARSE ? WSLOTS : BSLOTS) - (COMPACT ? 8 : 0)         // slots per wave copy of the sums (COMPACT: chunk_pos needs the LDS of two slots x 4)
+                       - (EXTRA ? EXTRA_SLOTS : 0);
+    constexpr int PQX = EXTRA ? PQ + 1 : PQ;                 // float4s per pixel pair
     static_assert(CH > 128 && CH <= 256 && 128 <= SL && SL <= 255, "a chunk is four 64-slot segments; each half of it must fit a wave copy; indices are bytes");
     constexpr int NSEG = (CH + 63) / 64;                     // 64-slot segments of a chunk: thread tid stages slot tid of segment tid >> 6
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -316,7 +328,8 @@ blend_bwd_scan_kernel(int W, int H, int grid_x, int T, const uint4* __restrict__
     __shared__ float recC[CH];
     // 8 pixel pairs (PixPair = 4 x float4) per block + one float4 of padding: the four rows of a wave read four different
     // blocks in one ds_read_b128, and a 512-B block stride would put all four on the same banks
-    __shared__ float4 pixq[16][8 * PQ + 1];          //  6.25 KB (8.25 without TF_FOLD)
+    __shared__ float4 pixq[16][8 * PQX + 1];         //  6.25 KB (EXTRA: 8.25)
+    __shared__ float recZ[EXTRA ? CH : 1];           // EXTRA: the staged splats' view depths
     __shared__ unsigned char lists[16][CH];
     __shared__ u32 masks[CH];                        // block reach masks
     __shared__ float acc[4][SL][12];                 // 33 KB, one copy per wave (LDS float atomics: 2.7x slower, profiles/r05/ab_blend_bwd.txt)
@@ -427,17 +440,23 @@ blend_bwd_scan_kernel(int W, int H, int grid_x, int T, const uint4* __restrict__
             const int py = t.ty * BAGS_TILE + (b >> 2) * 4 + (i >> 2);
             const bool in = (px < W) && (py < H);
             const size_t HW = (size_t)W * H, pixi = (size_t)min(py, H - 1) * W + min(px, W - 1);   // always a valid address
-            const float l0 = grad_color[pixi], l1 = grad_color[HW + pixi], l2 = grad_color[2 * HW + pixi];
+            float l0, l1, l2;
+            if (EXTRA && !grad_color) l0 = l1 = l2 = 0.f;
+            else { l0 = grad_color[pixi]; l1 = grad_color[HW + pixi]; l2 = grad_color[2 * HW + pixi]; }
             const float lT = final_T[pixi];
             const u32 lnc = n_contrib[pixi];
             const float g0 = in ? l0 : 0.f, g1 = in ? l1 : 0.f, g2 = in ? l2 : 0.f;
             const float Tf = in ? lT : 1.f;
             const u32 nc = in ? lnc : 0u;
-            const float bgg = bg[0] * g0 + bg[1] * g1 + bg[2] * g2;          // what lies behind the deepest splat
-            float* pp = reinterpret_cast<float*>(&pixq[tid >> 4][((tid >> 1) & 7) * PQ]);
+            const float bgg = bg[0] * g0 + bg[1] * g1 + bg[2] * g2;          // what lies behind the deepest splat (depth, weights: 0)
+            float* pp = reinterpret_cast<float*>(&pixq[tid >> 4][((tid >> 1) & 7) * PQX]);
             const int h = tid & 1;                        // A or B of the pair
             pp[0 + h] = g0; pp[2 + h] = g1; pp[4 + h] = g2; pp[6 + h] = 1.0f / Tf;   // T_final >= 1e-6: a pixel stops before T falls below 1e-4 and alpha <= 0.99
             pp[8 + h] = bgg; pp[10 + h] = __uint_as_float(nc);
+            if constexpr (EXTRA) {
+                const float lD = grad_depth ? grad_depth[pixi] : 0.f, lA = grad_weights ? grad_weights[pixi] : 0.f;
+                pp[12 + h] = in ? lD : 0.f; pp[14 + h] = in ? lA : 0.f;
+            }
             u32 m = nc;
 #pragma unroll
             for (int d = 8; d >= 1; d >>= 1) m = max(m, (u32)__shfl_xor((int)m, d));   // 16 consecutive threads = one block
@@ -505,11 +524,13 @@ blend_bwd_scan_kernel(int W, int H, int grid_x, int T, const uint4* __restrict__
     //   ...      lists + groups of chunk k            <- the loads land underneath
     //   barrier  consume gathers -> rec(k+1), ids(k+2); only then store the records of chunk k
     ChunkRec rec;
+    float recz = 0.f;                                        // EXTRA: the staged slot's view depth (the line's q2.y)
     {
         const uint2 gid0 = decode_id(gid0r, 1u);
         const Raw raw0 = fetch(gid0.x);
         rec = make_rec(raw0, slot_of(raw0, gid0.x != 0xFFFFFFFFu, A), gid0.y, A, hi0 - min(hi0, (u32)CH), min(hi0, (u32)CH), gid0p, tid,
                        -0.5f * LOG2E, -LOG2E);
+        if (EXTRA) recz = raw0.q2.y;
     }
     asm volatile("" :: "v"(gid1.x), "v"(gid1.y), "v"(gid1p));    // complete before the loop: a pending load on the entry edge costs a vmcnt(0) at every loop top
     gid1 = decode_id(gid1, 1u);
@@ -531,6 +552,7 @@ blend_bwd_scan_kernel(int W, int H, int grid_x, int T, const uint4* __restrict__
             recA[ptid] = make_float4(rec.x, rec.y, rec.ap, rec.bp); recB[ptid] = make_float4(rec.cp, rec.o, rec.r, rec.g); recC[ptid] = rec.b;
             masks[ptid] = rec.mask;
             if (COMPACT) chunk_pos[ptid] = rec.pos - 1u;
+            if (EXTRA) recZ[ptid] = recz;
         }
         // ranks of this slot among its segment's slots that reach quadrant 0..3 (an empty slot has mask 0), and the segment's totals
         u32 myidx;
@@ -557,6 +579,8 @@ blend_bwd_scan_kernel(int W, int H, int grid_x, int T, const uint4* __restrict__
         // interleave without pipeline bubbles.  `s` is the lane's splat, (bx0, by0) its block origin, pixb its block's
         // pixel pairs, `carry` marks the lane that holds the scan totals (the shallowest of its segment).
         f2 a0, a1, a2, a6, a9, a10;
+        f2 a11;                                             // EXTRA: sum w g_D ...
+        float s_z = 0.f;                                    // ... and the step's splat's z
         float sa3, sa4, sa5, sa7, sa8;
         auto block_rows = [&](auto skip_nc_tag, auto skip_p_tag, const StagedSplat s, const bool live, const float bx0, const float by0, float4* pixb, const bool carry) {
             constexpr bool SKIP_NC = decltype(skip_nc_tag)::value;
@@ -564,6 +588,7 @@ blend_bwd_scan_kernel(int W, int H, int grid_x, int T, const uint4* __restrict__
             float pyf = by0;                                // the row's pixel y: integers, so the += 1 below is exact and dy is
                                                             // the forward's s.y - (float)py bit for bit
             a0 = (f2){0.f, 0.f}; a1 = a0; a2 = a0; a6 = a0; a9 = a0; a10 = a0;
+            if constexpr (EXTRA) a11 = a0;
             sa3 = sa4 = sa5 = sa7 = sa8 = 0.f;
             // (Round 5, measured and not kept, profiles/r05/ab_blend_bwd.txt: peeling the first pixel row so that it STARTS the sums
             // instead of adding to 17 zeroed registers, the sums folded into register pairs once per step instead of inside every
@@ -571,8 +596,8 @@ blend_bwd_scan_kernel(int W, int H, int grid_x, int T, const uint4* __restrict__
             // instructions per 16-splat step, 0.3462 -> 0.3474 / 0.3480 ms: plain instructions are not what this kernel waits for.)
 #pragma unroll 1
             for (int iy = 0; iy < 4; ++iy) {
-                float4* P0 = pixb + iy * 2 * PQ;
-                float4* P1 = P0 + PQ;
+                float4* P0 = pixb + iy * 2 * PQX;
+                float4* P1 = P0 + PQX;
                 const float4 q00 = P0[0], q01 = P0[1], q02 = P0[2];       // q*1.zw: carry of prod (1 - alpha); q*2 = Rc Rc nc nc
                 const float4 q10 = P1[0], q11 = P1[1], q12 = P1[2];
                 const u32 nc0 = __float_as_uint(q02.z), nc1 = __float_as_uint(q02.w), nc2 = __float_as_uint(q12.z), nc3 = __float_as_uint(q12.w);
@@ -607,8 +632,14 @@ blend_bwd_scan_kernel(int W, int H, int grid_x, int T, const uint4* __restrict__
                 const f2 oma = 1.f - ala, omb = 1.f - alb;
                 const f2 g0a = {q00.x, q00.y}, g1a = {q00.z, q00.w}, g2a = {q01.x, q01.y};
                 const f2 g0b = {q10.x, q10.y}, g1b = {q10.z, q10.w}, g2b = {q11.x, q11.y};
-                const f2 sda = __builtin_elementwise_fma((f2){s.b, s.b}, g2a, __builtin_elementwise_fma((f2){s.g, s.g}, g1a, s.r * g0a));
-                const f2 sdb = __builtin_elementwise_fma((f2){s.b, s.b}, g2b, __builtin_elementwise_fma((f2){s.g, s.g}, g1b, s.r * g0b));
+                f2 sda = __builtin_elementwise_fma((f2){s.b, s.b}, g2a, __builtin_elementwise_fma((f2){s.g, s.g}, g1a, s.r * g0a));
+                f2 sdb = __builtin_elementwise_fma((f2){s.b, s.b}, g2b, __builtin_elementwise_fma((f2){s.g, s.g}, g1b, s.r * g0b));
+                if constexpr (EXTRA) {                      // + z g_D + g_A (zero cotangents leave sd as it was)
+                    const float4 q04 = P0[3], q14 = P1[3];
+                    const f2 zz = {s_z, s_z};
+                    sda += __builtin_elementwise_fma(zz, (f2){q04.x, q04.y}, (f2){q04.z, q04.w});
+                    sdb += __builtin_elementwise_fma(zz, (f2){q14.x, q14.y}, (f2){q14.z, q14.w});
+                }
                 // ---- one affine scan per pixel: F_i(x) = alpha_i (c_i . g) + (1 - alpha_i) x, lane 0 (deepest) innermost
                 const f2 ofa = ala * sda, ofb = alb * sdb;
                 f2 A01 = oma, A23 = omb, O01 = ofa, O23 = ofb;
@@ -632,6 +663,12 @@ blend_bwd_scan_kernel(int W, int H, int grid_x, int T, const uint4* __restrict__
                 const f2 dLb = Tnb * (sdb - (f2){R2, R3});
                 a0 = __builtin_elementwise_fma(wa, g0a, a0); a1 = __builtin_elementwise_fma(wa, g1a, a1); a2 = __builtin_elementwise_fma(wa, g2a, a2);
                 a0 = __builtin_elementwise_fma(wb, g0b, a0); a1 = __builtin_elementwise_fma(wb, g1b, a1); a2 = __builtin_elementwise_fma(wb, g2b, a2);
+                if constexpr (EXTRA) {
+                    // g_D read again rather than kept across the scan (kept, the ABS instances spill)
+                    const volatile float* dA = reinterpret_cast<const volatile float*>(P0 + 3);
+                    const volatile float* dB = reinterpret_cast<const volatile float*>(P1 + 3);
+                    a11 = __builtin_elementwise_fma(wa, (f2){dA[0], dA[1]}, a11); a11 = __builtin_elementwise_fma(wb, (f2){dB[0], dB[1]}, a11);
+                }
                 // q = dL/dpower = (o G) dL/dalpha (straight through the clamp, decision D3); 0 for non-contributing pairs.
                 // dy is common to the row: the moments in dy are taken on the row sums.  a3 collects sum q = o * sum G dL/dalpha;
                 // the division by o happens once per record.
@@ -678,6 +715,7 @@ blend_bwd_scan_kernel(int W, int H, int grid_x, int T, const uint4* __restrict__
             t0[1] = sa3;         t1[1] = sa4;         t2[1] = sa5;
             t0[2] = a6.x + a6.y; t1[2] = sa7;         t2[2] = sa8;
             t0[3] = a9.x + a9.y; t1[3] = a10.x + a10.y; t2[3] = 0.f;
+            if constexpr (EXTRA) t2[3] = a11.x + a11.y;
             // rotate by the lane's row: afterwards t_j[p] belongs to quarter (row + p) & 3 (two stages of selects per component)
             const bool b0 = (row & 1) != 0, b1 = (row & 2) != 0;
 #define ROT4(t) { const float x0 = b0 ? t[1] : t[0], x1 = b0 ? t[2] : t[1], x2 = b0 ? t[3] : t[2], x3 = b0 ? t[0] : t[3];            \
@@ -769,6 +807,7 @@ blend_bwd_scan_kernel(int W, int H, int grid_x, int T, const uint4* __restrict__
             const int slot = slot_next;
             const float4 ra = recA[slot], rb = recB[slot];
             const StagedSplat s = {ra.x, ra.y, ra.z, ra.w, rb.x, rb.y, rb.z, rb.w, recC[slot], (COMPACT ? chunk_pos[slot] : lo + (u32)slot) + 1u};
+            if (EXTRA) s_z = recZ[slot];
             const u32 rkw = rk4[slot];                      // (consumed at the end of the step)
             // the next step's list entry is read now: list byte -> record is a chain of two LDS latencies otherwise
             slot_next = (li < gend - 16) ? (int)lists[myblk][gend - 17 - li] : 0;
@@ -812,6 +851,7 @@ blend_bwd_scan_kernel(int W, int H, int grid_x, int T, const uint4* __restrict__
                         : "v"(gid2.x), "v"(gid2.y), "v"(raw_n.q0.x), "v"(raw_n.q0.y), "v"(raw_n.q0.z), "v"(raw_n.q0.w), "v"(raw_n.q1.x), "v"(raw_n.q1.y),
                           "v"(raw_n.q1.z), "v"(raw_n.q1.w), "v"(raw_n.q2.x), "v"(raw_n.q2.y), "v"(e_n), "v"(gid2p));
         if (lo > 0) rec = make_rec(raw_n, e_n, gid1.y, A, nx_lo, nx_cnt, gid1p, wtid, c_half, c_one);
+        if (EXTRA && lo > 0) recz = raw_n.q2.y;
         PH_MARK(1);
         // ---- one record per staged instance of the round's segments: the wave copies it sits in added in fixed order.  The record holds
         // the raw sums (sum q rather than sum q / o, the abs sums on the scaled conic): preprocess_bwd applies the per-Gaussian factors once.
@@ -828,6 +868,7 @@ blend_bwd_scan_kernel(int W, int H, int grid_x, int T, const uint4* __restrict__
                     r0.x += x0.x; r0.y += x0.y; r0.z += x2.x; r0.w += x0.z;
                     r1.x += x0.w; r1.y += x2.y; r1.z += x1.x; r1.w += x1.y;
                     r2.x += x2.z; r2.y += x1.z; r2.z += x1.w;
+                    if (EXTRA) r2.w += x2.w;                          // s11 = sum w g_D (0 in every other instance)
                 }
             }
             if (cur_e != 0xFFFFFFFFu) {
@@ -864,10 +905,13 @@ bool bwd_dense_mode(long long n_records, int T, int dense_per_tile_arg)
 }
 // live_map: the caller's ONE decision about the dense-scene mode (bags_backward: bwd_dense_mode) -- the byte map, or null.  The same
 // pointer goes to launch_preprocess_bwd, so the kernel that marks records and the kernel that reads the marks cannot disagree.
+// grad_depth / grad_weights (BagsExtraGrads): the EXTRA instances run when either is given (grad_color may then be null as well).
 hipError_t launch_blend_bwd(const BagsSettings& s, const GeomView& g, const BinView& b, const ImgView& im,
                             const float* grad_color, float* partials, bool want_abs, bool binned, hipStream_t st,
-                            long long n_records, unsigned char* live_map, hipEvent_t ev_start, hipEvent_t ev_stop)
+                            long long n_records, unsigned char* live_map, hipEvent_t ev_start, hipEvent_t ev_stop,
+                            const float* grad_depth, const float* grad_weights)
 {
+    const bool extra = grad_depth != nullptr || grad_weights != nullptr;
     const int gx = cdiv(s.image_width, BAGS_TILE), gy = cdiv(s.image_height, BAGS_TILE);
     const int T = gx * gy;
     if (T == 0) return hipSuccess;
@@ -883,11 +927,13 @@ hipError_t launch_blend_bwd(const BagsSettings& s, const GeomView& g, const BinV
 #define BWD_ARGS_ s.image_width, s.image_height, gx, T, im.tile_desc, (const u32*)b.point_list,                                          \
                   reinterpret_cast<const unsigned char*>(b.reach_mask), (u32)(binned ? 8u : 4u), (const float4*)g.g2d,                  \
                   (const u32*)(binned ? nullptr : g.inst_off), (const u32*)g.block_base, (const float*)s.bg, (const float*)im.final_T,  \
-                  (const u32*)im.n_contrib, grad_color, partials, (int)(compact ? 1 : 0), (const uint4*)im.tile_aux, live_map
-#define BWD_LAUNCH_(ABS_, CMP_, SPARSE_)                                                                                             \
-    do { if (ev_start || ev_stop) hipExtLaunchKernelGGL((blend_bwd_scan_kernel<ABS_, CMP_, SPARSE_>), dim3(grid), dim3(256), 0, st,     \
-                                                        ev_start, ev_stop, 0, BWD_ARGS_);                                             \
-         else LAUNCH_K((blend_bwd_scan_kernel<ABS_, CMP_, SPARSE_>), dim3(grid), dim3(256), 0, st, BWD_ARGS_); } while (0)
+                  (const u32*)im.n_contrib, grad_color, partials, (int)(compact ? 1 : 0), (const uint4*)im.tile_aux, live_map,                 \
+                  grad_depth, grad_weights
+#define BWD_LAUNCH_X_(ABS_, CMP_, SPARSE_, EXTRA_)                                                                                   \
+    do { if (ev_start || ev_stop) hipExtLaunchKernelGGL((blend_bwd_scan_kernel<ABS_, CMP_, SPARSE_, EXTRA_>), dim3(grid), dim3(256), 0, \
+                                                        st, ev_start, ev_stop, 0, BWD_ARGS_);                                         \
+         else LAUNCH_K((blend_bwd_scan_kernel<ABS_, CMP_, SPARSE_, EXTRA_>), dim3(grid), dim3(256), 0, st, BWD_ARGS_); } while (0)
+#define BWD_LAUNCH_(ABS_, CMP_, SPARSE_) do { if (extra) BWD_LAUNCH_X_(ABS_, CMP_, SPARSE_, true); else BWD_LAUNCH_X_(ABS_, CMP_, SPARSE_, false); } while (0)
     // The chunk geometry follows the SCENE, not the dense-scene decision: forcing the dense-scene mode on or off leaves the arithmetic
     // untouched, so the two modes stay bit-identical (tests, tools/fuzz_paths.py --cross-dense)
     // (stock tile rule on the tile-binned path: the chunks are staged from the compacted list of record holders -- ~60 % of the list's
@@ -902,6 +948,7 @@ hipError_t launch_blend_bwd(const BagsSettings& s, const GeomView& g, const BinV
     else          { if (compact) BWD_LAUNCH(false, true); else BWD_LAUNCH(false, false); }
 #undef BWD_LAUNCH
 #undef BWD_LAUNCH_
+#undef BWD_LAUNCH_X_
 #undef BWD_ARGS_
     return hipGetLastError();
 }

@@ -46,7 +46,8 @@ __device__ __forceinline__ float wave_sum(float x)
 // their tile's deepest contributor, 85 % of them at 1800 instances per tile -- hold whatever the buffer held before and are not
 // read.  The live ones are added in the same (slot) order as without the map, so the sums are the same bit for bit: the records
 // skipped are the ones that were zeros.
-template <bool LIVE>
+// EXTRA (BagsExtraGrads): the twelfth float of a record (sum w g_D = dL/dz) is summed too, in the same order as the others.
+template <bool LIVE, bool EXTRA>
 __device__ __forceinline__ void sum_records(u32 nrec, u32 first, const float* __restrict__ partials, const unsigned char* __restrict__ live,
                                             float4& s0, float4& s1, float4& s2)
 {
@@ -81,11 +82,11 @@ __device__ __forceinline__ void sum_records(u32 nrec, u32 first, const float* __
             asm volatile("" :: "v"(a1.x), "v"(b1.x), "v"(c1.x));
             s0.x += a0.x; s0.y += a0.y; s0.z += a0.z; s0.w += a0.w;
             s1.x += b0.x; s1.y += b0.y; s1.z += b0.z; s1.w += b0.w;
-            s2.x += c0.x; s2.y += c0.y; s2.z += c0.z;
+            s2.x += c0.x; s2.y += c0.y; s2.z += c0.z; if (EXTRA) s2.w += c0.w;
             if (two) {
                 s0.x += a1.x; s0.y += a1.y; s0.z += a1.z; s0.w += a1.w;
                 s1.x += b1.x; s1.y += b1.y; s1.z += b1.z; s1.w += b1.w;
-                s2.x += c1.x; s2.y += c1.y; s2.z += c1.z;
+                s2.x += c1.x; s2.y += c1.y; s2.z += c1.z; if (EXTRA) s2.w += c1.w;
             }
         }
     }
@@ -98,16 +99,16 @@ __device__ __forceinline__ void sum_records(u32 nrec, u32 first, const float* __
             const float4 a1 = rec[RQ * r + RQ], b1 = rec[RQ * r + RQ + 1], c1 = rec[RQ * r + RQ + 2];
             s0.x += a0.x; s0.y += a0.y; s0.z += a0.z; s0.w += a0.w;
             s1.x += b0.x; s1.y += b0.y; s1.z += b0.z; s1.w += b0.w;
-            s2.x += c0.x; s2.y += c0.y; s2.z += c0.z;
+            s2.x += c0.x; s2.y += c0.y; s2.z += c0.z; if (EXTRA) s2.w += c0.w;
             s0.x += a1.x; s0.y += a1.y; s0.z += a1.z; s0.w += a1.w;
             s1.x += b1.x; s1.y += b1.y; s1.z += b1.z; s1.w += b1.w;
-            s2.x += c1.x; s2.y += c1.y; s2.z += c1.z;
+            s2.x += c1.x; s2.y += c1.y; s2.z += c1.z; if (EXTRA) s2.w += c1.w;
         }
         if (r < nrec) {
             const float4 a0 = rec[RQ * r], b0 = rec[RQ * r + 1], c0 = rec[RQ * r + 2];
             s0.x += a0.x; s0.y += a0.y; s0.z += a0.z; s0.w += a0.w;
             s1.x += b0.x; s1.y += b0.y; s1.z += b0.z; s1.w += b0.w;
-            s2.x += c0.x; s2.y += c0.y; s2.z += c0.z;
+            s2.x += c0.x; s2.y += c0.y; s2.z += c0.z; if (EXTRA) s2.w += c0.w;
         }
     }
     u64 big = __ballot(nrec > SUM_COOP);
@@ -116,23 +117,25 @@ __device__ __forceinline__ void sum_records(u32 nrec, u32 first, const float* __
         big &= big - 1;
         const u32 bn = __shfl(nrec, src), bf = __shfl(first, src);
         const float4* rec = reinterpret_cast<const float4*>(partials + (size_t)bf * PART_FLOATS);
-        float v[11];
+        constexpr int NV = EXTRA ? 12 : 11;
+        float v[NV];
 #pragma unroll
-        for (int t = 0; t < 11; ++t) v[t] = 0.f;
+        for (int t = 0; t < NV; ++t) v[t] = 0.f;
         for (u32 r = lane; r < bn; r += 64) {
             if (LIVE && live[bf + r] == 0) continue;
             const float4 a0 = rec[RQ * r], b0 = rec[RQ * r + 1], c0 = rec[RQ * r + 2];
             v[0] += a0.x; v[1] += a0.y; v[2] += a0.z; v[3] += a0.w; v[4] += b0.x; v[5] += b0.y; v[6] += b0.z; v[7] += b0.w;
             v[8] += c0.x; v[9] += c0.y; v[10] += c0.z;
+            if (EXTRA) v[NV - 1] += c0.w;
         }
 #pragma unroll
-        for (int t = 0; t < 11; ++t) {
+        for (int t = 0; t < NV; ++t) {
 #pragma unroll
             for (int d = 32; d >= 1; d >>= 1) v[t] += __shfl_xor(v[t], d);
         }
         if (lane == src) {
             s0 = make_float4(v[0], v[1], v[2], v[3]); s1 = make_float4(v[4], v[5], v[6], v[7]);
-            s2 = make_float4(v[8], v[9], v[10], 0.f);
+            s2 = make_float4(v[8], v[9], v[10], EXTRA ? v[NV - 1] : 0.f);
         }
     }
 }
@@ -170,7 +173,8 @@ __device__ __forceinline__ void pose_write_out(const int t, const float val, flo
 
 // ACCUM (BagsBackwardArgs.accumulate): the seven Gaussian-parameter gradients are ADDED to what their buffers hold (several
 // views of one step accumulate in place: no separate add pass per view); means2D / densify / pose outputs are overwritten.
-template <bool COV3D, bool ACCUM, bool LIVE>   // COV3D: precomputed 3D covariances instead of scales + rotations (uniform: no branch at the top)
+// EXTRA: the records' twelfth float (dL/dz from the depth cotangent, BagsExtraGrads) is summed and added to dL/dtzs.
+template <bool COV3D, bool ACCUM, bool LIVE, bool EXTRA>   // COV3D: precomputed 3D covariances instead of scales + rotations (uniform: no branch at the top)
 __global__ void __launch_bounds__(256, PRE_BWD_WAVES)
 preprocess_bwd_kernel(int P, int M, int deg, int W, int H, float tanfovx, float tanfovy, float mod, int clamp_stock, int conic_stock,
                       const float* __restrict__ means3D, const float* __restrict__ shift_factors,
@@ -246,7 +250,7 @@ preprocess_bwd_kernel(int P, int M, int deg, int W, int H, float tanfovx, float 
     // the Gaussian's records (blend_bwd's, `partials` is the record array) summed here, with every other input in flight
     float4 sm_a, sm_b, sm_c;
     __builtin_amdgcn_sched_barrier(0);
-    sum_records<LIVE>(i < P ? n_inst : 0u, first_rec, partials, live_map, sm_a, sm_b, sm_c);
+    sum_records<LIVE, EXTRA>(i < P ? n_inst : 0u, first_rec, partials, live_map, sm_a, sm_b, sm_c);
     // every one of those loads is IN FLIGHT before the first of them is waited for (the compiler otherwise sinks the ones only
     // the visible branch needs behind the visibility test: one more round trip per group)
     asm volatile("" :: "v"(opac), "v"(n_inst), "v"(mj[9]), "v"(x), "v"(y), "v"(z), "v"(in_s0), "v"(in_s1), "v"(in_s2), "v"(in_q.x), "v"(in_c[0]),
@@ -269,7 +273,7 @@ preprocess_bwd_kernel(int P, int M, int deg, int W, int H, float tanfovx, float 
         {
             const float4 a = sm_a, b = sm_b, c = sm_c;
             s[0] = a.x; s[1] = a.y; s[2] = a.z; s[3] = a.w; s[4] = b.x; s[5] = b.y; s[6] = b.z; s[7] = b.w;
-            s[8] = c.x; s[9] = c.y; s[10] = c.z; s[11] = 0.f;
+            s[8] = c.x; s[9] = c.y; s[10] = c.z; s[11] = EXTRA ? c.w : 0.f;
         }
         drgb[0] = s[0]; drgb[1] = s[1]; drgb[2] = s[2];
         // the records carry sum q = o * sum G dL/dalpha (blend_bwd forms q from the unclamped o G): one division per Gaussian
@@ -384,6 +388,7 @@ preprocess_bwd_kernel(int P, int M, int deg, int W, int H, float tanfovx, float 
         const float ditz = dj00 * fx - dj02 * fx * ux + dj11 * fy - dj12 * fy * uy;
         float dtx = 0.f, dty = 0.f, dtz = 0.f;
         float dtzs = -ditz * itz * itz;
+        if (EXTRA) dtzs += s[11];                               // the depth map's z_i is tzs (preprocess_fwd's rgbz.w)
         // Frustum clamp (BagsSettings.clamp_grad).  Upstream's computeCov2DCUDA backward, which the reference's fork inherits
         // (README.md:126): dL/dt.x = x_grad_mul * (-h_x / t.z^2) dL/dJ02 and dL/dt.z takes (2 h_x t.x / t.z^3) dL/dJ02 with the
         // CLAMPED t.x (= ux tzs here) as a constant -- i.e. the unclamped formula with t.x replaced.  BAGS_CLAMP_GRAD_EXACT drops
@@ -638,14 +643,14 @@ pose_reduce_kernel(const float* __restrict__ slab, int nblocks, float* __restric
 
 hipError_t launch_preprocess_bwd(const BagsSettings& s, const BagsInputs& in, const GeomView& g, const int32_t*,
                                  const float* partials_records, float* pose_slab, int* nblocks_out, const BagsBackwardArgs& a,
-                                 hipStream_t st, bool binned, const unsigned char* live_map)
+                                 hipStream_t st, bool binned, const unsigned char* live_map, bool extra)
 {
     const int P = in.P;
     const int nb = cdiv(P, 256);
     *nblocks_out = nb;
     if (P == 0) return hipSuccess;
     const float* partials = partials_records;
-#define PRE_BWD_LAUNCH(COV)     LAUNCH_K((preprocess_bwd_kernel<COV, ACC_, LIVE_>), dim3(nb), dim3(256), 0, st, P, s.sh_coeffs, s.sh_degree, s.image_width, \
+#define PRE_BWD_LAUNCH_X(COV, EXTRA_) LAUNCH_K((preprocess_bwd_kernel<COV, ACC_, LIVE_, EXTRA_>), dim3(nb), dim3(256), 0, st, P, s.sh_coeffs, s.sh_degree, s.image_width, \
                        s.image_height, s.tanfovx, s.tanfovy, s.scale_modifier, (s.clamp_grad == BAGS_CLAMP_GRAD_EXACT) ? 0 : 1, \
                        (s.conic_grad == BAGS_CONIC_GRAD_EXACT) ? 0 : 1, in.means3D, in.shift_factors, in.shs, \
                        in.colors_precomp, in.scales, in.rotations, in.cov3D_precomp, s.viewmatrix, s.projmatrix, \
@@ -654,6 +659,7 @@ hipError_t launch_preprocess_bwd(const BagsSettings& s, const BagsInputs& in, co
                        pose_slab, a.grad_means3D, a.grad_means2D, a.grad_means2D_densify, a.grad_shs, in.shs_rest ? a.grad_shs_rest : nullptr, \
                        (in.shs && !in.colors_precomp) ? a.grad_dldc : nullptr, \
                        a.grad_colors_precomp, a.grad_opacities, a.grad_scales, a.grad_rotations, a.grad_cov3D_precomp);
+#define PRE_BWD_LAUNCH(COV) if (extra) { PRE_BWD_LAUNCH_X(COV, true) } else { PRE_BWD_LAUNCH_X(COV, false) }
 #define PRE_BWD_PICK if (in.cov3D_precomp) { PRE_BWD_LAUNCH(true) } else { PRE_BWD_LAUNCH(false) }
     if (live_map) {
 #define LIVE_ true
@@ -682,6 +688,7 @@ hipError_t launch_preprocess_bwd(const BagsSettings& s, const BagsInputs& in, co
     }
 #undef PRE_BWD_PICK
 #undef PRE_BWD_LAUNCH
+#undef PRE_BWD_LAUNCH_X
     return hipGetLastError();
 }
 

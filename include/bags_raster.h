@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define BAGS_ABI_VERSION 10
+#define BAGS_ABI_VERSION 11
 #define BAGS_TILE 16
 
 enum { BAGS_OK = 0, BAGS_ERR_ARG = -1, BAGS_ERR_HIP = -2, BAGS_ERR_SIZE = -3, BAGS_ERR_DEVICE = -4 };
@@ -225,6 +225,20 @@ int bags_forward_finish_speculative(const BagsSettings*, const BagsInputs*, cons
                                     int64_t capacity, void* stream);
 /* Backward of the whole op from dL/dimage. */
 int bags_backward(const BagsSettings*, const BagsInputs*, const BagsState*, const BagsBackwardArgs*, void* stream);
+
+/* (ABI 11) Cotangents of the forward's depth and weights maps.  depth = sum_i w_i z_i (z_i: view depth with the shift-factor
+ * term, for either depth_key) and weights = 1 - T_final = sum_i w_i composite like two more colour channels (colours z_i and 1,
+ * background 0), so they add z_i dL/ddepth + dL/dweights to every (pixel, splat) term of the colour backward, and sum_i w_i
+ * dL/ddepth reaches the view depth, hence means3D, the pose tensors and shift_factors.  Either pointer may be NULL (= zero). */
+typedef struct BagsExtraGrads {
+    const float* grad_depth;         /* (1,H,W) dL/ddepth   or NULL */
+    const float* grad_weights;       /* (1,H,W) dL/dweights or NULL */
+} BagsExtraGrads;
+/* bags_backward with the extra cotangents.  extra == NULL, or both its pointers NULL: exactly bags_backward (same kernels, same
+ * bits).  Otherwise args->grad_color may be NULL too (= zero: a loss on depth / weights alone).  Every BagsBackwardArgs mode
+ * applies; with `phase` both calls must be given the same extras. */
+int bags_backward_ex(const BagsSettings*, const BagsInputs*, const BagsState*, const BagsBackwardArgs*, const BagsExtraGrads* extra,
+                     void* stream);
 
 /* (ABI 10) The SH-gradient rows of up to BAGS_MAX_SH_VIEWS views of one step from their factored form (BagsBackwardArgs.grad_dldc):
  *   grad_shs[g][t][c] (+)= sum over the views v, in order, of basis_t(normalize(means3D[g] - campos_v)) * dldc_v[g][c]
