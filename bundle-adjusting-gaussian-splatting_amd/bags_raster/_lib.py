@@ -84,8 +84,25 @@ class BagsRawGaussians(C.Structure):
                 ("opacity", C.c_void_p), ("scaling", C.c_void_p), ("rotation", C.c_void_p)]
 
 
-SYMBOLS = {
-    "bags_abi_version": (C.c_int, []),
+ADAM_MAX_GROUPS = 8
+
+
+class BagsAdamGroup(C.Structure):
+    _fields_ = [("param", c_fp), ("grad", c_fp), ("exp_avg", c_fp), ("exp_avg_sq", c_fp), ("width", C.c_int32), ("reserved", C.c_int32),
+                ("step_size", C.c_float), ("bias_correction2_sqrt", C.c_float)]
+
+
+class BagsAdamArgs(C.Structure):
+    _fields_ = [("P", C.c_int32), ("n_groups", C.c_int32), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+                ("visible", c_fp), ("groups", BagsAdamGroup * ADAM_MAX_GROUPS)]
+
+
+class BagsDensifyStats(C.Structure):
+    _fields_ = [("radii", c_fp), ("grad_means2D", c_fp), ("grad_stride", C.c_int32), ("reserved", C.c_int32),
+                ("xyz_gradient_accum", c_fp), ("denom", c_fp), ("max_radii2D", c_fp)]
+
+
+SYMBOLS = {    "bags_abi_version": (C.c_int, []),
     "bags_build_info": (C.c_char_p, []),
     "bags_last_error": (C.c_char_p, []),
     "bags_geom_size": (C.c_size_t, [C.c_int32]),
@@ -128,6 +145,7 @@ SYMBOLS = {
                                [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bags_activations_forward": (C.c_int, [C.POINTER(BagsRawGaussians)] + [C.c_void_p] * 5),
     "bags_activations_backward": (C.c_int, [C.POINTER(BagsRawGaussians)] + [C.c_void_p] * 10),
+    "bags_adam_step": (C.c_int, [C.POINTER(BagsAdamArgs), C.POINTER(BagsDensifyStats), C.c_void_p]),
     "bags_knn_workspace_size": (C.c_size_t, [C.c_int32]),
     "bags_knn_mean_dist2": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "bags_compute_relocation": (C.c_int, [c_fp, c_fp, c_fp, c_fp, C.c_int32, C.c_int32, c_fp, c_fp, C.c_void_p]),

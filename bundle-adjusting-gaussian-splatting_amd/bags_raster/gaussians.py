@@ -11,7 +11,8 @@ Host-side mirror of the pieces of the reference's ``GaussianModel`` that sit on 
 
 Everything here is device-agnostic torch (the reference hard-codes ``device="cuda"``); values are pinned by
 tests/golden/{sh_basis,gaussian_activations}.npz, generated from the reference's own functions.
-Densification, pruning, optimiser plumbing and PLY I/O are out of scope (not on the path).
+Densification and pruning are out of scope (not on the path); the optimizer step is
+``bags_raster.optim.GaussianAdam``, PLY / checkpoint I/O ``bags_raster.io``.
 """
 from __future__ import annotations
 

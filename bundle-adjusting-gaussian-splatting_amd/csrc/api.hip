@@ -732,6 +732,31 @@ int bags_activations_backward(const BagsRawGaussians* r, const float* g_shs, con
     return BAGS_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- optimizer step
+int bags_adam_step(const BagsAdamArgs* a, const BagsDensifyStats* stats, void* stream)
+{
+    if (!a) return fail(BAGS_ERR_ARG, "adam: null struct");
+    if (a->P < 0) return fail(BAGS_ERR_ARG, "adam: P < 0 (got %d)", a->P);
+    if (a->n_groups < 1 || a->n_groups > BAGS_ADAM_MAX_GROUPS)
+        return fail(BAGS_ERR_ARG, "adam: n_groups %d not in 1..%d", a->n_groups, BAGS_ADAM_MAX_GROUPS);
+    for (int k = 0; k < a->n_groups; ++k) {
+        const BagsAdamGroup& g = a->groups[k];
+        if (g.width <= 0) return fail(BAGS_ERR_ARG, "adam: group %d: width %d <= 0", k, g.width);
+        if (g.grad && (!g.param || !g.exp_avg || !g.exp_avg_sq))
+            return fail(BAGS_ERR_ARG, "adam: group %d has a grad but a NULL param / exp_avg / exp_avg_sq", k);
+    }
+    if (stats) {
+        const int given = (stats->radii != nullptr) + (stats->grad_means2D != nullptr) + (stats->xyz_gradient_accum != nullptr) +
+                          (stats->denom != nullptr) + (stats->max_radii2D != nullptr);
+        if (given != 0 && given != 5)
+            return fail(BAGS_ERR_ARG, "adam: stats block needs all of radii, grad_means2D, xyz_gradient_accum, denom, max_radii2D or none (%d of 5 given)", given);
+        if (given == 5 && stats->grad_stride < 2) return fail(BAGS_ERR_ARG, "adam: stats grad_stride %d < 2", stats->grad_stride);
+    }
+    if (a->P == 0) return BAGS_OK;
+    HIP_TRY(launch_adam(*a, stats, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- kNN scale initialiser
 size_t bags_knn_workspace_size(int32_t P) { return knn_workspace_bytes(P > 0 ? P : 1); }
 

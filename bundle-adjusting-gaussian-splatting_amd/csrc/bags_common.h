@@ -232,6 +232,8 @@ hipError_t launch_activations_bwd(int P, int K, const float* dc, const float* re
                                   const float* rotation, const float* g_shs, const float* g_opacity, const float* g_scales,
                                   const float* g_rot, float* g_dc, float* g_rest, float* g_opacity_raw, float* g_scaling,
                                   float* g_rotation, hipStream_t st);
+// adam.hip: torch.optim.Adam step of up to BAGS_ADAM_MAX_GROUPS parameter groups (+ densification statistics) in one launch
+hipError_t launch_adam(const BagsAdamArgs& args, const BagsDensifyStats* stats, hipStream_t st);
 // knn.hip: mean squared distance to the three nearest neighbours (distCUDA2)
 size_t knn_workspace_bytes(int P);
 hipError_t launch_knn(const float* pts, int P, void* ws, float* out, hipStream_t st);

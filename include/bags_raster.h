@@ -359,6 +359,51 @@ int bags_activations_backward(const BagsRawGaussians* raw, const float* g_shs, c
                               const float* g_rotations, float* g_features_dc, float* g_features_rest, float* g_opacity_raw,
                               float* g_scaling, float* g_rotation, void* stream);
 
+/* One optimizer step of the Gaussian parameters: torch.optim.Adam (amsgrad = False, weight_decay = 0, maximize = False) over up to
+ * BAGS_ADAM_MAX_GROUPS parameter groups of one Gaussian count P in ONE launch (csrc/adam.hip).  The reference builds
+ * torch.optim.Adam(l, lr=0.0, eps=1e-15) over xyz, f_dc, f_rest, opacity, scaling, rotation (scene/gaussian_model.py:192-210)
+ * and steps it once per iteration (train.py:420-421).  Per element, fp32, each operation rounded once:
+ *     m = fma(1 - beta1, g - m, m);   v = fma(1 - beta2, g * g, v * beta2);   p = fma(-step_size, m / (sqrt(v) / bias_correction2_sqrt + eps), p)
+ * Every group is a contiguous (P, width) fp32 array.  step_size = lr / (1 - beta1^step) and bias_correction2_sqrt =
+ * sqrt(1 - beta2^step) are the caller's, per group, computed in double as PyTorch does.  A group whose grad is NULL is skipped.
+ * visible (int32 (P), may be NULL; the op's radii fits): row r of every group is updated iff visible[r] > 0; param, exp_avg and
+ * exp_avg_sq of any other row are not written.  NULL updates every row (the reference's behaviour).
+ * No atomics, no host synchronisation, nothing allocated; results are bitwise reproducible, and a row updated under a mask gets
+ * the bits the unmasked step gives it. */
+#define BAGS_ADAM_MAX_GROUPS 8
+typedef struct BagsAdamGroup {
+    float* param;                    /* (P, width), updated in place */
+    const float* grad;               /* (P, width) or NULL: group skipped */
+    float* exp_avg;                  /* (P, width), updated in place */
+    float* exp_avg_sq;               /* (P, width), updated in place */
+    int32_t width;                   /* floats per Gaussian, >= 1 */
+    int32_t reserved;
+    float step_size;                 /* lr / (1 - beta1^step) */
+    float bias_correction2_sqrt;     /* sqrt(1 - beta2^step) */
+} BagsAdamGroup;
+typedef struct BagsAdamArgs {
+    int32_t P, n_groups;             /* n_groups in 1..BAGS_ADAM_MAX_GROUPS */
+    double beta1, beta2, eps;        /* doubles: 1 - beta is formed in double before it is rounded to fp32, as PyTorch forms it */
+    const int32_t* visible;          /* (P) or NULL */
+    BagsAdamGroup groups[BAGS_ADAM_MAX_GROUPS];
+} BagsAdamArgs;
+/* The densification statistics of the same iteration, folded into that launch (GaussianModel.add_densification_stats,
+ * scene/gaussian_model.py:449-455, and train.py's max_radii2D line): for every row with radii > 0
+ *     xyz_gradient_accum += sqrt(gx * gx + gy * gy),  denom += 1,  max_radii2D = max(max_radii2D, (float)radii)
+ * with (gx, gy) the first two floats of the row of grad_means2D (row pitch grad_stride floats, >= 2).  Other rows are not
+ * written.  All five pointers NULL = off; some but not all is an error. */
+typedef struct BagsDensifyStats {
+    const int32_t* radii;            /* (P) */
+    const float* grad_means2D;       /* (P, grad_stride): means2D.grad, or the means2D_densify one for abs_grad */
+    int32_t grad_stride;
+    int32_t reserved;
+    float* xyz_gradient_accum;       /* (P,1) */
+    float* denom;                    /* (P,1) */
+    float* max_radii2D;              /* (P) */
+} BagsDensifyStats;
+/* stats may be NULL.  P == 0 is a successful no-op. */
+int bags_adam_step(const BagsAdamArgs* args, const BagsDensifyStats* stats, void* stream);
+
 /* distCUDA2 of the reference's second native dependency (simple_knn._C, imported at scene/gaussian_model.py:20, called at
  * scene/gaussian_model.py:177 to initialise the scales): out[i] = mean of the squared distances from point i to its three
  * nearest neighbours (self excluded by index; coincident points count with distance 0; with fewer than four points the
