@@ -102,6 +102,25 @@ class BagsDensifyStats(C.Structure):
                 ("xyz_gradient_accum", c_fp), ("denom", c_fp), ("max_radii2D", c_fp)]
 
 
+DENSIFY_MAX_GROUPS = 8
+DENSIFY_MAX_CHILDREN = 16
+ROLE_OTHER, ROLE_XYZ, ROLE_SCALING, ROLE_ROTATION, ROLE_OPACITY = 0, 1, 2, 3, 4
+SCREEN_PUBLISHED, SCREEN_PRE_DENSIFY = 0, 1
+COUNT_KEPT, COUNT_CLONES, COUNT_SPLIT, COUNT_PRUNED, COUNT_P_NEW, COUNT_CLONES_OUT, COUNT_CHILDREN_OUT, DENSIFY_COUNTS = 0, 1, 2, 3, 4, 5, 6, 8
+
+
+class BagsDensifyRule(C.Structure):
+    _fields_ = [("P", C.c_int32), ("N", C.c_int32), ("max_grad", C.c_float), ("min_opacity", C.c_float), ("dense_threshold", C.c_float),
+                ("world_threshold", C.c_float), ("max_screen_size", C.c_float), ("use_screen_size", C.c_int32),
+                ("screen_size_mode", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64), ("noise", c_fp),
+                ("xyz_gradient_accum", c_fp), ("denom", c_fp), ("max_radii2D", c_fp), ("scaling", c_fp), ("opacity", c_fp)]
+
+
+class BagsDensifyGroup(C.Structure):
+    _fields_ = [("param", c_fp), ("exp_avg", c_fp), ("exp_avg_sq", c_fp), ("param_out", c_fp), ("exp_avg_out", c_fp),
+                ("exp_avg_sq_out", c_fp), ("width", C.c_int32), ("role", C.c_int32)]
+
+
 SYMBOLS = {    "bags_abi_version": (C.c_int, []),
     "bags_build_info": (C.c_char_p, []),
     "bags_last_error": (C.c_char_p, []),
@@ -146,6 +165,11 @@ SYMBOLS = {    "bags_abi_version": (C.c_int, []),
     "bags_activations_forward": (C.c_int, [C.POINTER(BagsRawGaussians)] + [C.c_void_p] * 5),
     "bags_activations_backward": (C.c_int, [C.POINTER(BagsRawGaussians)] + [C.c_void_p] * 10),
     "bags_adam_step": (C.c_int, [C.POINTER(BagsAdamArgs), C.POINTER(BagsDensifyStats), C.c_void_p]),
+    "bags_densify_workspace_size": (C.c_size_t, [C.c_int32]),
+    "bags_densify_plan": (C.c_int, [C.POINTER(BagsDensifyRule), C.c_void_p, C.c_size_t, C.POINTER(C.c_int64), C.c_void_p]),
+    "bags_densify_apply": (C.c_int, [C.POINTER(BagsDensifyRule), C.POINTER(BagsDensifyGroup), C.c_int32, C.c_void_p, C.c_size_t, C.c_int64,
+                                     c_fp, c_fp, c_fp, c_fp, C.c_void_p]),
+    "bags_reset_opacity": (C.c_int, [c_fp, c_fp, c_fp, C.c_int32, C.c_void_p]),
     "bags_knn_workspace_size": (C.c_size_t, [C.c_int32]),
     "bags_knn_mean_dist2": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "bags_compute_relocation": (C.c_int, [c_fp, c_fp, c_fp, c_fp, C.c_int32, C.c_int32, c_fp, c_fp, C.c_void_p]),

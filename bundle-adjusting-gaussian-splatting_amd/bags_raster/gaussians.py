@@ -11,7 +11,8 @@ Host-side mirror of the pieces of the reference's ``GaussianModel`` that sit on 
 
 Everything here is device-agnostic torch (the reference hard-codes ``device="cuda"``); values are pinned by
 tests/golden/{sh_basis,gaussian_activations}.npz, generated from the reference's own functions.
-Densification and pruning are out of scope (not on the path); the optimizer step is
+``GaussianBag.densify_and_prune`` and ``GaussianBag.reset_opacity`` (scene/gaussian_model.py:393-447 and ``reset_opacity``) are
+fused HIP calls (csrc/densify.hip) and, unlike the rest of this module, run only on a GPU; the optimizer step is
 ``bags_raster.optim.GaussianAdam``, PLY / checkpoint I/O ``bags_raster.io``.
 """
 from __future__ import annotations
@@ -178,6 +179,156 @@ class GaussianBag:
     def oneupSHdegree(self):
         if self.active_sh_degree < self.max_sh_degree:
             self.active_sh_degree += 1
+
+    # ---- densification (scene/gaussian_model.py:393-447) and opacity reset: csrc/densify.hip
+    _GROUPS = {"xyz": ("_xyz", 1), "f_dc": ("_features_dc", 0), "f_rest": ("_features_rest", 0), "opacity": ("_opacity", 4),
+               "scaling": ("_scaling", 2), "rotation": ("_rotation", 3)}          # group name -> (leaf, BAGS_ROLE_*)
+
+    def _named_groups(self, optimizer, what: str):
+        """{name: (group, parameter, state or None)} of the six groups, each checked to hold this bag's leaf."""
+        found = {}
+        for group in optimizer.param_groups:
+            name = group.get("name")
+            if name in self._GROUPS:
+                if name in found or len(group["params"]) != 1:
+                    raise RuntimeError(f"{what}: the optimizer must hold exactly one group named {name!r} with one parameter")
+                p = group["params"][0]
+                if p is not getattr(self, self._GROUPS[name][0]):
+                    raise RuntimeError(f"{what}: the parameter of group {name!r} is not this bag's {self._GROUPS[name][0]}")
+                st = optimizer.state.get(p, None)
+                found[name] = (group, p, st if st is not None and "exp_avg" in st else None)
+        missing = [n for n in self._GROUPS if n not in found]
+        if missing:
+            raise RuntimeError(f"{what}: the optimizer has no parameter group named {missing[0]!r} (groups are found by their 'name' key: "
+                               f"{', '.join(self._GROUPS)})")
+        return found
+
+    @staticmethod
+    def _check_gpu(what: str, name: str, t: torch.Tensor) -> None:
+        if not t.is_cuda:
+            raise RuntimeError(f"{what} runs only on an AMD GPU: {name} must be on a 'cuda' (ROCm) device, got {t.device}; there is no CPU "
+                               f"fallback")
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise TypeError(f"{what}: {name} must be a contiguous float32 tensor, got {t.dtype}, strides {t.stride()}")
+
+    @torch.no_grad()
+    def densify_and_prune(self, optimizer, max_grad: float, min_opacity: float, extent: float, max_screen_size, percent_dense: float = 0.01,
+                          N: int = 2, noise: Optional[torch.Tensor] = None, seed: Optional[int] = None, screen_size: str = "published"):
+        """``GaussianModel.densify_and_prune`` with its optimizer surgery, in four HIP launches and one host synchronisation.
+
+        Rows whose mean screen-space gradient reaches ``max_grad`` are cloned (largest scale <= ``percent_dense * extent``) or
+        split into ``N`` children (larger); then rows with opacity below ``min_opacity`` and, when ``max_screen_size`` is given,
+        rows larger than ``0.1 * extent`` are pruned.  New ``nn.Parameter`` s are installed in the bag and in
+        ``group["params"][0]``; ``exp_avg`` / ``exp_avg_sq`` follow (kept rows bit for bit, new rows zero), ``step`` stays; the
+        three statistics are zeros of the new size.  Result rows: kept originals, clones, children (child k of the j-th split
+        row at ``k * S + j``), each in source order.
+
+        ``screen_size="published"`` (default) repeats the published order, which zeroes ``max_radii2D`` before the prune step
+        reads it, so that no row is ever pruned for its screen size; ``"pre_densify"`` tests a kept original against the radius
+        it had before the call.  ``noise`` ``(P, N, 3)``: the standard normals of the children, by source row and child;
+        without it they come from a counter-based generator in the kernel keyed by ``(seed, source row, child)``, ``seed`` drawn
+        from torch's CPU generator when None (so ``torch.manual_seed`` governs it).
+
+        Returns a dict: ``kept``, ``clones``, ``split``, ``pruned`` (rows the prune step removed), ``P_new`` and ``provenance``,
+        int32 ``(P_new, 2)`` = (source row, kind: 0 kept, 1 clone, 2 + k child k)."""
+        from . import _lib as L
+        what = "GaussianBag.densify_and_prune"
+        if screen_size not in ("published", "pre_densify"):
+            raise ValueError(f"{what}: screen_size must be 'published' or 'pre_densify', got {screen_size!r}")
+        if not 1 <= int(N) <= L.DENSIFY_MAX_CHILDREN:
+            raise ValueError(f"{what}: N must be in 1..{L.DENSIFY_MAX_CHILDREN}, got {N}")
+        N = int(N)
+        found = self._named_groups(optimizer, what)
+        P = self._xyz.shape[0]
+        dev = self._xyz.device
+        stats = (("xyz_gradient_accum", self.xyz_gradient_accum), ("denom", self.denom), ("max_radii2D", self.max_radii2D))
+        for name, t in [(self._GROUPS[n][0], found[n][1]) for n in found] + list(stats):
+            self._check_gpu(what, name, t)
+            if t.shape[0] != P or t.device != dev:
+                raise RuntimeError(f"{what}: {name} has {t.shape[0]} rows on {t.device}, _xyz {P} on {dev}")
+        for name, t in stats:
+            if t.numel() != P:
+                raise RuntimeError(f"{what}: {name} has {t.numel()} elements for {P} Gaussians")
+        if noise is not None:
+            self._check_gpu(what, "noise", noise)
+            if tuple(noise.shape) != (P, N, 3) or noise.device != dev:
+                raise RuntimeError(f"{what}: noise must be ({P}, {N}, 3) on {dev}, got {tuple(noise.shape)} on {noise.device}")
+        elif seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+        for n, (_, p, st) in found.items():
+            if st is not None:
+                for key in ("exp_avg", "exp_avg_sq"):
+                    self._check_gpu(what, f"{key} of group {n!r}", st[key])
+                    if st[key].shape != p.shape or st[key].device != dev:
+                        raise RuntimeError(f"{what}: {key} of group {n!r} has shape {tuple(st[key].shape)}, its parameter {tuple(p.shape)}")
+        rule = L.BagsDensifyRule(P, N, max_grad, min_opacity, percent_dense * extent, 0.1 * extent,
+                                 0.0 if max_screen_size is None else max_screen_size, 0 if max_screen_size is None else 1,
+                                 L.SCREEN_PRE_DENSIFY if screen_size == "pre_densify" else L.SCREEN_PUBLISHED, 0,
+                                 (0 if seed is None else int(seed)) & (2 ** 64 - 1), None if noise is None else noise.data_ptr(),
+                                 self.xyz_gradient_accum.data_ptr(), self.denom.data_ptr(), self.max_radii2D.data_ptr(),
+                                 self._scaling.data_ptr(), self._opacity.data_ptr())
+        lib = L.load()
+        counts = (L.C.c_int64 * L.DENSIFY_COUNTS)()
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream().cuda_stream
+            ws_bytes = lib.bags_densify_workspace_size(P)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            L.check(lib.bags_densify_plan(rule, ws.data_ptr(), ws_bytes, counts, stream), "bags_densify_plan")
+            P_new = int(counts[L.COUNT_P_NEW])
+            new, groups = {}, []
+            for n, (_, p, st) in found.items():
+                shape = (P_new,) + tuple(p.shape[1:])
+                out = [torch.empty(shape, dtype=torch.float32, device=dev) for _ in range(3 if st is not None else 1)]
+                new[n] = out
+                m, v = (st["exp_avg"], st["exp_avg_sq"]) if st is not None else (None, None)
+                ptr = lambda t: None if t is None else t.data_ptr()
+                groups.append(L.BagsDensifyGroup(p.data_ptr(), ptr(m), ptr(v), out[0].data_ptr(), ptr(out[1] if st is not None else None),
+                                                 ptr(out[2] if st is not None else None), int(math.prod(p.shape[1:])),
+                                                 self._GROUPS[n][1]))
+            accum = torch.empty(P_new, 1, dtype=torch.float32, device=dev)
+            denom = torch.empty(P_new, 1, dtype=torch.float32, device=dev)
+            radii = torch.empty(P_new, dtype=torch.float32, device=dev)
+            prov = torch.empty(P_new, 2, dtype=torch.int32, device=dev)
+            if P > 0:
+                L.check(lib.bags_densify_apply(rule, (L.BagsDensifyGroup * len(groups))(*groups), len(groups), ws.data_ptr(), ws_bytes, P_new,
+                                               accum.data_ptr(), denom.data_ptr(), radii.data_ptr(), prov.data_ptr(), stream),
+                        "bags_densify_apply")
+        for n, (group, p, st) in found.items():
+            param = torch.nn.Parameter(new[n][0].requires_grad_(True))
+            if p in optimizer.state:
+                stored = optimizer.state.pop(p)
+                if st is not None:
+                    stored["exp_avg"], stored["exp_avg_sq"] = new[n][1], new[n][2]
+                optimizer.state[param] = stored
+            group["params"][0] = param
+            setattr(self, self._GROUPS[n][0], param)
+        self.xyz_gradient_accum, self.denom, self.max_radii2D = accum, denom, radii
+        return {"kept": int(counts[L.COUNT_KEPT]), "clones": int(counts[L.COUNT_CLONES]), "split": int(counts[L.COUNT_SPLIT]),
+                "pruned": int(counts[L.COUNT_PRUNED]), "P_new": P_new, "provenance": prov}
+
+    @torch.no_grad()
+    def reset_opacity(self, optimizer) -> None:
+        """``GaussianModel.reset_opacity``: ``_opacity = inverse_sigmoid(min(sigmoid(_opacity), 0.01))`` and zero moments, in one
+        HIP launch and in place (the reference replaces the parameter; the values and the optimizer state are the same)."""
+        from . import _lib as L
+        what = "GaussianBag.reset_opacity"
+        group = [g for g in optimizer.param_groups if g.get("name") == "opacity"]
+        if len(group) != 1 or len(group[0]["params"]) != 1 or group[0]["params"][0] is not self._opacity:
+            raise RuntimeError(f"{what}: the optimizer must hold exactly one group named 'opacity' whose parameter is this bag's _opacity")
+        p = self._opacity
+        self._check_gpu(what, "_opacity", p)
+        st = optimizer.state.get(p, None)
+        m = v = None
+        if st is not None and "exp_avg" in st:
+            m, v = st["exp_avg"], st["exp_avg_sq"]
+            for key, t in (("exp_avg", m), ("exp_avg_sq", v)):
+                self._check_gpu(what, key, t)
+                if t.shape != p.shape or t.device != p.device:
+                    raise RuntimeError(f"{what}: {key} has shape {tuple(t.shape)} on {t.device}, _opacity {tuple(p.shape)} on {p.device}")
+        with torch.cuda.device(p.device):
+            L.check(L.load().bags_reset_opacity(p.data_ptr(), None if m is None else m.data_ptr(), None if v is None else v.data_ptr(),
+                                                p.numel(), torch.cuda.current_stream().cuda_stream), "bags_reset_opacity")
+        p.grad = None
 
     # ---- consumers of the op's screen-space gradients (scene/gaussian_model.py:449-455)
     def add_densification_stats(self, viewspace_point_tensor, viewspace_point_tensor_densify, update_filter, abs_grad: bool):

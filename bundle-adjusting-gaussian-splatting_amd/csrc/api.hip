@@ -757,6 +757,102 @@ int bags_adam_step(const BagsAdamArgs* a, const BagsDensifyStats* stats, void* s
     return BAGS_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- densify-and-prune, opacity reset
+size_t bags_densify_workspace_size(int32_t P) { return densify_workspace_bytes(P); }
+
+static int check_densify_rule(const BagsDensifyRule* r, const void* workspace, size_t workspace_bytes)
+{
+    if (!r) return fail(BAGS_ERR_ARG, "densify: null rule");
+    if (r->P < 0) return fail(BAGS_ERR_ARG, "densify: P < 0 (got %d)", r->P);
+    if (r->N < 1 || r->N > BAGS_DENSIFY_MAX_CHILDREN) return fail(BAGS_ERR_ARG, "densify: N %d not in 1..%d", r->N, BAGS_DENSIFY_MAX_CHILDREN);
+    if (r->screen_size_mode != BAGS_SCREEN_PUBLISHED && r->screen_size_mode != BAGS_SCREEN_PRE_DENSIFY)
+        return fail(BAGS_ERR_ARG, "densify: screen_size_mode %d is neither BAGS_SCREEN_PUBLISHED nor BAGS_SCREEN_PRE_DENSIFY", r->screen_size_mode);
+    if (r->use_screen_size != 0 && r->use_screen_size != 1) return fail(BAGS_ERR_ARG, "densify: use_screen_size %d is not 0 or 1", r->use_screen_size);
+    if (!(r->max_grad == r->max_grad) || !(r->min_opacity == r->min_opacity) || !(r->dense_threshold == r->dense_threshold))
+        return fail(BAGS_ERR_ARG, "densify: max_grad / min_opacity / dense_threshold is NaN");
+    if (r->use_screen_size && (!(r->world_threshold == r->world_threshold) || !(r->max_screen_size == r->max_screen_size)))
+        return fail(BAGS_ERR_ARG, "densify: world_threshold / max_screen_size is NaN");
+    if (r->P == 0) return BAGS_OK;
+    if (!r->xyz_gradient_accum) return fail(BAGS_ERR_ARG, "densify: NULL xyz_gradient_accum");
+    if (!r->denom) return fail(BAGS_ERR_ARG, "densify: NULL denom");
+    if (!r->max_radii2D) return fail(BAGS_ERR_ARG, "densify: NULL max_radii2D");
+    if (!r->scaling) return fail(BAGS_ERR_ARG, "densify: NULL scaling");
+    if (!r->opacity) return fail(BAGS_ERR_ARG, "densify: NULL opacity");
+    if (!workspace) return fail(BAGS_ERR_ARG, "densify: NULL workspace");
+    if (workspace_bytes < densify_workspace_bytes(r->P))
+        return fail(BAGS_ERR_SIZE, "densify: workspace %zu bytes < %zu", workspace_bytes, densify_workspace_bytes(r->P));
+    return BAGS_OK;
+}
+
+int bags_densify_plan(const BagsDensifyRule* r, void* workspace, size_t workspace_bytes, int64_t* host_counts, void* stream)
+{
+    if (const int rc = check_densify_rule(r, workspace, workspace_bytes)) return rc;
+    if (!host_counts) return fail(BAGS_ERR_ARG, "densify: NULL host_counts");
+    for (int k = 0; k < BAGS_DENSIFY_COUNTS; ++k) host_counts[k] = 0;
+    if (r->P == 0) return BAGS_OK;
+    u32 t[5] = {0, 0, 0, 0, 0};                      // kept, clones out, split rows out, clone-selected, split-selected
+    HIP_TRY(launch_densify_plan(*r, workspace, t, (hipStream_t)stream));
+    const int64_t children = (int64_t)t[2] * r->N, P_new = (int64_t)t[0] + t[1] + children;
+    host_counts[BAGS_COUNT_KEPT] = t[0];
+    host_counts[BAGS_COUNT_CLONES] = t[3];
+    host_counts[BAGS_COUNT_SPLIT] = t[4];
+    host_counts[BAGS_COUNT_PRUNED] = (int64_t)r->P + t[3] + (int64_t)t[4] * (r->N - 1) - P_new;
+    host_counts[BAGS_COUNT_P_NEW] = P_new;
+    host_counts[BAGS_COUNT_CLONES_OUT] = t[1];
+    host_counts[BAGS_COUNT_CHILDREN_OUT] = children;
+    if (P_new > 0x7FFFFFFFll) return fail(BAGS_ERR_SIZE, "densify: the new set would hold %lld rows (> 2^31 - 1)", (long long)P_new);
+    return BAGS_OK;
+}
+
+static inline bool misaligned16(const void* p) { return (reinterpret_cast<size_t>(p) & 15u) != 0; }
+
+int bags_densify_apply(const BagsDensifyRule* r, const BagsDensifyGroup* groups, int32_t n_groups, void* workspace, size_t workspace_bytes,
+                       int64_t P_new, float* accum_out, float* denom_out, float* radii_out, int32_t* provenance, void* stream)
+{
+    if (const int rc = check_densify_rule(r, workspace, workspace_bytes)) return rc;
+    if (n_groups < 1 || n_groups > BAGS_DENSIFY_MAX_GROUPS)
+        return fail(BAGS_ERR_ARG, "densify: n_groups %d not in 1..%d", n_groups, BAGS_DENSIFY_MAX_GROUPS);
+    if (!groups) return fail(BAGS_ERR_ARG, "densify: NULL groups");
+    if (P_new < 0 || P_new > (int64_t)r->P * (r->N > 2 ? r->N : 2))
+        return fail(BAGS_ERR_ARG, "densify: P_new %lld not in 0..P * max(2, N)", (long long)P_new);
+    int n_xyz = 0, n_scaling = 0, n_rotation = 0;
+    for (int k = 0; k < n_groups; ++k) {
+        const BagsDensifyGroup& g = groups[k];
+        if (g.width <= 0) return fail(BAGS_ERR_ARG, "densify: group %d: width %d <= 0", k, g.width);
+        if (g.role < BAGS_ROLE_OTHER || g.role > BAGS_ROLE_OPACITY) return fail(BAGS_ERR_ARG, "densify: group %d: unknown role %d", k, g.role);
+        const int want = g.role == BAGS_ROLE_XYZ || g.role == BAGS_ROLE_SCALING ? 3 : g.role == BAGS_ROLE_ROTATION ? 4 : g.role == BAGS_ROLE_OPACITY ? 1 : g.width;
+        if (g.width != want) return fail(BAGS_ERR_ARG, "densify: group %d: width %d, but its role %d has width %d", k, g.width, g.role, want);
+        n_xyz += g.role == BAGS_ROLE_XYZ; n_scaling += g.role == BAGS_ROLE_SCALING; n_rotation += g.role == BAGS_ROLE_ROTATION;
+        if (r->P > 0 && P_new > 0) {
+            const int moments = (g.exp_avg != nullptr) + (g.exp_avg_sq != nullptr) + (g.exp_avg_out != nullptr) + (g.exp_avg_sq_out != nullptr);
+            if (moments != 0 && moments != 4)
+                return fail(BAGS_ERR_ARG, "densify: group %d: exp_avg, exp_avg_sq and their outputs are given together or not at all (%d of 4 given)", k, moments);
+            if (!g.param || !g.param_out) return fail(BAGS_ERR_ARG, "densify: group %d: NULL param / param_out", k);
+            if (misaligned16(g.param_out) || misaligned16(g.exp_avg_out) || misaligned16(g.exp_avg_sq_out))
+                return fail(BAGS_ERR_ARG, "densify: group %d: param_out / exp_avg_out / exp_avg_sq_out is not 16-byte aligned", k);
+        }
+    }
+    if (n_xyz != 1 || n_scaling != 1 || n_rotation != 1)
+        return fail(BAGS_ERR_ARG, "densify: role xyz, scaling and rotation must each be given once (got %d, %d, %d)", n_xyz, n_scaling, n_rotation);
+    if (r->P == 0 || P_new == 0) return BAGS_OK;
+    if (!accum_out || !denom_out || !radii_out) return fail(BAGS_ERR_ARG, "densify: NULL xyz_gradient_accum_out / denom_out / max_radii2D_out");
+    if (misaligned16(accum_out) || misaligned16(denom_out) || misaligned16(radii_out))
+        return fail(BAGS_ERR_ARG, "densify: xyz_gradient_accum_out / denom_out / max_radii2D_out is not 16-byte aligned");
+    if (!provenance) return fail(BAGS_ERR_ARG, "densify: NULL provenance (it is the gather index of the copy)");
+    if (misaligned16(provenance)) return fail(BAGS_ERR_ARG, "densify: provenance is not 16-byte aligned");
+    HIP_TRY(launch_densify_apply(*r, groups, n_groups, workspace, (long long)P_new, accum_out, denom_out, radii_out, provenance, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
+int bags_reset_opacity(float* opacity, float* exp_avg, float* exp_avg_sq, int32_t P, void* stream)
+{
+    if (P < 0) return fail(BAGS_ERR_ARG, "reset_opacity: P < 0 (got %d)", P);
+    if (P == 0) return BAGS_OK;
+    if (!opacity) return fail(BAGS_ERR_ARG, "reset_opacity: NULL opacity");
+    HIP_TRY(launch_reset_opacity(opacity, exp_avg, exp_avg_sq, P, 0.01f, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- kNN scale initialiser
 size_t bags_knn_workspace_size(int32_t P) { return knn_workspace_bytes(P > 0 ? P : 1); }
 

@@ -234,6 +234,12 @@ hipError_t launch_activations_bwd(int P, int K, const float* dc, const float* re
                                   float* g_rotation, hipStream_t st);
 // adam.hip: torch.optim.Adam step of up to BAGS_ADAM_MAX_GROUPS parameter groups (+ densification statistics) in one launch
 hipError_t launch_adam(const BagsAdamArgs& args, const BagsDensifyStats* stats, hipStream_t st);
+// densify.hip: densify-and-prune (decide + scan, then map + gather) and the opacity reset
+size_t densify_workspace_bytes(int P);
+hipError_t launch_densify_plan(const BagsDensifyRule& r, void* workspace, u32 host_totals[5], hipStream_t st);
+hipError_t launch_densify_apply(const BagsDensifyRule& r, const BagsDensifyGroup* groups, int n_groups, void* workspace, long long P_new,
+                                float* accum_out, float* denom_out, float* radii_out, int32_t* provenance, hipStream_t st);
+hipError_t launch_reset_opacity(float* opacity, float* exp_avg, float* exp_avg_sq, int P, float cap, hipStream_t st);
 // knn.hip: mean squared distance to the three nearest neighbours (distCUDA2)
 size_t knn_workspace_bytes(int P);
 hipError_t launch_knn(const float* pts, int P, void* ws, float* out, hipStream_t st);

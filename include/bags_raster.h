@@ -404,6 +404,71 @@ typedef struct BagsDensifyStats {
 /* stats may be NULL.  P == 0 is a successful no-op. */
 int bags_adam_step(const BagsAdamArgs* args, const BagsDensifyStats* stats, void* stream);
 
+/* Densify-and-prune of the Gaussian set and the opacity reset (csrc/densify.hip): GaussianModel.densify_and_prune
+ * (scene/gaussian_model.py:393-447, called from train.py:381-386) with the optimizer surgery of cat_tensors_to_optimizer
+ * (:366-386) and _prune_optimizer (:324-340), and GaussianModel.reset_opacity.  With g = xyz_gradient_accum / denom (NaN -> 0),
+ * s = max(exp(scaling)), o = sigmoid(opacity) of a source row:
+ *   clone  |g| >= max_grad and s <= dense_threshold: the row stays and a copy is appended (moments zero);
+ *   split  |g| >= max_grad and s >  dense_threshold: the row is removed, N children are appended with
+ *          xyz = R(normalize(rotation)) (exp(scaling) * z) + xyz, scaling = log(exp(scaling) / (0.8 N)), the rest copied, moments zero;
+ *   prune  last, every row present then: o < min_opacity, or, with use_screen_size, max_radii2D > max_screen_size or
+ *          s > world_threshold (s of the row itself: a child is tested with its shrunk scale).
+ * The published code zeroes max_radii2D before the prune step reads it (BAGS_SCREEN_PUBLISHED, the default: the radius test sees 0
+ * for every row); BAGS_SCREEN_PRE_DENSIFY tests a kept original against the value it had before the call (clones, children: 0).
+ * Output rows: kept originals in source order, clones in source order, then child k of the j-th surviving split row at k * S + j.
+ * z: noise (P, N, 3), indexed by source row and child, or, with noise NULL, Philox-4x32-10 + Box-Muller keyed by
+ * (seed, source row, child) inside the kernel: independent of the compaction, the same on every rank that passes the same seed.
+ * A kept row keeps parameters and moments bit for bit.  No atomics; results are bitwise reproducible. */
+#define BAGS_DENSIFY_MAX_GROUPS 8
+#define BAGS_DENSIFY_MAX_CHILDREN 16
+enum { BAGS_ROLE_OTHER = 0, BAGS_ROLE_XYZ = 1, BAGS_ROLE_SCALING = 2, BAGS_ROLE_ROTATION = 3, BAGS_ROLE_OPACITY = 4 };
+enum { BAGS_SCREEN_PUBLISHED = 0, BAGS_SCREEN_PRE_DENSIFY = 1 };
+enum { BAGS_COUNT_KEPT = 0, BAGS_COUNT_CLONES = 1, BAGS_COUNT_SPLIT = 2, BAGS_COUNT_PRUNED = 3, BAGS_COUNT_P_NEW = 4,
+       BAGS_COUNT_CLONES_OUT = 5, BAGS_COUNT_CHILDREN_OUT = 6, BAGS_DENSIFY_COUNTS = 8 };
+typedef struct BagsDensifyRule {
+    int32_t P;                       /* source rows */
+    int32_t N;                       /* children per split row, 1..BAGS_DENSIFY_MAX_CHILDREN (the reference: 2) */
+    float max_grad;
+    float min_opacity;
+    float dense_threshold;           /* percent_dense * extent */
+    float world_threshold;           /* 0.1 * extent */
+    float max_screen_size;
+    int32_t use_screen_size;         /* 0: the reference's max_screen_size = None (neither size test) */
+    int32_t screen_size_mode;        /* BAGS_SCREEN_* */
+    int32_t reserved;
+    uint64_t seed;                   /* of the in-kernel generator; unused with noise */
+    const float* noise;              /* (P, N, 3) standard normals or NULL */
+    const float* xyz_gradient_accum; /* (P,1) */
+    const float* denom;              /* (P,1) */
+    const float* max_radii2D;        /* (P) */
+    const float* scaling;            /* (P,3) log-scale */
+    const float* opacity;            /* (P,1) pre-sigmoid */
+} BagsDensifyRule;
+typedef struct BagsDensifyGroup {
+    const float* param;              /* (P, width) */
+    const float* exp_avg;            /* (P, width), or NULL with exp_avg_sq and both outputs: a group without optimizer state */
+    const float* exp_avg_sq;
+    float* param_out;                /* (P_new, width), 16-byte aligned like every output */
+    float* exp_avg_out;
+    float* exp_avg_sq_out;
+    int32_t width;                   /* floats per Gaussian, >= 1 */
+    int32_t role;                    /* BAGS_ROLE_*: xyz, scaling and rotation must each be given exactly once */
+} BagsDensifyGroup;
+/* plan: decide + scan, then ONE stream synchronisation that hands host_counts[BAGS_DENSIFY_COUNTS] to the caller: kept originals,
+ * rows cloned, rows split, rows the prune step removed, P_new, clones and children in the output.  workspace: caller-owned device
+ * memory of the size bags_densify_workspace_size gives for P; it carries the plan to apply.
+ * apply: takes the same rule and workspace and the P_new of the plan, and writes every output array, the three statistics arrays
+ * of the new size (zero) and provenance, int32 (P_new, 2): source row and kind (0 kept, 1 clone, 2 + k child k).  provenance is
+ * required: it is the gather index of the copy.  Outputs must not alias inputs.  P == 0 (plan) and P_new == 0 (apply) are
+ * successful no-ops. */
+size_t bags_densify_workspace_size(int32_t P);
+int bags_densify_plan(const BagsDensifyRule* rule, void* workspace, size_t workspace_bytes, int64_t* host_counts, void* stream);
+int bags_densify_apply(const BagsDensifyRule* rule, const BagsDensifyGroup* groups, int32_t n_groups, void* workspace,
+                       size_t workspace_bytes, int64_t P_new, float* xyz_gradient_accum_out, float* denom_out,
+                       float* max_radii2D_out, int32_t* provenance, void* stream);
+/* GaussianModel.reset_opacity: opacity = logit(min(sigmoid(opacity), 0.01)) in place, its two moments (either may be NULL) zeroed. */
+int bags_reset_opacity(float* opacity, float* exp_avg, float* exp_avg_sq, int32_t P, void* stream);
+
 /* distCUDA2 of the reference's second native dependency (simple_knn._C, imported at scene/gaussian_model.py:20, called at
  * scene/gaussian_model.py:177 to initialise the scales): out[i] = mean of the squared distances from point i to its three
  * nearest neighbours (self excluded by index; coincident points count with distance 0; with fewer than four points the
