@@ -117,78 +117,82 @@ struct ProfScope {
 };
 
 // ---------------------------------------------------------------------------------------------- buffer carving
-template <typename Tp>
-static inline void take(char*& p, Tp*& out, size_t count)
+// (bags_common.h: Carver.  Each function below is the ONE statement of its buffer's layout: the bags_*_size functions call it with
+// a null base, the entry points with the caller's pointer, which is rounded up to 256 here and nowhere else.)
+static size_t carve_geom(void* base, int P, GeomView* v)
 {
-    out = reinterpret_cast<Tp*>(p);
-    p += align_up(count * sizeof(Tp), 256);
-}
-
-size_t carve_geom(void* base, int P, GeomView* v)
-{
-    char* p = reinterpret_cast<char*>(base);
-    GeomView g;
+    Carver c(base);
+    GeomView g{};
     const size_t n = (size_t)(P > 0 ? P : 1);
     g.nblocks_sort = radix_blocks_for((long long)n);
     g.nblocks_scan = cdiv((long long)n, SCAN_TILE);
-    take(p, g.depth_key, n); take(p, g.g2d, 4 * n); take(p, g.rect, n); take(p, g.tiles_touched, n); take(p, g.inst_off, n);
-    take(p, g.keep, n); take(p, g.shjac, 10 * n); take(p, g.rec_count, n);
-    take(p, g.keys_a, n); take(p, g.keys_b, n); take(p, g.vals_a, n); take(p, g.vals_b, n);
-    take(p, g.rank_offset, n);
-    take(p, g.scan_partials, (size_t)g.nblocks_scan + 1);
-    take(p, g.radix_hist, (size_t)RADIX_BINS * g.nblocks_sort);
-    take(p, g.digit_totals, RADIX_BINS);
-    take(p, g.num_rendered, 64);
-    take(p, g.local_off, n); take(p, g.block_total, 256); take(p, g.block_base, 256);
+    g.depth_key = c.take<u32>(n); g.g2d = c.take<float4>(4 * n); g.rect = c.take<uint2>(n); g.tiles_touched = c.take<u32>(n);
+    g.inst_off = c.take<u32>(n); g.keep = c.take<u64>(n); g.shjac = c.take<float>(10 * n); g.rec_count = c.take<u32>(n);
+    g.keys_a = c.take<u32>(n); g.keys_b = c.take<u32>(n); g.vals_a = c.take<u32>(n); g.vals_b = c.take<u32>(n);
+    g.rank_offset = c.take<u32>(n); g.scan_partials = c.take<u32>((size_t)g.nblocks_scan + 1);
+    g.radix_hist = c.take<u32>((size_t)RADIX_BINS * g.nblocks_sort); g.digit_totals = c.take<u32>(RADIX_BINS); g.num_rendered = c.take<u32>(64);
+    g.local_off = c.take<u32>(n); g.block_total = c.take<u32>(256); g.block_base = c.take<u32>(256);
     if (v) *v = g;
-    return (size_t)(p - reinterpret_cast<char*>(base));
+    return c.used();
 }
 
 static int tile_passes(int T) { return (bit_length((u32)(T > 1 ? T - 1 : 1)) + RADIX_BITS - 1) / RADIX_BITS; }
 
-size_t carve_binning(void* base, long long I, int W, int H, BinView* v, bool binned)
+static size_t carve_binning(void* base, long long I, int W, int H, BinView* v, bool binned)
 {
-    char* p = reinterpret_cast<char*>(base);
-    BinView b;
+    Carver c(base);
+    BinView b{};                                             // (what a path does not carve stays null)
     const size_t n = (size_t)(I > 0 ? I : 1);
     const int T = cdiv(W, BAGS_TILE) * cdiv(H, BAGS_TILE);
     b.nblocks_sort = radix_blocks_for((long long)n);
     b.passes = tile_passes(T);
-    b.words = nullptr; b.scratch = nullptr;
     if (binned) {                                            // tile-binned path: 20 bytes per instance
-        take(p, b.words, n); take(p, b.scratch, n); take(p, b.point_list, n);
-        b.keys_a = b.keys_b = b.vals_a = b.vals_b = nullptr; b.ranges = nullptr; b.radix_hist = b.digit_totals = nullptr;
-        b.tile_sorted = nullptr;
+        b.words = c.take<u64>(n); b.scratch = c.take<u64>(n); b.point_list = c.take<u32>(n);
         b.reach_mask = reinterpret_cast<unsigned short*>(b.words);       // the unsorted words are dead after the per-tile sorts
     } else {
-        take(p, b.keys_a, n); take(p, b.vals_a, n); take(p, b.keys_b, n); take(p, b.vals_b, n);
-        take(p, b.ranges, (size_t)(T > 0 ? T : 1));
-        take(p, b.radix_hist, (size_t)RADIX_BINS * b.nblocks_sort);
-        take(p, b.digit_totals, RADIX_BINS);
+        b.keys_a = c.take<u32>(n); b.vals_a = c.take<u32>(n); b.keys_b = c.take<u32>(n); b.vals_b = c.take<u32>(n);
+        b.ranges = c.take<uint2>((size_t)(T > 0 ? T : 1));
+        b.radix_hist = c.take<u32>((size_t)RADIX_BINS * b.nblocks_sort); b.digit_totals = c.take<u32>(RADIX_BINS);
         // emission writes the *_b half; pass 0: b -> a, pass 1: a -> b, ...
         b.point_list = (b.passes & 1) ? b.vals_a : b.vals_b;
         b.tile_sorted = (b.passes & 1) ? b.keys_a : b.keys_b;
         b.reach_mask = reinterpret_cast<unsigned short*>((b.passes & 1) ? b.keys_b : b.keys_a);   // the ping-pong half the last pass read
     }
     if (v) *v = b;
-    return (size_t)(p - reinterpret_cast<char*>(base));
+    return c.used();
 }
 
-size_t carve_image(void* base, int W, int H, ImgView* v)
+static size_t carve_image(void* base, int W, int H, ImgView* v)
 {
-    char* p = reinterpret_cast<char*>(base);
-    ImgView im;
+    Carver c(base);
+    ImgView im{};
     const size_t n = (size_t)W * H > 0 ? (size_t)W * H : 1;
-    take(p, im.final_T, n); take(p, im.n_contrib, n);
+    im.final_T = c.take<float>(n); im.n_contrib = c.take<u32>(n);
     const size_t T = (size_t)cdiv(W > 0 ? W : 1, BAGS_TILE) * cdiv(H > 0 ? H : 1, BAGS_TILE);
-    take(p, im.tile_desc, T); take(p, im.n_active, 64); take(p, im.tile_aux, T);
-    im.cnt_rows = im.pre = im.tile_total = nullptr; im.ranges = nullptr; im.tile_lstart = im.group_total = nullptr;
+    im.tile_desc = c.take<uint4>(T); im.n_active = c.take<u32>(64); im.tile_aux = c.take<uint4>(T);
     if (binned_supported(1, (int)T)) {                        // images the tile-binned path can take (<= 32768 tiles)
-        take(p, im.cnt_rows, 256 * ((T + 1) / 2)); take(p, im.pre, 256 * T); take(p, im.tile_total, T); take(p, im.ranges, T);
-        take(p, im.tile_lstart, T); take(p, im.group_total, 512);
+        im.cnt_rows = c.take<u32>(256 * ((T + 1) / 2)); im.pre = c.take<u32>(256 * T); im.tile_total = c.take<u32>(T);
+        im.ranges = c.take<uint2>(T); im.tile_lstart = c.take<u32>(T); im.group_total = c.take<u32>(512);
     }
     if (v) *v = im;
-    return (size_t)(p - reinterpret_cast<char*>(base));
+    return c.used();
+}
+
+static size_t carve_backward(void* base, int P, long long I, BwdWorkView* v)
+{
+    Carver c(base);
+    BwdWorkView w;
+    const size_t n = (size_t)(I > 0 ? I : 1);
+    w.partials = c.take<float>(n * PART_FLOATS);
+    w.pose_slab = c.take<float>((size_t)cdiv(P > 0 ? P : 1, 256) * POSE_VALS);
+    // Dense-scene mode: one byte per record, + the 64 bytes preprocess_bwd reads from a Gaussian's first mark on (the last Gaussian's
+    // read runs past the last mark).  launch_blend_bwd clears the WHOLE region, a multiple of 256: a fill of whole units is ONE launch
+    // of the runtime's fill kernel -- with an odd tail it was two, ~5.5 us each -- and the bytes behind the last mark are zero.
+    const size_t before = c.used();
+    w.live_map = c.take<unsigned char>(n + 64);
+    w.live_bytes = c.used() - before;
+    if (v) *v = w;
+    return c.used();
 }
 
 // ---------------------------------------------------------------------------------------------- validation
@@ -233,39 +237,37 @@ int bags_abi_version(void) { return BAGS_ABI_VERSION; }
 const char* bags_build_info(void) { return "src=" BAGS_SRC_HASH " commit=" BAGS_KERNEL_COMMIT; }
 const char* bags_last_error(void) { return g_err; }
 
-size_t bags_geom_size(int32_t P) { return carve_geom(nullptr, P, nullptr) + 256; }
+size_t bags_geom_size(int32_t P) { return carve_geom(nullptr, P, nullptr) + BASE_SLACK; }
 size_t bags_binning_size(int64_t I, int32_t W, int32_t H)
 {   // the caller does not know which path a call takes: the larger of the two layouts
     const size_t a = carve_binning(nullptr, I, W, H, nullptr, false), b = carve_binning(nullptr, I, W, H, nullptr, true);
-    return (a > b ? a : b) + 256;
+    return (a > b ? a : b) + BASE_SLACK;
 }
-size_t bags_image_size(int32_t W, int32_t H) { return carve_image(nullptr, W, H, nullptr) + 256; }
-size_t bags_backward_workspace_size(int32_t P, int64_t I)
-{
-    const size_t part = align_up((size_t)(I > 0 ? I : 1) * PART_FLOATS * sizeof(float), 256);
-    const size_t slab = align_up((size_t)(cdiv(P > 0 ? P : 1, 256)) * POSE_VALS * sizeof(float), 256);
-    // dense-scene mode: one byte per record, + the 64 bytes preprocess_bwd reads from a Gaussian's first mark on (launch_blend_bwd clears
-    // the same number of bytes)
-    const size_t live = align_up((size_t)(I > 0 ? I : 1) + 64, 256);
-    return part + slab + live + 256;
-}
+size_t bags_image_size(int32_t W, int32_t H) { return carve_image(nullptr, W, H, nullptr) + BASE_SLACK; }
+size_t bags_backward_workspace_size(int32_t P, int64_t I) { return carve_backward(nullptr, P, I, nullptr) + BASE_SLACK; }
 
-// tile-binned lists (binning.hip) unless the caller asked for the radix path or the problem is outside their limits
-static bool use_binned(const BagsSettings* s, int P)
+// The views of a call's state buffers and its binning path, decided once per entry point.  capacity: what the binning buffer was
+// sized for (the entry point has checked binning_bytes against it), or negative when the call does not touch that buffer.
+struct StateViews { GeomView g; BinView b; ImgView im; bool binned; };
+static StateViews bind_state(const BagsSettings* s, const BagsInputs* in, const BagsState* stt, int64_t capacity)
 {
-    const int T = cdiv(s->image_width, BAGS_TILE) * cdiv(s->image_height, BAGS_TILE);
-    return s->binning != BAGS_BINNING_RADIX && binned_supported(P, T);
+    StateViews v{};
+    const int W = s->image_width, H = s->image_height;
+    // tile-binned lists (binning.hip) unless the caller asked for the radix path or the problem is outside their limits
+    v.binned = s->binning != BAGS_BINNING_RADIX && binned_supported(in->P, cdiv(W, BAGS_TILE) * cdiv(H, BAGS_TILE));
+    carve_geom(stt->geom, in->P, &v.g);
+    carve_image(stt->image, W, H, &v.im);
+    if (capacity >= 0) carve_binning(stt->binning, capacity, W, H, &v.b, v.binned);
+    return v;
 }
-
-static inline void* align256(void* p) { return reinterpret_cast<void*>(align_up(reinterpret_cast<size_t>(p), 256)); }
 
 // K1 + everything the instance count needs; leaves it in g.num_rendered (device)
 // host_count (optional): device-visible address of the caller's pinned host word; when the tile-binned path takes it, the
 // count is written there by the kernel that computes it and *host_written is set (no copy needed)
-static int enqueue_prepare(const BagsSettings* s, const BagsInputs* in, const GeomView& g, const ImgView& im, const BagsForwardOut* out,
+static int enqueue_prepare(const BagsSettings* s, const BagsInputs* in, const StateViews& v, const BagsForwardOut* out,
                            hipStream_t st, u32* host_count = nullptr, bool* host_written = nullptr)
 {
-    const bool binned = use_binned(s, in->P);
+    const GeomView& g = v.g; const ImgView& im = v.im; const bool binned = v.binned;
     { ProfScope ps(ST_PRE_FWD, st, true);
       HIP_TRY(launch_preprocess_fwd(*s, *in, g, out->radii, out->mean2D, st, binned ? &im : nullptr, cdiv(s->image_width, BAGS_TILE))); }
     DEBUG_SYNC(s, st, "preprocess_fwd");
@@ -302,12 +304,13 @@ static int scan_forward(const BagsSettings* s, const BagsInputs* in, const GeomV
 
 // emission, per-tile ordering, blend.  n_dev != nullptr: the instance count is read on the device and checked against
 // `I` (the capacity the binning buffer was sized for)
-static int enqueue_finish(const BagsSettings* s, const BagsInputs* in, const GeomView& g, const BinView& b, const ImgView& im,
-                          const BagsForwardOut* out, int64_t I, const u32* n_dev, hipStream_t st, bool speculative = false)
+static int enqueue_finish(const BagsSettings* s, const BagsInputs* in, const StateViews& v, const BagsForwardOut* out, int64_t I,
+                          const u32* n_dev, hipStream_t st, bool speculative = false)
 {
+    const GeomView& g = v.g; const BinView& b = v.b; const ImgView& im = v.im;
     const int W = s->image_width, H = s->image_height;
     const int gx = cdiv(W, BAGS_TILE), gy = cdiv(H, BAGS_TILE);
-    if (use_binned(s, in->P)) {
+    if (v.binned) {
         if (in->P == 0) HIP_TRY(launch_binned_empty(g, im, gx * gy, st));      // no prepare phase ran: an all-empty tile list
         if (I > 0 && in->P > 0) {
             ProfScope ps(ST_TILE_SORT, st, true);
@@ -344,14 +347,13 @@ int bags_forward_prepare(const BagsSettings* s, const BagsInputs* in, const Bags
     if (rc) return rc;
     if (!out || (in->P > 0 && !out->radii) || !host_num_rendered) return fail(BAGS_ERR_ARG, "radii / host_num_rendered must be given");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    GeomView g; carve_geom(align256(stt->geom), in->P, &g);
-    ImgView im; carve_image(align256(stt->image), s->image_width, s->image_height, &im);
+    const StateViews v = bind_state(s, in, stt, -1);
     *host_num_rendered = 0;
     if (in->P == 0) return BAGS_OK;
-    rc = enqueue_prepare(s, in, g, im, out, st);
+    rc = enqueue_prepare(s, in, v, out, st);
     if (rc) return rc;
     u32 host_I = 0;
-    HIP_TRY(hipMemcpyAsync(&host_I, g.num_rendered, sizeof(u32), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&host_I, v.g.num_rendered, sizeof(u32), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     *host_num_rendered = (int64_t)host_I;
     return BAGS_OK;
@@ -367,12 +369,10 @@ int bags_forward_finish(const BagsSettings* s, const BagsInputs* in, const BagsS
     const int W = s->image_width, H = s->image_height;
     if (!stt->binning || stt->binning_bytes < bags_binning_size(I, W, H)) return fail(BAGS_ERR_SIZE, "binning buffer too small");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    GeomView g; carve_geom(align256(stt->geom), in->P, &g);
-    BinView b; carve_binning(align256(stt->binning), I, W, H, &b, use_binned(s, in->P));
-    ImgView im; carve_image(align256(stt->image), W, H, &im);
+    const StateViews v = bind_state(s, in, stt, I);
     // the count is compared with I on the device as well: a caller-supplied I below the true count renders the overflowing
     // lists empty instead of writing past the binning buffer (same guard as the speculative finish)
-    return enqueue_finish(s, in, g, b, im, out, I, in->P > 0 ? g.num_rendered : nullptr, st);
+    return enqueue_finish(s, in, v, out, I, in->P > 0 ? v.g.num_rendered : nullptr, st);
 }
 
 int bags_forward_prepare_async(const BagsSettings* s, const BagsInputs* in, const BagsState* stt, const BagsForwardOut* out,
@@ -382,10 +382,9 @@ int bags_forward_prepare_async(const BagsSettings* s, const BagsInputs* in, cons
     if (rc) return rc;
     if (!out || (in->P > 0 && !out->radii) || !host_num_rendered) return fail(BAGS_ERR_ARG, "radii / host_num_rendered must be given");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    GeomView g; carve_geom(align256(stt->geom), in->P, &g);
-    ImgView im; carve_image(align256(stt->image), s->image_width, s->image_height, &im);
+    const StateViews v = bind_state(s, in, stt, -1);
     if (in->P == 0) {
-        HIP_TRY(hipMemsetAsync(g.num_rendered, 0, sizeof(u32), st));
+        HIP_TRY(hipMemsetAsync(v.g.num_rendered, 0, sizeof(u32), st));
     } else {
         // a pinned (page-locked, device-mapped) host word can be written by the kernel that computes the count
         u32* dev_alias = nullptr;
@@ -394,11 +393,11 @@ int bags_forward_prepare_async(const BagsSettings* s, const BagsInputs* in, cons
             dev_alias = static_cast<u32*>(attr.devicePointer);
         else (void)hipGetLastError();                         // not a registered pointer: fall back to the copy
         bool written = false;
-        rc = enqueue_prepare(s, in, g, im, out, st, dev_alias, &written);
+        rc = enqueue_prepare(s, in, v, out, st, dev_alias, &written);
         if (rc) return rc;
         if (written) return BAGS_OK;
     }
-    HIP_TRY(hipMemcpyAsync(host_num_rendered, g.num_rendered, sizeof(u32), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(host_num_rendered, v.g.num_rendered, sizeof(u32), hipMemcpyDeviceToHost, st));
     return BAGS_OK;
 }
 
@@ -412,10 +411,8 @@ int bags_forward_finish_speculative(const BagsSettings* s, const BagsInputs* in,
     const int W = s->image_width, H = s->image_height;
     if (!stt->binning || stt->binning_bytes < bags_binning_size(capacity, W, H)) return fail(BAGS_ERR_SIZE, "binning buffer too small");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    GeomView g; carve_geom(align256(stt->geom), in->P, &g);
-    BinView b; carve_binning(align256(stt->binning), capacity, W, H, &b, use_binned(s, in->P));
-    ImgView im; carve_image(align256(stt->image), W, H, &im);
-    return enqueue_finish(s, in, g, b, im, out, capacity, g.num_rendered, st, true);
+    const StateViews v = bind_state(s, in, stt, capacity);
+    return enqueue_finish(s, in, v, out, capacity, v.g.num_rendered, st, true);
 }
 
 int bags_backward(const BagsSettings* s, const BagsInputs* in, const BagsState* stt, const BagsBackwardArgs* a, void* stream)
@@ -447,13 +444,8 @@ int bags_backward_ex(const BagsSettings* s, const BagsInputs* in, const BagsStat
     if (in->shs_rest ? ((a->grad_shs != nullptr) != (a->grad_shs_rest != nullptr)) : (a->grad_shs_rest != nullptr))
         return fail(BAGS_ERR_ARG, "grad_shs_rest goes with inputs.shs_rest, and then grad_shs (features_dc) and grad_shs_rest are given together");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    GeomView g; carve_geom(align256(stt->geom), in->P, &g);
-    BinView b; carve_binning(align256(stt->binning), cap, W, H, &b, use_binned(s, in->P));
-    ImgView im; carve_image(align256(stt->image), W, H, &im);
-    char* ws = reinterpret_cast<char*>(align256(a->workspace));
-    float* partials = reinterpret_cast<float*>(ws);
-    float* slab = reinterpret_cast<float*>(ws + align_up((size_t)(I > 0 ? I : 1) * PART_FLOATS * sizeof(float), 256));
-    unsigned char* live_map = reinterpret_cast<unsigned char*>(slab) + align_up((size_t)(cdiv(in->P > 0 ? in->P : 1, 256)) * POSE_VALS * sizeof(float), 256);
+    const StateViews v = bind_state(s, in, stt, cap);
+    BwdWorkView w; carve_backward(a->workspace, in->P, I, &w);
     // the dense-scene mode (a byte per gradient record instead of zero records) is decided HERE, once: both launchers get the map or null
     const bool dense = I > 0 && bwd_dense_mode(I, cdiv(W, BAGS_TILE) * cdiv(H, BAGS_TILE), a->dense_per_tile);
     if (I > 0 && a->phase != BAGS_BWD_PREPROCESS) {
@@ -464,17 +456,17 @@ int bags_backward_ex(const BagsSettings* s, const BagsInputs* in, const BagsStat
         // box of round 5), i.e. the measurement slowed down what it measured.
         hipEvent_t ea = nullptr, eb = nullptr;
         if (g_prof_mode == 1 && (g_prof_seq.fetch_add(1, std::memory_order_relaxed) % (unsigned long long)g_prof_stride) == 0ull) { ea = prof_event(); eb = prof_event(); }
-        { ProfScope ps(ST_BLEND_BWD, st, true); HIP_TRY(launch_blend_bwd(*s, g, b, im, a->grad_color, partials, a->grad_means2D_densify != nullptr, use_binned(s, in->P), st,
-                                                                  I, dense ? live_map : nullptr, ea, eb, grad_depth, grad_weights)); }
+        { ProfScope ps(ST_BLEND_BWD, st, true); HIP_TRY(launch_blend_bwd(*s, v.g, v.b, v.im, a->grad_color, w.partials, a->grad_means2D_densify != nullptr, v.binned, st,
+                                                                  I, dense ? w.live_map : nullptr, w.live_bytes, ea, eb, grad_depth, grad_weights)); }
         if (ea) { std::lock_guard<std::mutex> lk(g_prof_mutex); g_prof_pending.push_back({ST_BLEND_BWD, ea, eb}); }
         DEBUG_SYNC(s, st, "blend_bwd");
     }
     if (a->phase == BAGS_BWD_BLEND) return BAGS_OK;          // the per-Gaussian half comes with a second call (BAGS_BWD_PREPROCESS)
     int nblocks = 0;
-    { ProfScope ps(ST_PRE_BWD, st, true); HIP_TRY(launch_preprocess_bwd(*s, *in, g, nullptr, partials, slab, &nblocks, *a, st, use_binned(s, in->P), dense ? live_map : nullptr,
+    { ProfScope ps(ST_PRE_BWD, st, true); HIP_TRY(launch_preprocess_bwd(*s, *in, v.g, nullptr, w.partials, w.pose_slab, &nblocks, *a, st, v.binned, dense ? w.live_map : nullptr,
                                                                      extra)); }
     DEBUG_SYNC(s, st, "preprocess_bwd");
-    { ProfScope ps(ST_POSE_REDUCE, st, true); HIP_TRY(launch_pose_reduce(slab, nblocks, *a, st)); }
+    { ProfScope ps(ST_POSE_REDUCE, st, true); HIP_TRY(launch_pose_reduce(w.pose_slab, nblocks, *a, st)); }
     DEBUG_SYNC(s, st, "pose_reduce");
     if (s->debug) {
         const size_t P = (size_t)in->P;
@@ -486,7 +478,7 @@ int bags_backward_ex(const BagsSettings* s, const BagsInputs* in, const BagsStat
                                   {"grad_cov3D_precomp", a->grad_cov3D_precomp, 6 * P}, {"grad_viewmatrix", a->grad_viewmatrix, 16},
                                   {"grad_projmatrix", a->grad_projmatrix, 16}, {"grad_intrinsic", a->grad_intrinsic, 16},
                                   {"grad_campos", a->grad_campos, 3}, {"grad_shift_factors", a->grad_shift_factors, 3}};
-        return debug_scan(s, st, g.num_rendered + 8, items, 15, "the backward", fail);
+        return debug_scan(s, st, v.g.num_rendered + 8, items, 15, "the backward", fail);
     }
     return BAGS_OK;
 }
@@ -516,18 +508,17 @@ int bags_debug_views(const BagsSettings* s, const BagsInputs* in, const BagsStat
     if (!d) return fail(BAGS_ERR_ARG, "null views");
     const int W = s->image_width, H = s->image_height;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    GeomView g; carve_geom(align256(stt->geom), in->P, &g);
-    ImgView im; carve_image(align256(stt->image), W, H, &im);
+    const bool lists = d->point_list || d->keys_sorted || d->ranges;          // the views that live in the binning buffer
+    const StateViews v = bind_state(s, in, stt, lists ? (I > 0 ? I : 0) : -1);
+    const GeomView& g = v.g; const BinView& b = v.b; const ImgView& im = v.im; const bool binned = v.binned;
     const size_t P = (size_t)in->P, T = (size_t)cdiv(W, BAGS_TILE) * cdiv(H, BAGS_TILE);
     if (d->tiles_touched && P) HIP_TRY(hipMemcpyAsync(d->tiles_touched, g.tiles_touched, P * 4, hipMemcpyDeviceToDevice, st));
     if (d->depth_bits && P) HIP_TRY(hipMemcpyAsync(d->depth_bits, g.depth_key, P * 4, hipMemcpyDeviceToDevice, st));
     if (d->rect && P) HIP_TRY(launch_unpack_rect(g.rect, in->P, d->rect, st));
     if (d->n_contrib) HIP_TRY(hipMemcpyAsync(d->n_contrib, im.n_contrib, (size_t)W * H * 4, hipMemcpyDeviceToDevice, st));
     if (d->final_T) HIP_TRY(hipMemcpyAsync(d->final_T, im.final_T, (size_t)W * H * 4, hipMemcpyDeviceToDevice, st));
-    if (d->point_list || d->keys_sorted || d->ranges) {
+    if (lists) {
         if (!stt->binning || stt->binning_bytes < bags_binning_size(I, W, H)) return fail(BAGS_ERR_SIZE, "binning buffer too small");
-        BinView b; carve_binning(align256(stt->binning), I, W, H, &b, use_binned(s, in->P));
-        const bool binned = use_binned(s, in->P);
         const uint2* ranges = binned ? im.ranges : b.ranges;
         if (d->point_list && I) HIP_TRY(hipMemcpyAsync(d->point_list, b.point_list, (size_t)I * 4, hipMemcpyDeviceToDevice, st));
         if (d->keys_sorted && I) {
@@ -863,7 +854,7 @@ int bags_knn_mean_dist2(const float* points, int32_t P, void* workspace, size_t 
     if (!points || !workspace || !out) return fail(BAGS_ERR_ARG, "knn: null pointer");
     if (workspace_bytes < knn_workspace_bytes(P))
         return fail(BAGS_ERR_SIZE, "knn: workspace %zu bytes < %zu", workspace_bytes, knn_workspace_bytes(P));
-    HIP_TRY(launch_knn(points, P, align256(workspace), out, (hipStream_t)stream));
+    HIP_TRY(launch_knn(points, P, workspace, out, (hipStream_t)stream));
     return BAGS_OK;
 }
 

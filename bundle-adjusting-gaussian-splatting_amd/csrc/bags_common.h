@@ -75,7 +75,22 @@ __device__ __forceinline__ int rect_nth_tile(u64 keep, u32 n)
     return __ffsll((long long)keep) - 1;
 }
 
-// ---- carved views of the three caller-owned state buffers -------------------------------------------------
+// ---- carving of the caller-owned buffers ------------------------------------------------------------------
+// Every buffer the library works in is the caller's.  ONE layout function per buffer walks a Carver over it, fills a plain view
+// struct and returns used(); the buffer's size function is the same walk over a null base (sizing mode: the pointers it hands
+// out are never dereferenced) plus the buffer's slack, so a size and its layout cannot drift apart.
+struct Carver {
+    size_t base, pos;
+    // round_base: start at the next multiple of 256 (the buffer's size then carries BASE_SLACK); false: the base as given
+    explicit Carver(const void* b, bool round_base = true)
+        : base(round_base ? align_up(reinterpret_cast<size_t>(b), 256) : reinterpret_cast<size_t>(b)), pos(base) {}
+    // `count` elements of T; the next region starts 256 bytes aligned again
+    template <typename T> T* take(size_t count) { T* out = reinterpret_cast<T*>(pos); pos += align_up(count * sizeof(T), 256); return out; }
+    size_t used() const { return pos - base; }                // bytes handed out so far
+};
+static const size_t BASE_SLACK = 256;     // what rounding the caller's pointer up to 256 can cost (it costs at most 255)
+
+// ---- carved views of the caller-owned state buffers (api.hip: carve_geom / _binning / _image / _backward) -----
 struct GeomView {            // per Gaussian, indexed by Gaussian id unless stated
     u32*    depth_key;       // float bits of the sort depth, KEY_CULLED when not rendered
     // One 64-byte line per Gaussian with everything the blend kernels gather per (tile, Gaussian) instance, so an
@@ -147,6 +162,11 @@ struct ImgView {
     u32*   tile_lstart;      // [T] first instance of a tile relative to its group of 64 tiles (tile_prefix_kernel)
     u32*   group_total;      // [512] instances per group of 64 tiles
 };
+struct BwdWorkView {         // the backward workspace
+    float* partials;         // [I] one record of PART_FLOATS floats per sorted instance (blend_bwd -> preprocess_bwd)
+    float* pose_slab;        // [ceil(P / 256)] rows of POSE_VALS (preprocess_bwd -> pose_reduce)
+    unsigned char* live_map; size_t live_bytes;   // dense-scene mode: one byte per record; the bytes launch_blend_bwd clears
+};
 
 // ---- kernel launches that can carry the stage profiler's events ON THEIR OWN DISPATCH (hipExtLaunchKernelGGL: the timestamps of the
 // kernel's completion signal) instead of between two hipEventRecord packets.  The profiler (api.hip: ProfScope) parks a start / stop pair
@@ -169,9 +189,6 @@ static inline void launch_k(void (*kernel)(KArgs...), dim3 grid, dim3 block, siz
 
 int radix_items_for(long long n);
 int radix_blocks_for(long long n);
-size_t carve_geom(void* base, int P, GeomView* v);
-size_t carve_binning(void* base, long long I, int W, int H, BinView* v, bool binned = false);
-size_t carve_image(void* base, int W, int H, ImgView* v);
 
 // ---- launchers (each enqueues on `st`; returns hipError_t) --------------------------------------------------
 // count_into != nullptr (tile-binned path): K1 also counts the (block of Gaussians, tile) matrix and the block-local instance
@@ -195,6 +212,7 @@ hipError_t launch_blend_bwd(const BagsSettings& s, const GeomView& g, const BinV
                             const float* grad_color, float* partials, bool want_abs, bool binned, hipStream_t st,
                             long long n_records = 0,                      // instance count
                             unsigned char* live_map = nullptr,            // one byte per record (dense-scene mode: the caller's decision), or null
+                            size_t live_bytes = 0,                        // ... and the bytes of it to clear (BwdWorkView::live_bytes)
                             hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr,   // attached to the kernel's dispatch when given
                             const float* grad_depth = nullptr, const float* grad_weights = nullptr);   // BagsExtraGrads (ABI 11)
 bool bwd_dense_mode(long long n_records, int T, int dense_per_tile);      // does a backward of this size run in dense-scene mode?

@@ -908,7 +908,7 @@ bool bwd_dense_mode(long long n_records, int T, int dense_per_tile_arg)
 // grad_depth / grad_weights (BagsExtraGrads): the EXTRA instances run when either is given (grad_color may then be null as well).
 hipError_t launch_blend_bwd(const BagsSettings& s, const GeomView& g, const BinView& b, const ImgView& im,
                             const float* grad_color, float* partials, bool want_abs, bool binned, hipStream_t st,
-                            long long n_records, unsigned char* live_map, hipEvent_t ev_start, hipEvent_t ev_stop,
+                            long long n_records, unsigned char* live_map, size_t live_bytes, hipEvent_t ev_start, hipEvent_t ev_stop,
                             const float* grad_depth, const float* grad_weights)
 {
     const bool extra = grad_depth != nullptr || grad_weights != nullptr;
@@ -919,10 +919,8 @@ hipError_t launch_blend_bwd(const BagsSettings& s, const GeomView& g, const BinV
     const bool compact = binned && s.tile_bounds != BAGS_TILES_OPACITY;
     // Dense scenes (long tile lists, most of each list behind the deepest contributor): clearing the record array with one
     // streaming memset is cheaper than the per-tile zero loops, which gather an id and two geometry lines per dead instance.
-    // (the map is carved 256-byte aligned, in 256-byte units, with room for the 64 bytes preprocess_bwd reads from a mark on --
-    // bags_backward_workspace_size: a fill of whole units is ONE launch of the runtime's fill kernel; with the odd tail it was two, ~5.5 us
-    // each -- and the bytes behind the last mark are zero rather than arbitrary)
-    if (live_map) { hipError_t e = hipMemsetAsync(live_map, 0, ((size_t)n_records + 64 + 255) / 256 * 256, st); if (e != hipSuccess) return e; }
+    // (live_bytes: the map's whole region as carve_backward laid it out, slack behind the last mark included)
+    if (live_map) { hipError_t e = hipMemsetAsync(live_map, 0, live_bytes, st); if (e != hipSuccess) return e; }
     // (ev_start / ev_stop: the stage profiler's events ride on this dispatch -- bags_backward says why)
 #define BWD_ARGS_ s.image_width, s.image_height, gx, T, im.tile_desc, (const u32*)b.point_list,                                          \
                   reinterpret_cast<const unsigned char*>(b.reach_mask), (u32)(binned ? 8u : 4u), (const float4*)g.g2d,                  \

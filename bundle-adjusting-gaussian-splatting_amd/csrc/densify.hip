@@ -32,22 +32,18 @@ struct DensWorkspace { u32* cls; u32* sums; u32* totals; int nb; };
 
 static inline int dens_blocks(int P) { return (int)(((size_t)P + DENS_BLOCK - 1) / DENS_BLOCK); }
 
-size_t densify_workspace_bytes(int P)
+// workspace (base rounded up here): [cls P: a row's flag word | sums nb * DENS_COUNTS: per-workgroup counts | totals DENS_COUNTS]
+static size_t carve_densify(void* base, int P, DensWorkspace* out)
 {
-    const size_t nb = (size_t)dens_blocks(P > 0 ? P : 1);
-    return 256 + align_up((size_t)(P > 0 ? P : 1) * 4, 256) + align_up(nb * DENS_COUNTS * 4, 256) + 256;
-}
-
-static DensWorkspace carve(void* base, int P)
-{
-    char* p = reinterpret_cast<char*>(align_up(reinterpret_cast<size_t>(base), 256));
+    Carver c(base);
+    const int n = P > 0 ? P : 1;
     DensWorkspace w;
-    w.nb = dens_blocks(P);
-    w.cls = reinterpret_cast<u32*>(p);    p += align_up((size_t)P * 4, 256);
-    w.sums = reinterpret_cast<u32*>(p);   p += align_up((size_t)w.nb * DENS_COUNTS * 4, 256);
-    w.totals = reinterpret_cast<u32*>(p);
-    return w;
+    w.nb = dens_blocks(n);
+    w.cls = c.take<u32>((size_t)n); w.sums = c.take<u32>((size_t)w.nb * DENS_COUNTS); w.totals = c.take<u32>(DENS_COUNTS);
+    if (out) *out = w;
+    return c.used();
 }
+size_t densify_workspace_bytes(int P) { return carve_densify(nullptr, P, nullptr) + BASE_SLACK; }
 
 // ------------------------------------------------------------------------------------------------ decide
 struct DecideParams {
@@ -291,7 +287,7 @@ __global__ void __launch_bounds__(DENS_BLOCK) reset_opacity_kernel(float* __rest
 // ------------------------------------------------------------------------------------------------ launchers (arguments validated by api.hip)
 hipError_t launch_densify_plan(const BagsDensifyRule& r, void* workspace, u32 host_totals[DENS_COUNTS], hipStream_t st)
 {
-    const DensWorkspace w = carve(workspace, r.P);
+    DensWorkspace w; carve_densify(workspace, r.P, &w);
     DecideParams d;
     d.accum = r.xyz_gradient_accum; d.denom = r.denom; d.radii = r.max_radii2D; d.scaling = r.scaling; d.opacity = r.opacity;
     d.max_grad = r.max_grad; d.min_opacity = r.min_opacity; d.dense_thr = r.dense_threshold; d.world_thr = r.world_threshold;
@@ -309,7 +305,7 @@ hipError_t launch_densify_plan(const BagsDensifyRule& r, void* workspace, u32 ho
 hipError_t launch_densify_apply(const BagsDensifyRule& r, const BagsDensifyGroup* groups, int n_groups, void* workspace, long long P_new,
                                 float* accum_out, float* denom_out, float* radii_out, int32_t* provenance, hipStream_t st)
 {
-    const DensWorkspace w = carve(workspace, r.P);
+    DensWorkspace w; carve_densify(workspace, r.P, &w);
     hipLaunchKernelGGL(densify_map_kernel, dim3((unsigned)w.nb), dim3(DENS_BLOCK), 0, st, w.cls, w.sums, w.totals, w.nb, r.P, r.N, P_new,
                        reinterpret_cast<int2*>(provenance));
     ApplyParams a;

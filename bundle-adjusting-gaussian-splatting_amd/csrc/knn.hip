@@ -215,47 +215,43 @@ knn_search_kernel(const float4* __restrict__ sorted, int P, const KnnGrid* __res
     out[__float_as_uint(p.w)] = (b0 + b1 + b2) / 3.0f;
 }
 
-// workspace: [box 8 u32 | grid | counts (P+1) | cell_start (P+2) | fill (P+1) | cell_id P | partials | sorted P float4]
-static size_t knn_carve(void* base, int P, u32** box, KnnGrid** grid, u32** counts, u32** start, u32** fill, u32** cid,
-                        u32** partials, float4** sorted)
+struct KnnWork { u32* box; KnnGrid* grid; u32 *counts, *fill, *start, *cid, *partials; float4* sorted; };
+
+// workspace (base rounded up here): [box 8 u32 | grid | counts (P+1) | fill (P+1) | cell_start (P+2) | cell_id P | partials | sorted P float4]
+// counts, fill, start stay in this order: launch_knn clears counts AND fill with ONE memset that runs from counts up to start.
+static size_t knn_carve(void* base, int P, KnnWork* w)
 {
-    char* p = reinterpret_cast<char*>(base);
+    Carver c(base);
     const size_t n = (size_t)(P > 0 ? P : 1);
-    auto take = [&](size_t bytes) { char* q = p; p += align_up(bytes, 256); return q; };
-    u32* b = reinterpret_cast<u32*>(take(8 * sizeof(u32)));
-    KnnGrid* g = reinterpret_cast<KnnGrid*>(take(sizeof(KnnGrid)));
-    u32* c = reinterpret_cast<u32*>(take((n + 1) * sizeof(u32)));
-    u32* f = reinterpret_cast<u32*>(take((n + 1) * sizeof(u32)));          // counts and fill are adjacent: one memset
-    u32* s = reinterpret_cast<u32*>(take((n + 2) * sizeof(u32)));
-    u32* ci = reinterpret_cast<u32*>(take(n * sizeof(u32)));
-    u32* pa = reinterpret_cast<u32*>(take(((n + 1) / KSCAN_TILE + 2) * sizeof(u32)));
-    float4* so = reinterpret_cast<float4*>(take(n * sizeof(float4)));
-    if (box) { *box = b; *grid = g; *counts = c; *fill = f; *start = s; *cid = ci; *partials = pa; *sorted = so; }
-    return (size_t)(p - reinterpret_cast<char*>(base));
+    KnnWork k;
+    k.box = c.take<u32>(8); k.grid = c.take<KnnGrid>(1);
+    k.counts = c.take<u32>(n + 1); k.fill = c.take<u32>(n + 1); k.start = c.take<u32>(n + 2);
+    k.cid = c.take<u32>(n); k.partials = c.take<u32>((n + 1) / KSCAN_TILE + 2); k.sorted = c.take<float4>(n);
+    if (w) *w = k;
+    return c.used();
 }
 
-size_t knn_workspace_bytes(int P) { return knn_carve(nullptr, P, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) + 256; }
+size_t knn_workspace_bytes(int P) { return knn_carve(nullptr, P, nullptr) + BASE_SLACK; }
 
 hipError_t launch_knn(const float* pts, int P, void* ws, float* out, hipStream_t st)
 {
     if (P <= 0) return hipSuccess;
-    u32 *box, *counts, *start, *fill, *cid, *partials; KnnGrid* grid; float4* sorted;
-    knn_carve(ws, P, &box, &grid, &counts, &start, &fill, &cid, &partials, &sorted);
+    KnnWork k; knn_carve(ws, P, &k);
     hipError_t e;
-    if ((e = hipMemsetAsync(box, 0xFF, 3 * sizeof(u32), st)) != hipSuccess) return e;               // min slots
-    if ((e = hipMemsetAsync(box + 3, 0x00, 3 * sizeof(u32), st)) != hipSuccess) return e;           // max slots
-    const size_t zero_bytes = (size_t)(reinterpret_cast<char*>(start) - reinterpret_cast<char*>(counts));
-    if ((e = hipMemsetAsync(counts, 0, zero_bytes, st)) != hipSuccess) return e;                     // counts + fill
+    if ((e = hipMemsetAsync(k.box, 0xFF, 3 * sizeof(u32), st)) != hipSuccess) return e;             // min slots
+    if ((e = hipMemsetAsync(k.box + 3, 0x00, 3 * sizeof(u32), st)) != hipSuccess) return e;         // max slots
+    const size_t zero_bytes = (size_t)(reinterpret_cast<char*>(k.start) - reinterpret_cast<char*>(k.counts));
+    if ((e = hipMemsetAsync(k.counts, 0, zero_bytes, st)) != hipSuccess) return e;                   // counts + fill
     const int nb = cdiv(P, 256);
-    hipLaunchKernelGGL(knn_bbox_kernel, dim3(nb < 1024 ? nb : 1024), dim3(256), 0, st, pts, P, box);
-    hipLaunchKernelGGL(knn_setup_kernel, dim3(1), dim3(64), 0, st, (const u32*)box, P, grid);
-    hipLaunchKernelGGL(knn_count_kernel, dim3(nb), dim3(256), 0, st, pts, P, (const KnnGrid*)grid, counts, cid);
+    hipLaunchKernelGGL(knn_bbox_kernel, dim3(nb < 1024 ? nb : 1024), dim3(256), 0, st, pts, P, k.box);
+    hipLaunchKernelGGL(knn_setup_kernel, dim3(1), dim3(64), 0, st, (const u32*)k.box, P, k.grid);
+    hipLaunchKernelGGL(knn_count_kernel, dim3(nb), dim3(256), 0, st, pts, P, (const KnnGrid*)k.grid, k.counts, k.cid);
     const int n = P + 1;                                                 // scan over the cell capacity (>= ncells)
     const int nparts = cdiv(n, KSCAN_TILE);
-    hipLaunchKernelGGL(knn_scan_partial_kernel, dim3(nparts), dim3(KSCAN_BLOCK), 0, st, (const u32*)counts, n, partials);
-    hipLaunchKernelGGL(knn_scan_top_kernel, dim3(1), dim3(256), 0, st, partials, nparts);
-    hipLaunchKernelGGL(knn_scan_final_kernel, dim3(nparts), dim3(KSCAN_BLOCK), 0, st, (const u32*)counts, n, (const u32*)partials, start);
-    hipLaunchKernelGGL(knn_scatter_kernel, dim3(nb), dim3(256), 0, st, pts, P, (const u32*)cid, (const u32*)start, fill, sorted);
-    hipLaunchKernelGGL(knn_search_kernel, dim3(nb), dim3(256), 0, st, (const float4*)sorted, P, (const KnnGrid*)grid, (const u32*)start, out);
+    hipLaunchKernelGGL(knn_scan_partial_kernel, dim3(nparts), dim3(KSCAN_BLOCK), 0, st, (const u32*)k.counts, n, k.partials);
+    hipLaunchKernelGGL(knn_scan_top_kernel, dim3(1), dim3(256), 0, st, k.partials, nparts);
+    hipLaunchKernelGGL(knn_scan_final_kernel, dim3(nparts), dim3(KSCAN_BLOCK), 0, st, (const u32*)k.counts, n, (const u32*)k.partials, k.start);
+    hipLaunchKernelGGL(knn_scatter_kernel, dim3(nb), dim3(256), 0, st, pts, P, (const u32*)k.cid, (const u32*)k.start, k.fill, k.sorted);
+    hipLaunchKernelGGL(knn_search_kernel, dim3(nb), dim3(256), 0, st, (const float4*)k.sorted, P, (const KnnGrid*)k.grid, (const u32*)k.start, out);
     return hipGetLastError();
 }

@@ -317,32 +317,32 @@ static LossWindow make_window()
     return w;
 }
 
-size_t loss_workspace_bytes(int C, int H, int W)
-{
-    const size_t n = (size_t)C * H * W;
-    const size_t slots = (size_t)C * cdiv(H, LT) * cdiv(W, LT);
-    return 3 * align_up(n * sizeof(float), 256) + align_up(2 * slots * sizeof(float), 256);
-}
+struct LossWork { float *dmu, *de11, *de12, *partials; };   // three planes for the backward; two partial sums per forward workgroup
 
-static void carve_loss(void* ws, int C, int H, int W, float** dmu, float** de11, float** de12, float** partials)
+// The base is used as given, not rounded up to 256: the size has no slack for that, and launch_loss_bwd picks its vector path
+// from the alignment the planes end up with.
+static size_t carve_loss(const void* ws, int C, int H, int W, LossWork* w)
 {
-    char* p = reinterpret_cast<char*>(ws);
-    const size_t n = align_up((size_t)C * H * W * sizeof(float), 256);
-    *dmu = reinterpret_cast<float*>(p); *de11 = reinterpret_cast<float*>(p + n); *de12 = reinterpret_cast<float*>(p + 2 * n);
-    *partials = reinterpret_cast<float*>(p + 3 * n);
+    Carver c(ws, false);
+    const size_t n = (size_t)C * H * W;
+    LossWork l;
+    l.dmu = c.take<float>(n); l.de11 = c.take<float>(n); l.de12 = c.take<float>(n);
+    l.partials = c.take<float>(2 * (size_t)C * cdiv(H, LT) * cdiv(W, LT));
+    if (w) *w = l;
+    return c.used();
 }
+size_t loss_workspace_bytes(int C, int H, int W) { return carve_loss(nullptr, C, H, W, nullptr); }     // (no slack: see carve_loss)
 
 hipError_t launch_loss_fwd(const float* img, const float* gt, int C, int H, int W, void* ws, float* out_terms, hipStream_t st,
                            bool combined, float lambda_dssim)
 {
-    float *dmu, *de11, *de12, *partials;
-    carve_loss(ws, C, H, W, &dmu, &de11, &de12, &partials);
+    LossWork k; carve_loss(ws, C, H, W, &k);
     const dim3 grid(cdiv(W, LT), cdiv(H, LT), C);
     const LossWindow win = make_window();
     const int vec = ((W & 3) == 0) && (((size_t)img | (size_t)gt) & 15) == 0;
-    hipLaunchKernelGGL(loss_fwd_kernel, grid, dim3(256), 0, st, img, gt, H, W, vec, win, dmu, de11, de12, partials);
+    hipLaunchKernelGGL(loss_fwd_kernel, grid, dim3(256), 0, st, img, gt, H, W, vec, win, k.dmu, k.de11, k.de12, k.partials);
     const int nslots = (int)(grid.x * grid.y * grid.z);
-    hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(256), 0, st, (const float*)partials, nslots,
+    hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(256), 0, st, (const float*)k.partials, nslots,
                        1.0 / ((double)C * H * W), out_terms, combined ? 1 : 0, lambda_dssim);
     return hipGetLastError();
 }
@@ -350,12 +350,11 @@ hipError_t launch_loss_fwd(const float* img, const float* gt, int C, int H, int 
 hipError_t launch_loss_bwd(const float* img, const float* gt, int C, int H, int W, const void* ws, const float* grad_terms,
                            float* grad_img, hipStream_t st, bool combined, float lambda_dssim)
 {
-    float *dmu, *de11, *de12, *partials;
-    carve_loss(const_cast<void*>(ws), C, H, W, &dmu, &de11, &de12, &partials);
+    LossWork k; carve_loss(ws, C, H, W, &k);
     const dim3 grid(cdiv(W, LT), cdiv(H, LT), C);
     const LossWindow win = make_window();
-    const int vec = ((W & 3) == 0) && (((size_t)dmu | (size_t)de11 | (size_t)de12) & 15) == 0;
-    hipLaunchKernelGGL(loss_bwd_kernel, grid, dim3(256), 0, st, img, gt, H, W, vec, win, (const float*)dmu, (const float*)de11,
-                       (const float*)de12, grad_terms, (float)(1.0 / ((double)C * H * W)), grad_img, combined ? 1 : 0, lambda_dssim);
+    const int vec = ((W & 3) == 0) && (((size_t)k.dmu | (size_t)k.de11 | (size_t)k.de12) & 15) == 0;
+    hipLaunchKernelGGL(loss_bwd_kernel, grid, dim3(256), 0, st, img, gt, H, W, vec, win, (const float*)k.dmu, (const float*)k.de11,
+                       (const float*)k.de12, grad_terms, (float)(1.0 / ((double)C * H * W)), grad_img, combined ? 1 : 0, lambda_dssim);
     return hipGetLastError();
 }

@@ -57,7 +57,7 @@ __device__ __forceinline__ void sum_records(u32 nrec, u32 first, const float* __
         // the Gaussian's <= 64 marks first (consecutive bytes, all requested before the first is looked at), then its live records two
         // at a time as below
         // 64 bytes from the Gaussian's first mark on, as four 16-byte loads at whatever alignment, all in flight at once (bytes past its last
-        // mark belong to the next Gaussians or to the 256 bytes of slack behind the map, bags_backward_workspace_size).  Until the end of round 5
+        // mark belong to the next Gaussians or to the slack behind the map, api.hip: carve_backward).  Until the end of round 5
         // this was a loop of eight byte loads per trip: four dependent round trips for the 30 records of a Gaussian at sm 2.0.
         // A mark is 0 or 1: the four of a word gather into four bits with one multiplication.
         struct __attribute__((packed, aligned(1))) U4 { u32 x, y, z, w; };

@@ -364,19 +364,18 @@ hipError_t launch_resample_fwd(const float* image, int C, int H, int W, const fl
 
 static size_t rs_carve(void* base, int H, int W, int Hc, int Wc, RsWork* w)
 {
-    char* p = reinterpret_cast<char*>(align_up(reinterpret_cast<size_t>(base), 256));
+    Carver c(base);                                           // (the base is rounded up here)
     const size_t To = (size_t)cdiv(Wc, RS_TILE) * cdiv(Hc, RS_TILE), Ts = (size_t)cdiv(W, RS_TILE) * cdiv(H, RS_TILE);
     RsWork r;
-    r.gflow = reinterpret_cast<float2*>(p); p += align_up((size_t)Hc * Wc * sizeof(float2), 256);
-    r.bbox = reinterpret_cast<int4*>(p); p += align_up(To * sizeof(int4), 256);
-    r.tmax = reinterpret_cast<float*>(p); p += align_up(To * sizeof(float), 256);
-    r.count = reinterpret_cast<u32*>(p); p += align_up(Ts * sizeof(u32), 256);
-    r.list = reinterpret_cast<u32*>(p); p += align_up(Ts * RS_CAP * sizeof(u32), 256);
-    r.taps = reinterpret_cast<float4*>(p); p += align_up((size_t)Hc * Wc * sizeof(float4), 256);
+    r.gflow = c.take<float2>((size_t)Hc * Wc); r.bbox = c.take<int4>(To); r.tmax = c.take<float>(To);
+    r.count = c.take<u32>(Ts); r.list = c.take<u32>(Ts * RS_CAP); r.taps = c.take<float4>((size_t)Hc * Wc);
     if (w) *w = r;
-    return (size_t)(p - reinterpret_cast<char*>(base));
+    return c.used();
 }
-size_t resample_workspace_bytes(int H, int W, int Hc, int Wc) { return rs_carve(nullptr, H, W, Hc, Wc, nullptr) + 512; }
+// 512: BASE_SLACK for rounding the base up, and 256 bytes more that the layout does not use.  The figure is part of the ABI
+// (callers allocate, and cache their allocations, by it), so the spare 256 stay.
+static const size_t RS_SLACK = 2 * BASE_SLACK;
+size_t resample_workspace_bytes(int H, int W, int Hc, int Wc) { return rs_carve(nullptr, H, W, Hc, Wc, nullptr) + RS_SLACK; }
 
 hipError_t launch_resample_bwd(const float* image, int C, int H, int W, const float* ctrl, int h, int w, int Hf, int Wf, int Hc, int Wc,
                                const float* grad_out, void* workspace, float* grad_image, float* grad_ctrl, hipStream_t st)

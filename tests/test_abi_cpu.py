@@ -39,6 +39,28 @@ def test_buffer_sizes_grow_with_problem(lib):
     assert lib.bags_backward_workspace_size(500_000, 3_700_000) >= 3_700_000 * 48      # one 48-byte record per instance
 
 
+def test_buffer_sizes_match_the_recorded_ones(lib):
+    """The eight size functions are ABI: callers allocate by them, and the operator counts on equal problems giving equal sizes.
+    tests/golden/buffer_sizes.json holds what they reported BEFORE the layouts moved onto one carving helper (written by
+    tests/golden/make_buffer_sizes.py from a build of that earlier commit); every entry must still be reported, to the byte."""
+    import importlib.util
+    import json
+    golden = os.path.join(ROOT, "tests", "golden")
+    spec = importlib.util.spec_from_file_location("make_buffer_sizes", os.path.join(golden, "make_buffer_sizes.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    want = json.load(open(os.path.join(golden, "buffer_sizes.json")))["sizes"]
+    cases = gen.cases()
+    assert len(cases) == 11 + 7 * 6 + 6 + 11 * 7 + 4 + 4 + 11 + 11
+    assert set(want) == {gen.key(name, args) for name, args in cases}
+    wrong = {}
+    for name, args in cases:
+        got = int(getattr(lib, name)(*args))
+        if got != want[gen.key(name, args)]:
+            wrong[gen.key(name, args)] = (got, want[gen.key(name, args)])
+    assert not wrong, wrong
+
+
 def test_struct_layout_matches_header(lib):
     # field counts and pointer-size packing of the POD structs (a mismatch would corrupt every call)
     assert C.sizeof(_lib.BagsSettings) == 14 * 4 + 5 * 8     # + clamp_grad (ABI 5), conic_grad (ABI 8; reserved0 before)
