@@ -11,7 +11,7 @@ import numpy as np
 
 
 def _flow_taps(n_in, n_out, idx):
-    s = np.maximum((idx + 0.5) * (np.float32(n_in) / np.float32(n_out)) - 0.5, 0.0)
+    s = np.maximum((idx + 0.5) * (float(n_in) / float(n_out)) - 0.5, 0.0)      # float64 ratio, as F.interpolate forms it for float64 input
     i0 = np.minimum(s.astype(np.int64), n_in - 1)
     i1 = i0 + (i0 < n_in - 1)
     lam = s - i0
@@ -31,7 +31,13 @@ def _prepare(image, ctrl, flow_hw, crop_hw):
     ix = (flow[0] + 1) / 2 * (W - 1); iy = (flow[1] + 1) / 2 * (H - 1)
     fx0 = np.floor(ix); fy0 = np.floor(iy)
     return dict(C=C, H=H, W=W, h=h, w=w, Hc=Hc, Wc=Wc, yi=yi, xi=xi, wy=wy, wx=wx, fx=ix - fx0, fy=iy - fy0,
-                x0=fx0.astype(np.int64), y0=fy0.astype(np.int64))
+                x0=fx0.astype(np.int64), y0=fy0.astype(np.int64), flow=flow)
+
+
+def interpolated_flow(ctrl, flow_hw, crop_hw):
+    """The control flow upsampled to ``flow_hw`` and cropped to ``crop_hw``: (Hc,Wc,2) float64, the sampling positions that
+    ``forward`` uses (``bags_resample_forward`` returns them in ``flow_out``)."""
+    return _prepare(np.zeros((1, 2, 2)), ctrl, flow_hw, crop_hw)["flow"].transpose(1, 2, 0)
 
 
 def forward(image, ctrl, flow_hw, crop_hw):

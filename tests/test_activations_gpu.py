@@ -61,3 +61,48 @@ def test_activations_without_the_feature_concatenation():
     for a, b in zip(pc1.leaves()[3:], pc0.leaves()[3:]):
         assert torch.equal(a.grad, b.grad)
     assert pc1._features_dc.grad is None and pc1._features_rest.grad is None
+
+
+def test_fused_activations_at_edge_values():
+    """Saturated sigmoid and exp inputs, and quaternions at and around the 1e-12 clamp of normalize (zero, norms 1e-13 and
+    5e-13 below it, 2e-12 just above it, and a single component of 1e-20 whose square underflows), in the first rows of a
+    257-Gaussian set: forward against GaussianBag's properties, backward against their autograd, nothing NaN where PyTorch is
+    finite.  The clamped rows have gradients of ~1e12 and exp(88) of ~1e38, so beside the whole-tensor bar (rtol 1e-4, atol
+    1e-5 of the largest reference gradient) the untouched rows are held to the absolute bar of
+    test_fused_activations_match_properties."""
+    P, deg = 257, 1
+    sc = synth_scene(P, 9, 0.5, deg)
+    g = torch.Generator().manual_seed(4)
+    sc["rotations"] = sc["rotations"] * (0.3 + 2.0 * torch.rand(P, 1, generator=g))
+    pc0 = GaussianBag.from_activated(sc, deg, device=DEV)
+    pc1 = GaussianBag.from_activated(sc, deg, device=DEV)
+    raw_op = torch.tensor([-104.0, -90.0, -20.0, 0.0, 20.0, 90.0, 104.0])
+    raw_sc = torch.tensor([-100.0, -20.0, 0.0, 20.0, 88.0])
+    u = torch.tensor([0.5, -0.5, 0.5, 0.5])
+    quats = torch.stack([torch.zeros(4), 1e-13 * u, 5e-13 * u, 2e-12 * u, torch.tensor([0.0, 1e-20, 0.0, 0.0])])
+    E = 7                                                   # rows that hold an edge value
+    with torch.no_grad():
+        pc0._rotation.copy_(sc["rotations"].to(DEV))
+        pc0._opacity[:7, 0] = raw_op.to(DEV)
+        pc0._scaling[:5] = raw_sc.to(DEV)[:, None].expand(5, 3)
+        pc0._scaling[5] = torch.tensor([88.0, -100.0, 0.0], device=DEV)     # the extremes side by side in one row
+        pc0._rotation[:5] = quats.to(DEV)
+        for a, b in zip(pc0.leaves(), pc1.leaves()):
+            b.copy_(a)
+    want = [pc0.get_xyz, pc0.get_features, pc0.get_opacity, pc0.get_scaling, pc0.get_rotation]
+    got = list(pc1.activated())
+    cots = [(2.0 * torch.rand(w.shape, generator=g) - 1.0).to(DEV) for w in want]      # |cotangent| <= 1: exp(88) * it stays finite
+    for a, b in zip(got, want):
+        assert a.shape == b.shape and torch.allclose(a, b, rtol=2e-6, atol=1e-7), (a - b).abs().max()
+        assert not (torch.isnan(a) & torch.isfinite(b)).any()
+    assert torch.isfinite(want[3]).all() and want[3].max().item() > 1e38 and want[2][0].item() == 0.0 and want[2][6].item() == 1.0
+    torch.autograd.backward(want[1:], cots[1:])
+    torch.autograd.backward(got[1:], cots[1:])
+    for a, b in zip(pc1.leaves()[1:], pc0.leaves()[1:]):
+        assert a.grad is not None and not (torch.isnan(a.grad) & torch.isfinite(b.grad)).any()
+        assert torch.isfinite(b.grad).all()
+        big = b.grad.abs().max().item()
+        assert torch.allclose(a.grad, b.grad, rtol=1e-4, atol=1e-5 * big), (a.grad - b.grad).abs().max()
+        assert torch.allclose(a.grad[E:], b.grad[E:], rtol=1e-4, atol=1e-5), (a.grad[E:] - b.grad[E:]).abs().max()
+    rg = pc0._rotation.grad
+    assert rg[:3].abs().max().item() > 1e11 and rg[4].abs().max().item() > 1e11            # clamped denominator: g / 1e-12

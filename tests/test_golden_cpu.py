@@ -179,6 +179,55 @@ def test_resample_oracle_and_torch_pipeline_match_reference(golden_dir):
     np.testing.assert_allclose(ctl.grad.numpy(), g["d_ctrl"], rtol=1e-4, atol=1e-4)
 
 
+def test_resample_oracle_flow_matches_interpolate(golden_dir):
+    """RO.interpolated_flow (what bags_resample_forward's flow_out is held to) against F.interpolate(bilinear,
+    align_corners=False) in float64 followed by the integer crop, on the golden geometry."""
+    import torch.nn.functional as F
+    from oracle import resample_oracle as RO
+    g = np.load(os.path.join(golden_dir, "resample.npz"))
+    fhw, chw = tuple(int(v) for v in g["flow_hw"]), tuple(int(v) for v in g["crop_hw"])
+    flow = RO.interpolated_flow(g["ctrl"], fhw, chw)
+    assert flow.shape == chw + (2,) and flow.dtype == np.float64
+    up = F.interpolate(torch.from_numpy(g["ctrl"]).double().permute(2, 0, 1).unsqueeze(0), size=fhw, mode="bilinear",
+                       align_corners=False)[0].permute(1, 2, 0).numpy()
+    y0, x0 = (fhw[0] - chw[0]) // 2, (fhw[1] - chw[1]) // 2
+    np.testing.assert_allclose(flow, up[y0:y0 + chw[0], x0:x0 + chw[1]], rtol=0, atol=1e-12)
+
+
+def test_loss_cases_and_float32_error_cpu():
+    """The CPU half of tests/test_loss_gpu.py's measured bar (tests/loss_cases.py): every input class is what it says, and the
+    float32 PyTorch loss is within 1e-6 (relative, gradient) of the float64 oracle except on the flat bright image, where
+    E[a^2] - mu^2 cancels against C2 = 9e-4."""
+    import loss_cases as LC
+    for shape in LC.RAGGED_SHAPES:
+        assert shape[2] % 4 == 0 and shape[2] % 32 != 0
+        for kind in LC.KINDS:
+            a, b = LC.make_pair(kind, shape)
+            a2, b2 = LC.make_pair(kind, shape)
+            assert a.shape == shape and a.dtype == np.float32 and b.dtype == np.float32 and a.flags.c_contiguous
+            assert np.array_equal(a, a2) and np.array_equal(b, b2)
+            if kind == "noise":
+                assert np.array_equal(a[..., : shape[2] // 2], b[..., : shape[2] // 2]) and 0 <= a.min() and a.max() < 1
+            elif kind == "flat_bright":
+                assert abs(a.mean() - 0.9) < 1e-3 and np.abs(a - 0.9).max() < 6e-3 and np.abs(b - 0.9).max() < 6e-3
+            elif kind == "dark":
+                assert 0 <= min(a.min(), b.min()) and max(a.max(), b.max()) < 1e-3
+            elif kind == "out_of_range":
+                assert -1 <= a.min() and a.max() < 2 and 0 <= b.min() and b.max() < 1
+                assert shape[1] * shape[2] < 100 or (a.min() < 0 and a.max() > 1)
+            else:
+                assert set(np.unique(a)) <= {0.0, 1.0} and np.array_equal(a[..., 1:], b[..., :-1])
+                assert np.array_equal(a[:, : max(shape[1] - 7, 0)], 1 - a[:, 7:]) and np.array_equal(a[..., : max(shape[2] - 5, 0)], 1 - a[..., 5:])
+            r = LC.reference(a, b)
+            if r["scale"] == 0.0:                        # the (2,5,4) checkerboard is one cell: both images zero, no gradient
+                assert kind == "checkerboard" and shape == (2, 5, 4) and r["err32_grad"] == 0.0
+            rel = r["err32_grad"] / max(r["scale"], 1e-300)
+            print(f"{kind:13s} {shape}: err32 grad {rel:.2e} rel, l1 {r['err32_l1']:.1e}, ssim {r['err32_ssim']:.1e}")
+            assert np.isfinite(r["grad"]).all()
+            assert rel < (1e-3 if kind == "flat_bright" else 1e-6), (kind, shape, rel)
+            assert r["err32_l1"] < 1e-6 and r["err32_ssim"] < 1e-5
+
+
 def _pose_camera_from_golden(g, i, device="cpu"):
     from bags_raster.camera import PoseCamera
     c = PoseCamera(torch.eye(3), torch.zeros(3), 1.0, 1.0, 64, 48, device=device)
