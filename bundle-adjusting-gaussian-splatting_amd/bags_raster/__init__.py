@@ -7,10 +7,10 @@ from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, rast
                          compute_relocation)
 
 from .render import render, PipelineParams
-from .gaussians import GaussianBag, eval_sh
+from .gaussians import GaussianBag, eval_sh, sh_colors
 from .io import save_ply, load_ply, save_checkpoint, load_checkpoint
 from .optim import GaussianAdam
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "debug_views",
-           "compute_relocation", "render", "PipelineParams", "GaussianBag", "eval_sh",
+           "compute_relocation", "render", "PipelineParams", "GaussianBag", "eval_sh", "sh_colors",
            "save_ply", "load_ply", "save_checkpoint", "load_checkpoint", "GaussianAdam"]

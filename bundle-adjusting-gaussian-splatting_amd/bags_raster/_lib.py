@@ -84,6 +84,11 @@ class BagsRawGaussians(C.Structure):
                 ("opacity", C.c_void_p), ("scaling", C.c_void_p), ("rotation", C.c_void_p)]
 
 
+class BagsShColors(C.Structure):
+    _fields_ = [("P", C.c_int32), ("K", C.c_int32), ("sh_degree", C.c_int32), ("reserved", C.c_int32), ("shs", c_fp), ("shs_rest", c_fp),
+                ("xyz", c_fp), ("campos", c_fp)]
+
+
 ADAM_MAX_GROUPS = 8
 
 
@@ -164,6 +169,9 @@ SYMBOLS = {    "bags_abi_version": (C.c_int, []),
                                [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bags_activations_forward": (C.c_int, [C.POINTER(BagsRawGaussians)] + [C.c_void_p] * 5),
     "bags_activations_backward": (C.c_int, [C.POINTER(BagsRawGaussians)] + [C.c_void_p] * 10),
+    "bags_sh_colors_workspace_size": (C.c_size_t, [C.c_int32]),
+    "bags_sh_colors_forward": (C.c_int, [C.POINTER(BagsShColors), c_fp, C.c_void_p]),
+    "bags_sh_colors_backward": (C.c_int, [C.POINTER(BagsShColors), c_fp, C.c_void_p, C.c_size_t, c_fp, c_fp, c_fp, c_fp, C.c_void_p]),
     "bags_adam_step": (C.c_int, [C.POINTER(BagsAdamArgs), C.POINTER(BagsDensifyStats), C.c_void_p]),
     "bags_densify_workspace_size": (C.c_size_t, [C.c_int32]),
     "bags_densify_plan": (C.c_int, [C.POINTER(BagsDensifyRule), C.c_void_p, C.c_size_t, C.POINTER(C.c_int64), C.c_void_p]),

@@ -5,7 +5,8 @@ Host-side mirror of the pieces of the reference's ``GaussianModel`` that sit on 
   * activations  ``get_xyz / get_scaling / get_rotation / get_opacity / get_features / get_covariance``
     (scene/gaussian_model.py:118-141; set up in ``setup_functions``, scene/gaussian_model.py:26-43)
   * ``build_rotation / build_scaling_rotation / strip_lowerdiag / strip_symmetric`` (utils/general_utils.py:114-163)
-  * ``eval_sh / RGB2SH / SH2RGB`` (utils/sh_utils.py:57-122) -- the Python colour path of ``render()``
+  * ``eval_sh / RGB2SH / SH2RGB`` (utils/sh_utils.py:57-122) -- the Python colour path of ``render()``; on a GPU that path is
+    ``sh_colors``, one HIP launch each way (csrc/sh_colors.hip)
   * the consumers of the op's screen-space gradients, ``add_densification_stats``
     (scene/gaussian_model.py:449-455)
 
@@ -400,3 +401,93 @@ class _FusedActivations(torch.autograd.Function):
 def fused_activations(features_dc, features_rest, opacity, scaling, rotation):
     """(get_features, get_opacity, get_scaling, get_rotation) of scene/gaussian_model.py:118-141 in one HIP launch."""
     return _FusedActivations.apply(features_dc, features_rest, opacity, scaling, rotation)
+
+
+class _ShColors(torch.autograd.Function):
+    """``shs_rest`` None: ``shs`` is the packed (P,K,3) tensor; otherwise ``shs`` (P,1,3) and ``shs_rest`` (P,K-1,3)."""
+
+    @staticmethod
+    def forward(ctx, deg, shs, shs_rest, xyz, campos):
+        from . import _lib as L
+        ts = [None if t is None else t.detach().contiguous() for t in (shs, shs_rest, xyz, campos)]
+        P = ts[2].shape[0]
+        K = ts[0].shape[1] + (0 if ts[1] is None else ts[1].shape[1])
+        rgb = torch.empty(P, 3, dtype=torch.float32, device=ts[2].device)
+        args = L.BagsShColors(P, K, deg, 0, *[None if t is None else t.data_ptr() for t in ts])
+        with torch.cuda.device(rgb.device):
+            L.check(L.load().bags_sh_colors_forward(args, rgb.data_ptr(), torch.cuda.current_stream().cuda_stream), "bags_sh_colors_forward")
+        ctx.deg, ctx.split = deg, ts[1] is not None
+        ctx.save_for_backward(*[t for t in ts if t is not None])       # the inputs and nothing else: the clamp mask is recomputed
+        ctx.set_materialize_grads(False)
+        return rgb
+
+    @staticmethod
+    def backward(ctx, g_rgb):
+        from . import _lib as L
+        if g_rgb is None:
+            return None, None, None, None, None
+        ts = list(ctx.saved_tensors)
+        if not ctx.split:
+            ts.insert(1, None)
+        shs, rest, xyz, campos = ts
+        P = xyz.shape[0]
+        K = shs.shape[1] + (0 if rest is None else rest.shape[1])
+        need = ctx.needs_input_grad
+        g_rgb = g_rgb.to(torch.float32).contiguous()
+        out = [torch.empty_like(t) if (t is not None and need[k]) else None for k, t in ((1, shs), (2, rest), (3, xyz), (4, campos))]
+        p = lambda t: None if t is None else t.data_ptr()
+        args = L.BagsShColors(P, K, ctx.deg, 0, p(shs), p(rest), p(xyz), p(campos))
+        lib = L.load()
+        with torch.cuda.device(xyz.device):
+            ws_bytes = lib.bags_sh_colors_workspace_size(P) if out[3] is not None else 0
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=xyz.device) if ws_bytes else None
+            L.check(lib.bags_sh_colors_backward(args, g_rgb.data_ptr(), p(ws), ws_bytes, *[p(o) for o in out],
+                                                torch.cuda.current_stream().cuda_stream), "bags_sh_colors_backward")
+        return (None,) + tuple(out)
+
+
+def sh_colors(deg: int, shs: torch.Tensor, xyz: torch.Tensor, campos: torch.Tensor, shs_rest: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``clamp_min(eval_sh(deg, shs, normalize(xyz - campos)) + 0.5, 0)`` -> ``(P,3)``: the Python colour path of ``render()``
+    (gaussian_renderer/__init__.py:90-95) in one HIP launch each way, gradients to the coefficients, ``xyz`` and ``campos``.
+
+    ``shs`` is the ``(P,K,3)`` feature tensor, or, with ``shs_rest (P,K-1,3)``, the ``(P,1,3)`` DC part: the two stored parameters
+    go in as they are, without ``get_features``' concatenation.  K is 1, 4, 9 or 16 and at least ``(deg+1)^2``; the gradient of the
+    stored rows beyond the active degree is exactly zero.  float32 tensors on a GPU; there is no CPU fallback (use ``eval_sh``)."""
+    what = "sh_colors"
+    deg = int(deg)
+    if not 0 <= deg <= 3:
+        raise ValueError(f"{what}: SH degree must be in 0..3, got {deg}")
+    named = [("shs", shs), ("xyz", xyz), ("campos", campos)] + ([("shs_rest", shs_rest)] if shs_rest is not None else [])
+    for name, t in named:
+        if not torch.is_tensor(t):
+            raise TypeError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
+        if t.dtype != torch.float32:
+            raise TypeError(f"{what}: {name} must be float32, got {t.dtype}")
+    if xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise RuntimeError(f"{what}: xyz must be (P,3), got {tuple(xyz.shape)}")
+    P = xyz.shape[0]
+    if tuple(campos.shape) != (3,):
+        raise RuntimeError(f"{what}: campos must be (3,), got {tuple(campos.shape)}")
+    if shs_rest is None:
+        if shs.dim() != 3 or shs.shape[0] != P or shs.shape[2] != 3:
+            raise RuntimeError(f"{what}: shs must be ({P},K,3) for xyz {tuple(xyz.shape)}, got {tuple(shs.shape)}")
+        K = shs.shape[1]
+    else:
+        if tuple(shs.shape) != (P, 1, 3):
+            raise RuntimeError(f"{what}: with shs_rest, shs must be the ({P},1,3) DC part for xyz {tuple(xyz.shape)}, got {tuple(shs.shape)}")
+        if shs_rest.dim() != 3 or shs_rest.shape[0] != P or shs_rest.shape[2] != 3 or shs_rest.shape[1] < 1:
+            raise RuntimeError(f"{what}: shs_rest must be ({P},K-1,3) with K >= 2 for shs {tuple(shs.shape)}, got {tuple(shs_rest.shape)}")
+        K = 1 + shs_rest.shape[1]
+    if K not in (1, 4, 9, 16):
+        raise RuntimeError(f"{what}: K = {K} stored coefficients (shs {tuple(shs.shape)}"
+                           + (f", shs_rest {tuple(shs_rest.shape)}" if shs_rest is not None else "") + "): K must be 1, 4, 9 or 16")
+    if K < (deg + 1) ** 2:
+        raise RuntimeError(f"{what}: degree {deg} needs {(deg + 1) ** 2} coefficients, shs"
+                           + (" + shs_rest hold " if shs_rest is not None else " holds ") + f"{K} (shs {tuple(shs.shape)})")
+    for name, t in named:
+        if not t.is_cuda:
+            raise RuntimeError(f"{what} runs only on an AMD GPU: {name} must be on a 'cuda' (ROCm) device, got {t.device}; there is no CPU "
+                               f"fallback (bags_raster.eval_sh is the host-side evaluation)")
+        if t.device != xyz.device:
+            raise RuntimeError(f"{what}: {name} is on {t.device}, xyz on {xyz.device}")
+    return _ShColors.apply(deg, shs, shs_rest, xyz, campos)

@@ -9,7 +9,9 @@ arguments, same choice of covariance path (``pipe.compute_cov3D_python``) and co
   * ``global_alignment`` may be ``None`` (the reference always passes a pair, ``train.py:250``);
   * ``shift_factors`` may be ``None`` (= zeros(3)); two extra keywords, ``depth_key`` (decision D6 of DESIGN.md) and
     ``depth_weights_grad`` (the returned ``depth`` / ``weights`` maps carry gradients; decision D5);
-  * the two screen-space gradient sinks are leaf tensors (the reference: ``zeros + 0`` with ``retain_grad()``, :37-44).
+  * the two screen-space gradient sinks are leaf tensors (the reference: ``zeros + 0`` with ``retain_grad()``, :37-44);
+  * on a GPU the Python-side SH colours (``hybrid`` / ``pipe.convert_SHs_python``) come from ``bags_raster.sh_colors``, one HIP
+    launch each way, fed with ``_features_dc`` / ``_features_rest`` as stored; ``_python_colors`` is the host path.
 """
 from __future__ import annotations
 
@@ -19,7 +21,7 @@ from typing import Optional
 
 import torch
 
-from .gaussians import eval_sh
+from .gaussians import eval_sh, sh_colors
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer
 
 
@@ -59,12 +61,14 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, mlp_color, shift_
     required, ``hybrid`` defaults to True (Python-side SH colours + ``mlp_color``).  ``shift_factors=None`` stands for the
     zero vector the reference keeps (train.py:125-126: its optimizer is never stepped)."""
     # activations: one fused launch when the container offers it (GaussianBag on a GPU), else the reference's properties
-    # rasterizer-side SH colours: the two feature parameters go to the op as they are stored (shs = features_dc, shs_rest =
-    # features_rest), without get_features' torch.cat; every other colour path needs the (P,K,3) tensor
+    # rasterizer-side SH colours and, on a GPU, the Python-side ones (bags_raster.sh_colors): the two feature parameters go to the
+    # kernel as they are stored (shs = features_dc, shs_rest = features_rest), without get_features' torch.cat; every other colour
+    # path needs the (P,K,3) tensor
     raster_sh = override_color is None and not (hybrid or pipe.convert_SHs_python)
+    fused_colors = override_color is None and not raster_sh and pc.get_xyz.is_cuda
     rest = getattr(pc, "_features_rest", None)
-    split = (raster_sh and torch.is_tensor(rest) and torch.is_tensor(getattr(pc, "_features_dc", None)) and rest.dim() == 3
-             and rest.shape[1] >= 1 and rest.is_cuda)
+    split = ((raster_sh or fused_colors) and torch.is_tensor(rest) and torch.is_tensor(getattr(pc, "_features_dc", None))
+             and rest.dim() == 3 and rest.shape[1] >= 1 and rest.is_cuda)
     if hasattr(pc, "activated"):                               # GaussianBag: one fused launch each way
         xyz, features, opacity, scaling, rotation = pc.activated(features=not split)
     else:                                                      # any container with the reference's properties (GaussianModel)
@@ -114,6 +118,13 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, mlp_color, shift_
     shs = shs_rest = colors_precomp = None
     if override_color is not None:
         colors_precomp = override_color
+    elif fused_colors:                                         # one HIP launch each way; `+ mlp_color` stays in PyTorch
+        if split:
+            colors_precomp = sh_colors(pc.active_sh_degree, pc._features_dc, xyz, campos, shs_rest=pc._features_rest)
+        else:
+            colors_precomp = sh_colors(pc.active_sh_degree, features, xyz, campos)
+        if not (isinstance(mlp_color, (int, float)) and mlp_color == 0):          # the reference passes 0
+            colors_precomp = colors_precomp + mlp_color
     elif hybrid or pipe.convert_SHs_python:
         colors_precomp = _python_colors(pc, xyz, features, campos, mlp_color)
     elif split:

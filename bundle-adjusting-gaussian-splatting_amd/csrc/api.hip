@@ -195,6 +195,14 @@ static size_t carve_backward(void* base, int P, long long I, BwdWorkView* v)
     return c.used();
 }
 
+static size_t carve_sh_colors(void* base, int P, float** slab)
+{
+    Carver c(base);
+    float* s = c.take<float>((size_t)cdiv(P > 0 ? P : 1, 256) * SH_SLAB);      // one row of campos sums per workgroup (sh_colors.hip)
+    if (slab) *slab = s;
+    return c.used();
+}
+
 // ---------------------------------------------------------------------------------------------- validation
 static int check_common(const BagsSettings* s, const BagsInputs* in, const BagsState* stt)
 {
@@ -720,6 +728,54 @@ int bags_activations_backward(const BagsRawGaussians* r, const float* g_shs, con
     if (rc) return rc;
     HIP_TRY(launch_activations_bwd(r->P, r->K, r->features_dc, r->features_rest, r->opacity, r->scaling, r->rotation, g_shs, g_opacity,
                                    g_scales, g_rotations, g_dc, g_rest, g_opacity_raw, g_scaling, g_rotation, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- SH colours
+static int check_sh_colors(const BagsShColors* a)
+{
+    if (!a) return fail(BAGS_ERR_ARG, "sh_colors: null struct");
+    if (a->P < 0) return fail(BAGS_ERR_ARG, "sh_colors: P < 0 (got %d)", a->P);
+    if (a->sh_degree < 0 || a->sh_degree > 3) return fail(BAGS_ERR_ARG, "sh_colors: sh_degree %d not in 0..3", a->sh_degree);
+    if (a->K != 1 && a->K != 4 && a->K != 9 && a->K != 16) return fail(BAGS_ERR_ARG, "sh_colors: K %d not one of 1, 4, 9, 16", a->K);
+    if ((a->sh_degree + 1) * (a->sh_degree + 1) > a->K)
+        return fail(BAGS_ERR_ARG, "sh_colors: sh_degree %d needs %d coefficients, K is %d", a->sh_degree, (a->sh_degree + 1) * (a->sh_degree + 1), a->K);
+    if (a->shs_rest && a->K < 4) return fail(BAGS_ERR_ARG, "sh_colors: shs_rest needs K >= 4 (got %d)", a->K);
+    if (a->P > 0 && (!a->shs || !a->xyz || !a->campos)) return fail(BAGS_ERR_ARG, "sh_colors: shs / xyz / campos must be given");
+    if (!a->shs_rest && a->K == 16 && (reinterpret_cast<size_t>(a->shs) & 15))
+        return fail(BAGS_ERR_ARG, "sh_colors: packed shs (P,16,3) must be 16-byte aligned");
+    return BAGS_OK;
+}
+
+size_t bags_sh_colors_workspace_size(int32_t P) { return carve_sh_colors(nullptr, P, nullptr) + BASE_SLACK; }
+
+int bags_sh_colors_forward(const BagsShColors* a, float* rgb, void* stream)
+{
+    int rc = check_sh_colors(a);
+    if (rc) return rc;
+    if (a->P == 0) return BAGS_OK;
+    if (!rgb) return fail(BAGS_ERR_ARG, "sh_colors_forward: null rgb");
+    HIP_TRY(launch_sh_colors_fwd(*a, rgb, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
+int bags_sh_colors_backward(const BagsShColors* a, const float* grad_rgb, void* workspace, size_t workspace_bytes, float* grad_shs,
+                            float* grad_shs_rest, float* grad_xyz, float* grad_campos, void* stream)
+{
+    int rc = check_sh_colors(a);
+    if (rc) return rc;
+    if (!grad_shs && !grad_shs_rest && !grad_xyz && !grad_campos) return BAGS_OK;
+    if (a->P > 0 && !grad_rgb) return fail(BAGS_ERR_ARG, "sh_colors_backward: null grad_rgb");
+    if (grad_shs_rest && !a->shs_rest) return fail(BAGS_ERR_ARG, "sh_colors_backward: grad_shs_rest without shs_rest");
+    if ((reinterpret_cast<size_t>(grad_shs) | reinterpret_cast<size_t>(grad_shs_rest)) & 15)
+        return fail(BAGS_ERR_ARG, "sh_colors_backward: grad_shs / grad_shs_rest must be 16-byte aligned");
+    float* slab = nullptr;
+    if (grad_campos) {
+        if (!workspace || workspace_bytes < bags_sh_colors_workspace_size(a->P))
+            return fail(BAGS_ERR_SIZE, "sh_colors_backward: grad_campos needs a workspace of %zu bytes", bags_sh_colors_workspace_size(a->P));
+        carve_sh_colors(workspace, a->P, &slab);
+    }
+    HIP_TRY(launch_sh_colors_bwd(*a, grad_rgb, slab, grad_shs, grad_shs_rest, grad_xyz, grad_campos, (hipStream_t)stream));
     return BAGS_OK;
 }
 

@@ -250,6 +250,12 @@ hipError_t launch_activations_bwd(int P, int K, const float* dc, const float* re
                                   const float* rotation, const float* g_shs, const float* g_opacity, const float* g_scales,
                                   const float* g_rot, float* g_dc, float* g_rest, float* g_opacity_raw, float* g_scaling,
                                   float* g_rotation, hipStream_t st);
+// sh_colors.hip: SH -> RGB of the Python colour path (view direction, basis, +0.5, clamp at 0), and the adjoint; slab: SH_SLAB floats per
+// workgroup of 256 Gaussians (carve_sh_colors in api.hip)
+#define SH_SLAB 4
+hipError_t launch_sh_colors_fwd(const BagsShColors& a, float* rgb, hipStream_t st);
+hipError_t launch_sh_colors_bwd(const BagsShColors& a, const float* g_rgb, float* slab, float* g_shs, float* g_shs_rest, float* g_xyz,
+                                float* g_campos, hipStream_t st);
 // adam.hip: torch.optim.Adam step of up to BAGS_ADAM_MAX_GROUPS parameter groups (+ densification statistics) in one launch
 hipError_t launch_adam(const BagsAdamArgs& args, const BagsDensifyStats* stats, hipStream_t st);
 // densify.hip: densify-and-prune (decide + scan, then map + gather) and the opacity reset

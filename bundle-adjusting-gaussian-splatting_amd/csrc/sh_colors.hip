@@ -1,0 +1,260 @@
+// sh_colors.hip -- SH -> RGB as a stand-alone operator with its own backward: the colour path render() takes by default
+// (hybrid=True: gaussian_renderer/__init__.py:90-95, the rasterizer then gets colors_precomp).
+//
+//   d = xyz - campos,  u = d / |d|,  raw_c = sum_{t < (deg+1)^2} basis_t(u) * sh[t][c] + 0.5,  rgb_c = raw_c < 0 ? 0 : raw_c
+//
+// In PyTorch that is a cat, a transposed copy, ~30 elementwise launches for the basis, a broadcast product and a sum, and all of
+// it again backwards; here one kernel each way plus a three-workgroup reduction for dL/dcampos.  One thread per Gaussian, the
+// coefficient row in registers (K = 16: twelve dwordx4 loads requested before the first use, as in K1); the coefficients come
+// packed, shs (P,K,3), or split, shs (P,1,3) + shs_rest (P,K-1,3), whose rows are only 4-byte aligned.
+//
+// COMPILED WITH -ffp-contract=off: the backward saves nothing, it recomputes raw_c with the forward's operations to get the
+// forward's clamp decision, and the packed and the split instance must give the same bits.  Nothing here is bound by arithmetic.
+//
+// Backward, per Gaussian (m_c = raw_c < 0 ? 0 : dL/drgb_c; raw_c == 0 passes, as clamp_min does):
+//   dL/dsh[t][c] = basis_t * m_c  (t < (deg+1)^2; exactly zero for the stored rows beyond)
+//   dL/du        = sum_t grad basis_t * (sum_c sh[t][c] m_c),   dL/dxyz = (dL/du - u (u . dL/du)) / |d|,   dL/dcampos = -sum_P dL/dxyz
+// A Gaussian whose three cotangents are zero (everything the rasterizer culled) reads neither its position nor its row and writes
+// zeros.  The SH gradient rows leave as whole lines through LDS (K9's store pass); the campos sums go wave (DPP) -> workgroup ->
+// one slab row, and sh_campos_reduce_kernel adds the rows in fp64 in a fixed order (a last-workgroup tail inside the kernel is the
+// fold that lost twice for pose_reduce).  No atomics: every gradient is bitwise reproducible.
+#include "bags_common.h"
+#include "sh_basis.h"
+
+struct ShcIn { int P, deg; const float *shs, *shs_rest, *xyz, *campos; };
+
+// the first 3 * nb floats of a Gaussian's coefficients into c[]; K == 16 loads the whole 192-byte row with wide loads
+template <int K, bool SPLIT>
+__device__ __forceinline__ void shc_load_row(const ShcIn& A, const size_t i, const int nb, float* __restrict__ c)
+{
+    const float* __restrict__ dcp = SPLIT ? A.shs + 3 * i : A.shs + i * (size_t)(K * 3);
+    const float* __restrict__ rsp = SPLIT ? A.shs_rest + i * (size_t)((K - 1) * 3) : dcp + 3;
+    if (K == 16) {
+        if (SPLIT) {                      // 12 + 180 bytes, the second row only 4-byte aligned (dwordx4 loads at any dword)
+            struct __attribute__((packed, aligned(4))) UF4 { float x, y, z, w; };
+            c[0] = dcp[0]; c[1] = dcp[1]; c[2] = dcp[2];
+            const UF4* u4 = reinterpret_cast<const UF4*>(rsp);
+#pragma unroll
+            for (int t = 0; t < 11; ++t) {
+                const UF4 w = u4[t];
+                c[3 + 4 * t] = w.x; c[4 + 4 * t] = w.y; c[5 + 4 * t] = w.z; c[6 + 4 * t] = w.w;
+            }
+            c[47] = rsp[44];
+        } else {
+            const float4* s4 = reinterpret_cast<const float4*>(dcp);
+#pragma unroll
+            for (int t = 0; t < 12; ++t) {
+                const float4 w = s4[t];
+                c[4 * t] = w.x; c[4 * t + 1] = w.y; c[4 * t + 2] = w.z; c[4 * t + 3] = w.w;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3 * K; ++k) c[k] = (k < 3 * nb) ? (k < 3 ? dcp[k] : rsp[k - 3]) : 0.f;
+    }
+}
+
+// raw colour: the ONE spelling of the sum, shared by the forward and the backward's clamp mask
+template <int K>
+__device__ __forceinline__ void shc_raw(const int nb, const float* __restrict__ b, const float* __restrict__ c, float& r, float& g, float& bl)
+{
+    r = 0.f; g = 0.f; bl = 0.f;
+#pragma unroll
+    for (int t = 0; t < K; ++t)
+        if (t < nb) { r += b[t] * c[3 * t]; g += b[t] * c[3 * t + 1]; bl += b[t] * c[3 * t + 2]; }
+    r += 0.5f; g += 0.5f; bl += 0.5f;
+}
+
+template <int K, bool SPLIT>
+__global__ void __launch_bounds__(256)
+sh_colors_fwd_kernel(const ShcIn A, float* __restrict__ rgb)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= A.P) return;
+    const int nb = (A.deg + 1) * (A.deg + 1);
+    const float x = A.xyz[3 * (size_t)i], y = A.xyz[3 * (size_t)i + 1], z = A.xyz[3 * (size_t)i + 2];
+    float c[48];
+    shc_load_row<K, SPLIT>(A, (size_t)i, nb, c);
+    const float dx = x - A.campos[0], dy = y - A.campos[1], dz = z - A.campos[2];
+    const float dl = sqrtf(dx * dx + dy * dy + dz * dz);
+    float b[16];
+    sh_basis(A.deg, dx / dl, dy / dl, dz / dl, b);
+    float r, g, bl;
+    shc_raw<K>(nb, b, c, r, g, bl);
+    rgb[3 * (size_t)i] = r < 0.f ? 0.f : r; rgb[3 * (size_t)i + 1] = g < 0.f ? 0.f : g; rgb[3 * (size_t)i + 2] = bl < 0.f ? 0.f : bl;
+}
+
+// sum over the 64 lanes on DPP, valid in lane 63, every lane active (the reduction preprocess_bwd.hip uses for the pose sums)
+__device__ __forceinline__ float shc_wave_total(float x)
+{
+#define DPP_ADD(ctrl, rmask) x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), ctrl, rmask, 0xf, false))
+    DPP_ADD(0x111, 0xf); DPP_ADD(0x112, 0xf); DPP_ADD(0x114, 0xf); DPP_ADD(0x118, 0xf); DPP_ADD(0x142, 0xa); DPP_ADD(0x143, 0xc);
+#undef DPP_ADD
+    return x;
+}
+
+// The workgroup's 256 gradient rows of one tensor, R floats each starting at coefficient T0, as whole lines: thread t owns float4
+// number t, t + 256, ... of the workgroup's span (256 R floats: a multiple of 16 bytes from a 16-byte aligned base).
+// srow[g] = basis[16] (zero beyond the active degree and for a Gaussian that writes zeros), masked cotangent[3], pad.
+template <u32 R, u32 T0>
+__device__ __forceinline__ void shc_store_span(const float (*srow)[20], float* __restrict__ out, const int P)
+{
+    const size_t first_f = (size_t)blockIdx.x * 256u * R, total = (size_t)P * R;
+#pragma unroll
+    for (u32 k = 0; k < (64u * R + 255u) / 256u; ++k) {
+        const u32 el = k * 256u + threadIdx.x;
+        const size_t g0 = first_f + (size_t)el * 4u;
+        if (el < 64u * R && g0 < total) {
+            float o4[4];
+#pragma unroll
+            for (u32 u = 0; u < 4; ++u) {
+                const u32 f = el * 4u + u, row = f / R, r = f - row * R, t = T0 + r / 3u, ch = r - 3u * (r / 3u);
+                o4[u] = srow[row][t] * srow[row][16u + ch];
+            }
+            if (g0 + 3 < total) *reinterpret_cast<float4*>(out + g0) = make_float4(o4[0], o4[1], o4[2], o4[3]);
+            else {                                    // the tensor's last float4 may be partial (P R not a multiple of 4)
+                out[g0] = o4[0];
+                if (g0 + 1 < total) out[g0 + 1] = o4[1];
+                if (g0 + 2 < total) out[g0 + 2] = o4[2];
+            }
+        }
+    }
+}
+
+// need_dir: the direction gradient is wanted (deg > 0 and g_xyz or slab given); without it g_xyz, if given, receives zeros
+template <int K, bool SPLIT>
+__global__ void __launch_bounds__(256)
+sh_colors_bwd_kernel(const ShcIn A, const float* __restrict__ g_rgb, float* __restrict__ g_shs, float* __restrict__ g_shs_rest,
+                     float* __restrict__ g_xyz, float* __restrict__ slab, const int need_dir)
+{
+    __shared__ float srow[256][20];
+    __shared__ float wsum[4][4];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const bool on = i < A.P;
+    const size_t ic = (size_t)(on ? i : A.P - 1);
+    const int nb = (A.deg + 1) * (A.deg + 1);
+    const float g0 = g_rgb[3 * ic], g1 = g_rgb[3 * ic + 1], g2 = g_rgb[3 * ic + 2];
+    const bool any = on && (g0 != 0.f || g1 != 0.f || g2 != 0.f);
+    float bs[16];
+#pragma unroll
+    for (int t = 0; t < 16; ++t) bs[t] = 0.f;
+    float m0 = 0.f, m1 = 0.f, m2 = 0.f, gx = 0.f, gy = 0.f, gz = 0.f;
+    if (any) {
+        const float x = A.xyz[3 * ic], y = A.xyz[3 * ic + 1], z = A.xyz[3 * ic + 2];
+        float c[48];
+        shc_load_row<K, SPLIT>(A, ic, nb, c);
+        const float dx = x - A.campos[0], dy = y - A.campos[1], dz = z - A.campos[2];
+        const float dl = sqrtf(dx * dx + dy * dy + dz * dz);
+        const float ux = dx / dl, uy = dy / dl, uz = dz / dl;
+        float b[16];
+        sh_basis(A.deg, ux, uy, uz, b);
+        float r, g, bl;
+        shc_raw<K>(nb, b, c, r, g, bl);                  // the forward's bits, hence the forward's clamp decision
+        m0 = r < 0.f ? 0.f : g0; m1 = g < 0.f ? 0.f : g1; m2 = bl < 0.f ? 0.f : g2;
+#pragma unroll
+        for (int t = 0; t < K; ++t) bs[t] = (t < nb) ? b[t] : 0.f;
+        if (need_dir && (m0 != 0.f || m1 != 0.f || m2 != 0.f)) {
+            float bx[16], by[16], bz[16];
+            sh_basis_grad(A.deg, ux, uy, uz, bx, by, bz);
+            float dux = 0.f, duy = 0.f, duz = 0.f;
+#pragma unroll
+            for (int t = 1; t < K; ++t)
+                if (t < nb) {
+                    const float s = c[3 * t] * m0 + c[3 * t + 1] * m1 + c[3 * t + 2] * m2;
+                    dux += bx[t] * s; duy += by[t] * s; duz += bz[t] * s;
+                }
+            const float dot = ux * dux + uy * duy + uz * duz;          // d(d / |d|): the component along u drops out
+            gx = (dux - ux * dot) / dl; gy = (duy - uy * dot) / dl; gz = (duz - uz * dot) / dl;
+        }
+    }
+    if (g_xyz && on) { g_xyz[3 * ic] = gx; g_xyz[3 * ic + 1] = gy; g_xyz[3 * ic + 2] = gz; }
+
+    if (g_shs || g_shs_rest) {                           // (kernel arguments: the whole workgroup takes the same side)
+        float4* d4 = reinterpret_cast<float4*>(&srow[threadIdx.x][0]);
+        d4[0] = make_float4(bs[0], bs[1], bs[2], bs[3]);
+        d4[1] = make_float4(bs[4], bs[5], bs[6], bs[7]);
+        d4[2] = make_float4(bs[8], bs[9], bs[10], bs[11]);
+        d4[3] = make_float4(bs[12], bs[13], bs[14], bs[15]);
+        d4[4] = make_float4(m0, m1, m2, 0.f);
+        __syncthreads();
+        if constexpr (SPLIT) {
+            if (g_shs) shc_store_span<3u, 0u>(srow, g_shs, A.P);
+            if (g_shs_rest) shc_store_span<3u * (K - 1), 1u>(srow, g_shs_rest, A.P);
+        } else if (g_shs) {
+            shc_store_span<3u * K, 0u>(srow, g_shs, A.P);
+        }
+    }
+
+    if (slab) {                                          // dL/dcampos = -sum dL/dxyz: wave, workgroup, one slab row
+        const float r0 = shc_wave_total(-gx), r1 = shc_wave_total(-gy), r2 = shc_wave_total(-gz);
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        if (lane == 63) { wsum[wave][0] = r0; wsum[wave][1] = r1; wsum[wave][2] = r2; wsum[wave][3] = 0.f; }
+        __syncthreads();
+        if (threadIdx.x < 4) {
+            const int t = threadIdx.x;
+            slab[(size_t)blockIdx.x * 4 + t] = (wsum[0][t] + wsum[1][t]) + (wsum[2][t] + wsum[3][t]);
+        }
+    }
+}
+
+// slab rows -> dL/dcampos in fp64: one workgroup per component, thread t adds rows t, t + 256, ... in row order, the lanes of a
+// wave by a fixed shuffle tree, the four waves in wave order (pose_reduce_kernel's scheme, clamped batched loads included)
+__global__ void __launch_bounds__(256)
+sh_campos_reduce_kernel(const float* __restrict__ slab, const int nblocks, float* __restrict__ g_campos)
+{
+    __shared__ double wsum[4];
+    const int t = blockIdx.x;
+    double acc = 0.0;
+    for (int b = threadIdx.x; b < nblocks; b += 8 * 256) {
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = slab[(size_t)min(b + u * 256, nblocks - 1) * 4 + t];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) acc += (b + u * 256 < nblocks) ? (double)v[u] : 0.0;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) g_campos[t] = (float)(((wsum[0] + wsum[1]) + wsum[2]) + wsum[3]);
+}
+
+#define SHC_DISPATCH(CALL)                                                                  \
+    if (split) {                                                                            \
+        if (K == 16) { CALL(16, true) } else if (K == 9) { CALL(9, true) } else { CALL(4, true) } \
+    } else {                                                                                \
+        if (K == 16) { CALL(16, false) } else if (K == 9) { CALL(9, false) } else if (K == 4) { CALL(4, false) } else { CALL(1, false) } \
+    }
+
+hipError_t launch_sh_colors_fwd(const BagsShColors& a, float* rgb, hipStream_t st)
+{
+    if (a.P <= 0) return hipSuccess;
+    const ShcIn A{a.P, a.sh_degree, a.shs, a.shs_rest, a.xyz, a.campos};
+    const int K = a.K; const bool split = a.shs_rest != nullptr;
+    const dim3 grid((unsigned)cdiv(a.P, 256));
+#define SHC_FWD(K_, S_) hipLaunchKernelGGL((sh_colors_fwd_kernel<K_, S_>), grid, dim3(256), 0, st, A, rgb);
+    SHC_DISPATCH(SHC_FWD)
+#undef SHC_FWD
+    return hipGetLastError();
+}
+
+hipError_t launch_sh_colors_bwd(const BagsShColors& a, const float* g_rgb, float* slab, float* g_shs, float* g_shs_rest, float* g_xyz,
+                                float* g_campos, hipStream_t st)
+{
+    if (a.P <= 0) return g_campos ? hipMemsetAsync(g_campos, 0, 3 * sizeof(float), st) : hipSuccess;
+    const ShcIn A{a.P, a.sh_degree, a.shs, a.shs_rest, a.xyz, a.campos};
+    const int K = a.K; const bool split = a.shs_rest != nullptr;
+    const int need_dir = (a.sh_degree > 0 && (g_xyz || g_campos)) ? 1 : 0;
+    float* const rows = (need_dir && g_campos) ? slab : nullptr;
+    const int nb = cdiv(a.P, 256);
+    if (g_shs || g_shs_rest || g_xyz || rows) {
+#define SHC_BWD(K_, S_) hipLaunchKernelGGL((sh_colors_bwd_kernel<K_, S_>), dim3(nb), dim3(256), 0, st, A, g_rgb, g_shs, g_shs_rest, g_xyz, rows, need_dir);
+        SHC_DISPATCH(SHC_BWD)
+#undef SHC_BWD
+    }
+    if (g_campos) {
+        if (rows) hipLaunchKernelGGL(sh_campos_reduce_kernel, dim3(3), dim3(256), 0, st, rows, nb, g_campos);
+        else { const hipError_t e = hipMemsetAsync(g_campos, 0, 3 * sizeof(float), st); if (e != hipSuccess) return e; }   // degree 0: no direction
+    }
+    return hipGetLastError();
+}

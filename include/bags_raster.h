@@ -359,6 +359,28 @@ int bags_activations_backward(const BagsRawGaussians* raw, const float* g_shs, c
                               const float* g_rotations, float* g_features_dc, float* g_features_rest, float* g_opacity_raw,
                               float* g_scaling, float* g_rotation, void* stream);
 
+/* SH -> RGB outside the rasterizer: the colours render() hands over as colors_precomp on its default (hybrid) path,
+ * gaussian_renderer/__init__.py:90-95, one launch each way (csrc/sh_colors.hip):
+ *     d = xyz - campos,  u = d / |d|,  raw = sum_{t < (sh_degree+1)^2} basis_t(u) * sh[t] + 0.5,  rgb = raw < 0 ? 0 : raw
+ * K = stored coefficient rows per Gaussian, one of 1, 4, 9, 16, K >= (sh_degree+1)^2.  Coefficients packed, shs (P,K,3) with
+ * shs_rest NULL, or split, shs (P,1,3) + shs_rest (P,K-1,3) (K >= 4; the two parameters as they are stored).  campos: 3 floats in
+ * device memory.  xyz == campos is 0/0, as in the reference.
+ * Backward: dL/dsh rows beyond the active degree are exactly zero; raw == 0 passes its gradient; a Gaussian with an all-zero
+ * cotangent row gets zeros and costs 12 bytes of reads.  Any of the four gradient pointers may be NULL (the SH gradient tensors
+ * must be 16-byte aligned); the workspace (the size function's bytes) is only touched when grad_campos is given.  No atomics:
+ * the gradients are bitwise reproducible. */
+typedef struct BagsShColors {
+    int32_t P, K, sh_degree, reserved;
+    const float* shs;                /* (P,K,3), or (P,1,3) when shs_rest is given */
+    const float* shs_rest;           /* (P,K-1,3) or NULL */
+    const float* xyz;                /* (P,3) */
+    const float* campos;             /* (3)   */
+} BagsShColors;
+size_t bags_sh_colors_workspace_size(int32_t P);
+int bags_sh_colors_forward(const BagsShColors* a, float* rgb, void* stream);
+int bags_sh_colors_backward(const BagsShColors* a, const float* grad_rgb, void* workspace, size_t workspace_bytes, float* grad_shs,
+                            float* grad_shs_rest, float* grad_xyz, float* grad_campos, void* stream);
+
 /* One optimizer step of the Gaussian parameters: torch.optim.Adam (amsgrad = False, weight_decay = 0, maximize = False) over up to
  * BAGS_ADAM_MAX_GROUPS parameter groups of one Gaussian count P in ONE launch (csrc/adam.hip).  The reference builds
  * torch.optim.Adam(l, lr=0.0, eps=1e-15) over xyz, f_dc, f_rest, opacity, scaling, rotation (scene/gaussian_model.py:192-210)

@@ -3,7 +3,7 @@ BASELINE config 3 shape (500 k Gaussians, 1920x1080, SH 3, pose leaves learnable
   fused      PoseCamera.get_matrices (csrc/camera.hip) + rasterizer + fused_photometric_loss (csrc/loss.hip)
   unfused    the four camera getters in PyTorch + rasterizer + dense 11x11 depthwise-conv SSIM (what utils/loss_utils.py launches)
 The rasterizer is the same HIP library in both; the difference is the neighbours SURVEY.md section 8(f) ranks 1 and 4 name.
-Prints one JSON line.  Usage: python tools/bench_iteration.py [--steps 20]"""
+Prints one JSON line.  Usage: python tools/bench_iteration.py [--steps 20] [--hybrid]   (--hybrid: render()'s default colour path)"""
 import argparse, json, os, sys
 
 import torch
@@ -51,7 +51,10 @@ def main():
     ap.add_argument("--host-profile", action="store_true", help="cProfile of the fused iteration's HOST side (lazy host wait, so that "
                                                                 "nothing blocks): where the Python time per iteration goes")
     ap.add_argument("--unpacked", action="store_true", help="get_features (torch.cat of features_dc and features_rest, as the reference "
-                                                            "calls the op) instead of the shs / shs_rest pair"); args = ap.parse_args()
+                                                            "calls the op) instead of the shs / shs_rest pair")
+    ap.add_argument("--hybrid", action="store_true", help="render()'s own default, hybrid=True: SH colours outside the rasterizer "
+                                                          "(bags_raster.sh_colors, csrc/sh_colors.hip), as the reference's train.py runs it")
+    args = ap.parse_args()
     dev = torch.device("cuda", 0)
     P, W, H = 500_000, 1920, 1080
     scene = synth_scene(P, 0, 0.5, 3)
@@ -67,7 +70,7 @@ def main():
     def iteration(camera, loss_fn):
         for t in leaves:
             t.grad = None
-        out = render(camera, pc, pipe, bg, 0.0, None, hybrid=False)
+        out = render(camera, pc, pipe, bg, 0.0, None, hybrid=args.hybrid)
         loss_fn(out["render"], gt).backward()
 
     def timed(camera, loss_fn):
@@ -100,12 +103,12 @@ def main():
         return
     t_fused = timed(cam, L.fused_photometric_loss)
     if args.fused_only:
-        print(json.dumps({"fused": t_fused, "split_sh": not args.unpacked})); return
+        print(json.dumps({"fused": t_fused, "split_sh": not args.unpacked, "hybrid": args.hybrid})); return
     t_unfused = timed(PlainCamera(cam), dense_loss)
     t_mixed = timed(PlainCamera(cam), L.fused_photometric_loss)
     print(json.dumps({"metric": "ms per iteration (camera chain + render + loss + backward) @1920x1080, 500k Gaussians",
                       "fused": t_fused, "pytorch_camera_chain_fused_loss": t_mixed, "pytorch_camera_chain_dense_ssim": t_unfused,
-                      "speedup": t_unfused / t_fused, "split_sh": not args.unpacked}))
+                      "speedup": t_unfused / t_fused, "split_sh": not args.unpacked, "hybrid": args.hybrid}))
 
 
 if __name__ == "__main__":
