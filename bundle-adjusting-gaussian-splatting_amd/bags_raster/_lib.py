@@ -1,10 +1,16 @@
 """ctypes binding of libbags_raster.so (include/bags_raster.h).  No torch types cross this boundary: only raw
 device pointers (``tensor.data_ptr()``), ints and floats.  The library is built in-tree by ``__graft_entry__.build()``
-(or ``make -C csrc``); importing this module without it raises -- there is no CPU or eager fallback."""
+(or ``make -C csrc``); importing this module without it raises -- there is no CPU or eager fallback.
+
+A wrapper crosses the boundary with the helpers at the end of this module: ``require`` checks an argument, ``as_f32c`` /
+``ptr`` / ``workspace`` prepare what is passed, ``call`` launches -- on the argument's device, on its current stream, which
+every launching entry point takes as its LAST parameter."""
 from __future__ import annotations
 
 import ctypes as C
 import os
+
+import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # BAGS_RASTER_LIB: another build of the SAME library (csrc/Makefile `asan`: host-side AddressSanitizer build for the CPU ABI
@@ -229,3 +235,57 @@ def profile_read():
     calls = (C.c_int64 * n)()
     k = load().bags_profile_read(n, names, ms, calls)
     return {names[i].decode(): (ms[i], calls[i]) for i in range(min(k, n))}
+
+
+# ------------------------------------------------------------------------------------------------ crossing the boundary
+def ptr(t):
+    """What a ``c_void_p`` parameter or struct field takes for an optional tensor: None (NULL) or its device address."""
+    return None if t is None else t.data_ptr()
+
+
+def workspace(nbytes: int, device) -> torch.Tensor:
+    """``nbytes`` of uninitialised scratch for the library.  Zero bytes give an empty tensor, whose ``data_ptr()`` is 0: the
+    library receives (NULL, 0), which every entry point accepts wherever it needs no workspace."""
+    return torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+
+
+def as_f32c(t):
+    """A tensor as the library reads it: detached, float32, contiguous.  None stays None; a tensor that already qualifies comes
+    back as it is (no copy, no launch)."""
+    if t is None:
+        return None
+    if t.requires_grad:
+        t = t.detach()
+    return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.to(torch.float32).contiguous()
+
+
+def require(op: str, name: str, t, *, gpu: bool = False, f32: bool = False, contiguous: bool = False, on=None, host: str = "",
+            type_error=TypeError, layout_error=RuntimeError) -> None:
+    """The argument check of every wrapper: argument ``name`` of operation ``op`` is a tensor and, as asked for, on a GPU
+    (``gpu``), float32 (``f32``), dense and contiguous (``contiguous``), on the device of the tensor ``on``.  ``host`` ends the GPU
+    message with the host-side alternative, e.g. " (use torch.optim.Adam on the host)".  A wrong device is a RuntimeError; a wrong
+    type or dtype raises ``type_error`` and a wrong layout ``layout_error``, for the call sites whose callers catch another type."""
+    if not isinstance(t, torch.Tensor):
+        raise type_error(f"{op}: {name} must be a tensor, got {type(t).__name__}")
+    if gpu and not t.is_cuda:
+        raise RuntimeError(f"{op} runs only on an AMD GPU: {name} must be on a 'cuda' (ROCm) device, got {t.device}; it takes a GPU tensor, "
+                           f"there is no CPU fallback{host}")
+    if contiguous and t.is_sparse:
+        raise RuntimeError(f"{op}: {name} is sparse; only dense tensors are supported")
+    if f32 and t.dtype != torch.float32:
+        raise type_error(f"{op}: {name} must be float32, got {t.dtype}")
+    if contiguous and not t.is_contiguous():
+        raise layout_error(f"{op}: {name} must be contiguous (shape {tuple(t.shape)}, strides {t.stride()})")
+    if on is not None and t.device != on.device:
+        raise RuntimeError(f"{op}: {name} is on {t.device}, expected {on.device}")
+
+
+def call(name: str, device, *args) -> None:
+    """Launch entry point ``name`` on ``device``: ``args`` followed by the ``cuda_stream`` of that device's current stream, which every
+    launching entry point of ``SYMBOLS`` takes last; a failure raises with ``name`` and ``bags_last_error()``.  (The size queries and
+    ``bags_profile_*`` take no stream: they are plain ``load().bags_...`` calls.)"""
+    if name not in SYMBOLS:
+        raise AttributeError(f"bags_raster: {name} is not an entry point of include/bags_raster.h (bags_raster._lib.SYMBOLS)")
+    fn = getattr(load(), name)
+    with torch.cuda.device(device):
+        check(fn(*args, torch.cuda.current_stream(device).cuda_stream), name)

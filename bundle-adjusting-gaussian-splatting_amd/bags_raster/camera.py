@@ -17,6 +17,8 @@ from typing import Optional
 
 import torch
 
+from . import _lib as L
+
 
 def fov2focal(fov: float, pixels: int) -> float:
     return pixels / (2.0 * math.tan(fov / 2.0))
@@ -152,29 +154,22 @@ class _FusedCameraChain(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, dq, dt, fovx, fovy, q0, t0, znear, zfar, grot, gscale):
-        from . import _lib as L
+        L.require("fused_camera_chain", "delta_quaternion", dq, gpu=True, host=" (use PoseCamera's getters on the host)")
         dev = dq.device
-        if not dq.is_cuda:
-            raise RuntimeError("fused_camera_chain: tensors must live on a GPU (use PoseCamera's getters on the host)")
 
         def f32(t, n):
             if t is None:
                 return None
-            t = t.detach().to(dev, torch.float32).contiguous().reshape(-1)
+            t = L.as_f32c(t.to(dev)).reshape(-1)
             if t.numel() != n:
                 raise RuntimeError(f"fused_camera_chain: expected {n} values, got {t.numel()}")
             return t
         keep = dict(q0=f32(q0, 4), dq=f32(dq, 4), t0=f32(t0, 3), dt=f32(dt, 3), fovx=f32(fovx, 1), fovy=f32(fovy, 1),
                     grot=f32(grot, 9), gscale=f32(gscale, 1))
-        p = lambda t: None if t is None else t.data_ptr()
-        cam = L.BagsCamera(p(keep["q0"]), p(keep["dq"]), p(keep["t0"]), p(keep["dt"]), p(keep["fovx"]), p(keep["fovy"]),
-                           p(keep["grot"]), p(keep["gscale"]), float(znear), float(zfar))
+        cam = L.BagsCamera(*[L.ptr(keep[n]) for n in ("q0", "dq", "t0", "dt", "fovx", "fovy", "grot", "gscale")], float(znear), float(zfar))
         out = torch.empty(51, dtype=torch.float32, device=dev)
         V, M, K, Cc = out[0:16].view(4, 4), out[16:32].view(4, 4), out[32:48].view(4, 4), out[48:51]
-        lib = L.load()
-        with torch.cuda.device(dev):
-            L.check(lib.bags_camera_forward(cam, V.data_ptr(), M.data_ptr(), K.data_ptr(), Cc.data_ptr(),
-                                            torch.cuda.current_stream().cuda_stream), "bags_camera_forward")
+        L.call("bags_camera_forward", dev, cam, V.data_ptr(), M.data_ptr(), K.data_ptr(), Cc.data_ptr())
         ctx.keep, ctx.cam = keep, cam
         ctx.shapes = (dq.shape, dt.shape, fovx.shape, fovy.shape, None if grot is None else grot.shape,
                       None if gscale is None else gscale.shape)
@@ -182,22 +177,17 @@ class _FusedCameraChain(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gV, gM, gK, gC):
-        from . import _lib as L
         keep, cam = ctx.keep, ctx.cam
         dev = keep["dq"].device
-        c = lambda t: None if t is None else t.to(torch.float32).contiguous()
-        gV, gM, gK, gC = c(gV), c(gM), c(gK), c(gC)
+        gV, gM, gK, gC = L.as_f32c(gV), L.as_f32c(gM), L.as_f32c(gK), L.as_f32c(gC)
         need = ctx.needs_input_grad
         out = torch.empty(19, dtype=torch.float32, device=dev)                  # dq 4 | dt 3 | fovx | fovy | grot 9 | gscale (every requested
         # slice is fully written by the kernel, the others are not returned: no fill launch)
         g_dq, g_dt, g_fx, g_fy, g_gr, g_gs = out[0:4], out[4:7], out[7:8], out[8:9], out[9:18], out[18:19]
-        p = lambda t, on=True: None if (t is None or not on) else t.data_ptr()
-        lib = L.load()
-        with torch.cuda.device(dev):
-            L.check(lib.bags_camera_backward(cam, p(gV), p(gM), p(gK), p(gC), p(g_dq, need[0]), p(g_dt, need[1]),
-                                             p(g_fx, need[2]), p(g_fy, need[3]), p(g_gr, need[8] and keep["grot"] is not None),
-                                             p(g_gs, need[9] and keep["gscale"] is not None),
-                                             torch.cuda.current_stream().cuda_stream), "bags_camera_backward")
+        p = lambda t, on: L.ptr(t) if on else None
+        L.call("bags_camera_backward", dev, cam, L.ptr(gV), L.ptr(gM), L.ptr(gK), L.ptr(gC), p(g_dq, need[0]), p(g_dt, need[1]),
+               p(g_fx, need[2]), p(g_fy, need[3]), p(g_gr, need[8] and keep["grot"] is not None),
+               p(g_gs, need[9] and keep["gscale"] is not None))
         sh = ctx.shapes
         r = lambda g, on, shape: g.reshape(shape) if (on and shape is not None) else None
         return (r(g_dq, need[0], sh[0]), r(g_dt, need[1], sh[1]), r(g_fx, need[2], sh[2]), r(g_fy, need[3], sh[3]), None, None,

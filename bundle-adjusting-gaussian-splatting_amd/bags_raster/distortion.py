@@ -12,6 +12,8 @@ from typing import Tuple
 import torch
 import torch.nn.functional as F
 
+from . import _lib as L
+
 
 def center_crop(t: torch.Tensor, th: int, tw: int) -> torch.Tensor:
     """(N,C,H,W) -> (N,C,th,tw): the reference crops with a second grid_sample on an integer grid
@@ -38,25 +40,19 @@ def resample_image_torch(image: torch.Tensor, ctrl_flow: torch.Tensor, flow_hw: 
 class _Resample(torch.autograd.Function):
     @staticmethod
     def forward(ctx, image, ctrl_flow, flow_hw, crop_hw):
-        from . import _lib as L
         for name, t in (("image", image), ("ctrl_flow", ctrl_flow)):
-            if not t.is_cuda:
-                raise RuntimeError(f"resample_image: {name} must be a GPU tensor (use resample_image_torch on the host)")
+            L.require("resample_image", name, t, gpu=True, host=" (use resample_image_torch on the host)")
         if image.dim() != 3 or ctrl_flow.dim() != 3 or ctrl_flow.shape[2] != 2:
             raise RuntimeError(f"resample_image: expected image (C,H,W) and flow (h,w,2), got {tuple(image.shape)}, {tuple(ctrl_flow.shape)}")
-        img = image.detach().to(torch.float32).contiguous()
-        ctl = ctrl_flow.detach().to(torch.float32).contiguous()
+        img, ctl = L.as_f32c(image), L.as_f32c(ctrl_flow)
         Cn, H, W = img.shape
         h, w = ctl.shape[:2]
         Hf, Wf = int(flow_hw[0]), int(flow_hw[1])
         Hc, Wc = int(crop_hw[0]), int(crop_hw[1])
         out = torch.empty(Cn, Hc, Wc, dtype=torch.float32, device=img.device)
         mask = torch.empty(1, Hc, Wc, dtype=torch.float32, device=img.device)
-        lib = L.load()
-        with torch.cuda.device(img.device):
-            L.check(lib.bags_resample_forward(img.data_ptr(), Cn, H, W, ctl.data_ptr(), h, w, Hf, Wf, Hc, Wc, out.data_ptr(),
-                                              mask.data_ptr(), None, torch.cuda.current_stream().cuda_stream),
-                    "bags_resample_forward")
+        L.call("bags_resample_forward", img.device, img.data_ptr(), Cn, H, W, ctl.data_ptr(), h, w, Hf, Wf, Hc, Wc, out.data_ptr(),
+               mask.data_ptr(), None)
         ctx.save_for_backward(img, ctl)
         ctx.dims = (Cn, H, W, h, w, Hf, Wf, Hc, Wc)
         ctx.mark_non_differentiable(mask)
@@ -64,20 +60,14 @@ class _Resample(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_out, _g_mask):
-        from . import _lib as L
         img, ctl = ctx.saved_tensors
         Cn, H, W, h, w, Hf, Wf, Hc, Wc = ctx.dims
-        g_out = g_out.to(torch.float32).contiguous()
+        g_out = L.as_f32c(g_out)
         g_img = torch.empty_like(img) if ctx.needs_input_grad[0] else None
         g_ctl = torch.empty_like(ctl) if ctx.needs_input_grad[1] else None
-        lib = L.load()
-        with torch.cuda.device(img.device):
-            nbytes = lib.bags_resample_workspace_size(H, W, Hc, Wc)
-            ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=img.device)
-            L.check(lib.bags_resample_backward(img.data_ptr(), Cn, H, W, ctl.data_ptr(), h, w, Hf, Wf, Hc, Wc, g_out.data_ptr(),
-                                               ws.data_ptr(), nbytes, None if g_img is None else g_img.data_ptr(),
-                                               None if g_ctl is None else g_ctl.data_ptr(),
-                                               torch.cuda.current_stream().cuda_stream), "bags_resample_backward")
+        ws = L.workspace(L.load().bags_resample_workspace_size(H, W, Hc, Wc), img.device)
+        L.call("bags_resample_backward", img.device, img.data_ptr(), Cn, H, W, ctl.data_ptr(), h, w, Hf, Wf, Hc, Wc, g_out.data_ptr(),
+               ws.data_ptr(), ws.numel(), L.ptr(g_img), L.ptr(g_ctl))
         return g_img, g_ctl, None, None
 
 

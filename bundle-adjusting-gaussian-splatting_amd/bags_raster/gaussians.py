@@ -23,6 +23,8 @@ from typing import Dict, Optional
 
 import torch
 
+from . import _lib as L
+
 SH_C0 = 0.28209479177387814
 _SH_C1 = 0.4886025119029199
 _SH_C2 = (1.0925484305920792, -1.0925484305920792, 0.31539156525252005, -1.0925484305920792, 0.5462742152960396)
@@ -204,13 +206,7 @@ class GaussianBag:
                                f"{', '.join(self._GROUPS)})")
         return found
 
-    @staticmethod
-    def _check_gpu(what: str, name: str, t: torch.Tensor) -> None:
-        if not t.is_cuda:
-            raise RuntimeError(f"{what} runs only on an AMD GPU: {name} must be on a 'cuda' (ROCm) device, got {t.device}; there is no CPU "
-                               f"fallback")
-        if t.dtype != torch.float32 or not t.is_contiguous():
-            raise TypeError(f"{what}: {name} must be a contiguous float32 tensor, got {t.dtype}, strides {t.stride()}")
+    _ARG = dict(gpu=True, f32=True, contiguous=True, layout_error=TypeError)         # what the densify kernels take (_lib.require)
 
     @torch.no_grad()
     def densify_and_prune(self, optimizer, max_grad: float, min_opacity: float, extent: float, max_screen_size, percent_dense: float = 0.01,
@@ -232,7 +228,6 @@ class GaussianBag:
 
         Returns a dict: ``kept``, ``clones``, ``split``, ``pruned`` (rows the prune step removed), ``P_new`` and ``provenance``,
         int32 ``(P_new, 2)`` = (source row, kind: 0 kept, 1 clone, 2 + k child k)."""
-        from . import _lib as L
         what = "GaussianBag.densify_and_prune"
         if screen_size not in ("published", "pre_densify"):
             raise ValueError(f"{what}: screen_size must be 'published' or 'pre_densify', got {screen_size!r}")
@@ -244,14 +239,14 @@ class GaussianBag:
         dev = self._xyz.device
         stats = (("xyz_gradient_accum", self.xyz_gradient_accum), ("denom", self.denom), ("max_radii2D", self.max_radii2D))
         for name, t in [(self._GROUPS[n][0], found[n][1]) for n in found] + list(stats):
-            self._check_gpu(what, name, t)
+            L.require(what, name, t, **self._ARG)
             if t.shape[0] != P or t.device != dev:
                 raise RuntimeError(f"{what}: {name} has {t.shape[0]} rows on {t.device}, _xyz {P} on {dev}")
         for name, t in stats:
             if t.numel() != P:
                 raise RuntimeError(f"{what}: {name} has {t.numel()} elements for {P} Gaussians")
         if noise is not None:
-            self._check_gpu(what, "noise", noise)
+            L.require(what, "noise", noise, **self._ARG)
             if tuple(noise.shape) != (P, N, 3) or noise.device != dev:
                 raise RuntimeError(f"{what}: noise must be ({P}, {N}, 3) on {dev}, got {tuple(noise.shape)} on {noise.device}")
         elif seed is None:
@@ -259,41 +254,34 @@ class GaussianBag:
         for n, (_, p, st) in found.items():
             if st is not None:
                 for key in ("exp_avg", "exp_avg_sq"):
-                    self._check_gpu(what, f"{key} of group {n!r}", st[key])
+                    L.require(what, f"{key} of group {n!r}", st[key], **self._ARG)
                     if st[key].shape != p.shape or st[key].device != dev:
                         raise RuntimeError(f"{what}: {key} of group {n!r} has shape {tuple(st[key].shape)}, its parameter {tuple(p.shape)}")
         rule = L.BagsDensifyRule(P, N, max_grad, min_opacity, percent_dense * extent, 0.1 * extent,
                                  0.0 if max_screen_size is None else max_screen_size, 0 if max_screen_size is None else 1,
                                  L.SCREEN_PRE_DENSIFY if screen_size == "pre_densify" else L.SCREEN_PUBLISHED, 0,
-                                 (0 if seed is None else int(seed)) & (2 ** 64 - 1), None if noise is None else noise.data_ptr(),
+                                 (0 if seed is None else int(seed)) & (2 ** 64 - 1), L.ptr(noise),
                                  self.xyz_gradient_accum.data_ptr(), self.denom.data_ptr(), self.max_radii2D.data_ptr(),
                                  self._scaling.data_ptr(), self._opacity.data_ptr())
-        lib = L.load()
         counts = (L.C.c_int64 * L.DENSIFY_COUNTS)()
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream().cuda_stream
-            ws_bytes = lib.bags_densify_workspace_size(P)
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            L.check(lib.bags_densify_plan(rule, ws.data_ptr(), ws_bytes, counts, stream), "bags_densify_plan")
-            P_new = int(counts[L.COUNT_P_NEW])
-            new, groups = {}, []
-            for n, (_, p, st) in found.items():
-                shape = (P_new,) + tuple(p.shape[1:])
-                out = [torch.empty(shape, dtype=torch.float32, device=dev) for _ in range(3 if st is not None else 1)]
-                new[n] = out
-                m, v = (st["exp_avg"], st["exp_avg_sq"]) if st is not None else (None, None)
-                ptr = lambda t: None if t is None else t.data_ptr()
-                groups.append(L.BagsDensifyGroup(p.data_ptr(), ptr(m), ptr(v), out[0].data_ptr(), ptr(out[1] if st is not None else None),
-                                                 ptr(out[2] if st is not None else None), int(math.prod(p.shape[1:])),
-                                                 self._GROUPS[n][1]))
-            accum = torch.empty(P_new, 1, dtype=torch.float32, device=dev)
-            denom = torch.empty(P_new, 1, dtype=torch.float32, device=dev)
-            radii = torch.empty(P_new, dtype=torch.float32, device=dev)
-            prov = torch.empty(P_new, 2, dtype=torch.int32, device=dev)
-            if P > 0:
-                L.check(lib.bags_densify_apply(rule, (L.BagsDensifyGroup * len(groups))(*groups), len(groups), ws.data_ptr(), ws_bytes, P_new,
-                                               accum.data_ptr(), denom.data_ptr(), radii.data_ptr(), prov.data_ptr(), stream),
-                        "bags_densify_apply")
+        ws = L.workspace(L.load().bags_densify_workspace_size(P), dev)
+        L.call("bags_densify_plan", dev, rule, ws.data_ptr(), ws.numel(), counts)
+        P_new = int(counts[L.COUNT_P_NEW])
+        new, groups = {}, []
+        for n, (_, p, st) in found.items():
+            shape = (P_new,) + tuple(p.shape[1:])
+            out = [torch.empty(shape, dtype=torch.float32, device=dev) for _ in range(3 if st is not None else 1)] + [None, None]
+            new[n] = out
+            m, v = (st["exp_avg"], st["exp_avg_sq"]) if st is not None else (None, None)
+            groups.append(L.BagsDensifyGroup(p.data_ptr(), L.ptr(m), L.ptr(v), out[0].data_ptr(), L.ptr(out[1]), L.ptr(out[2]),
+                                             int(math.prod(p.shape[1:])), self._GROUPS[n][1]))
+        accum = torch.empty(P_new, 1, dtype=torch.float32, device=dev)
+        denom = torch.empty(P_new, 1, dtype=torch.float32, device=dev)
+        radii = torch.empty(P_new, dtype=torch.float32, device=dev)
+        prov = torch.empty(P_new, 2, dtype=torch.int32, device=dev)
+        if P > 0:
+            L.call("bags_densify_apply", dev, rule, (L.BagsDensifyGroup * len(groups))(*groups), len(groups), ws.data_ptr(), ws.numel(), P_new,
+                   accum.data_ptr(), denom.data_ptr(), radii.data_ptr(), prov.data_ptr())
         for n, (group, p, st) in found.items():
             param = torch.nn.Parameter(new[n][0].requires_grad_(True))
             if p in optimizer.state:
@@ -311,24 +299,21 @@ class GaussianBag:
     def reset_opacity(self, optimizer) -> None:
         """``GaussianModel.reset_opacity``: ``_opacity = inverse_sigmoid(min(sigmoid(_opacity), 0.01))`` and zero moments, in one
         HIP launch and in place (the reference replaces the parameter; the values and the optimizer state are the same)."""
-        from . import _lib as L
         what = "GaussianBag.reset_opacity"
         group = [g for g in optimizer.param_groups if g.get("name") == "opacity"]
         if len(group) != 1 or len(group[0]["params"]) != 1 or group[0]["params"][0] is not self._opacity:
             raise RuntimeError(f"{what}: the optimizer must hold exactly one group named 'opacity' whose parameter is this bag's _opacity")
         p = self._opacity
-        self._check_gpu(what, "_opacity", p)
+        L.require(what, "_opacity", p, **self._ARG)
         st = optimizer.state.get(p, None)
         m = v = None
         if st is not None and "exp_avg" in st:
             m, v = st["exp_avg"], st["exp_avg_sq"]
             for key, t in (("exp_avg", m), ("exp_avg_sq", v)):
-                self._check_gpu(what, key, t)
+                L.require(what, key, t, **self._ARG)
                 if t.shape != p.shape or t.device != p.device:
                     raise RuntimeError(f"{what}: {key} has shape {tuple(t.shape)} on {t.device}, _opacity {tuple(p.shape)} on {p.device}")
-        with torch.cuda.device(p.device):
-            L.check(L.load().bags_reset_opacity(p.data_ptr(), None if m is None else m.data_ptr(), None if v is None else v.data_ptr(),
-                                                p.numel(), torch.cuda.current_stream().cuda_stream), "bags_reset_opacity")
+        L.call("bags_reset_opacity", p.device, p.data_ptr(), L.ptr(m), L.ptr(v), p.numel())
         p.grad = None
 
     # ---- consumers of the op's screen-space gradients (scene/gaussian_model.py:449-455)
@@ -347,13 +332,13 @@ class _FusedActivations(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, dc, rest, opacity, scaling, rotation):
-        from . import _lib as L
         feats = dc is not None
         if (dc is None) != (rest is None):
             raise RuntimeError("fused_activations: features_dc and features_rest are given together or not at all")
-        ts = [None if t is None else t.detach().to(torch.float32).contiguous() for t in (dc, rest, opacity, scaling, rotation)]
-        if not all(t.is_cuda for t in ts if t is not None):
-            raise RuntimeError("fused_activations: tensors must live on a GPU (use the GaussianBag properties on the host)")
+        ts = [L.as_f32c(t) for t in (dc, rest, opacity, scaling, rotation)]
+        for name, t in zip(("features_dc", "features_rest", "opacity", "scaling", "rotation"), ts):
+            if t is not None:
+                L.require("fused_activations", name, t, gpu=True, host=" (use the GaussianBag properties on the host)")
         P = ts[3].shape[0]
         K = 1 + ts[1].shape[1] if feats else 1
         if (feats and (ts[0].shape != (P, 1, 3) or ts[1].shape != (P, K - 1, 3))) or ts[2].numel() != P or ts[3].shape != (P, 3) or ts[4].shape != (P, 4):
@@ -363,11 +348,8 @@ class _FusedActivations(torch.autograd.Function):
         op = torch.empty(P, 1, dtype=torch.float32, device=dev)
         sc = torch.empty(P, 3, dtype=torch.float32, device=dev)
         rot = torch.empty(P, 4, dtype=torch.float32, device=dev)
-        raw = L.BagsRawGaussians(P, K, *[None if t is None else t.data_ptr() for t in ts])
-        lib = L.load()
-        with torch.cuda.device(dev):
-            L.check(lib.bags_activations_forward(raw, None if shs is None else shs.data_ptr(), op.data_ptr(), sc.data_ptr(), rot.data_ptr(),
-                                                 torch.cuda.current_stream().cuda_stream), "bags_activations_forward")
+        raw = L.BagsRawGaussians(P, K, *[L.ptr(t) for t in ts])
+        L.call("bags_activations_forward", dev, raw, L.ptr(shs), op.data_ptr(), sc.data_ptr(), rot.data_ptr())
         ctx.feats = feats
         ctx.save_for_backward(*[t for t in ts if t is not None])
         ctx.set_materialize_grads(False)          # an unused output arrives as None, not as 96 MB of zeros
@@ -375,26 +357,20 @@ class _FusedActivations(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_shs, g_op, g_sc, g_rot):
-        from . import _lib as L
         ts = list(ctx.saved_tensors)
         if not ctx.feats:
             ts = [None, None] + ts
         P = ts[3].shape[0]
         K = 1 + ts[1].shape[1] if ctx.feats else 1
         need = ctx.needs_input_grad
-        c = lambda g: None if g is None else g.to(torch.float32).contiguous()
-        g_shs, g_op, g_sc, g_rot = c(g_shs), c(g_op), c(g_sc), c(g_rot)
+        g_shs, g_op, g_sc, g_rot = L.as_f32c(g_shs), L.as_f32c(g_op), L.as_f32c(g_sc), L.as_f32c(g_rot)
         out = [torch.empty_like(ts[0]) if (ctx.feats and need[0] and g_shs is not None) else None,
                torch.empty_like(ts[1]) if (ctx.feats and need[1] and g_shs is not None) else None,
                torch.empty_like(ts[2]) if (need[2] and g_op is not None) else None,
                torch.empty_like(ts[3]) if (need[3] and g_sc is not None) else None,
                torch.empty_like(ts[4]) if (need[4] and g_rot is not None) else None]
-        p = lambda t: None if t is None else t.data_ptr()
-        raw = L.BagsRawGaussians(P, K, *[p(t) for t in ts])
-        lib = L.load()
-        with torch.cuda.device(ts[3].device):
-            L.check(lib.bags_activations_backward(raw, p(g_shs), p(g_op), p(g_sc), p(g_rot), *[p(o) for o in out],
-                                                  torch.cuda.current_stream().cuda_stream), "bags_activations_backward")
+        raw = L.BagsRawGaussians(P, K, *[L.ptr(t) for t in ts])
+        L.call("bags_activations_backward", ts[3].device, raw, L.ptr(g_shs), L.ptr(g_op), L.ptr(g_sc), L.ptr(g_rot), *[L.ptr(o) for o in out])
         return tuple(out)
 
 
@@ -408,14 +384,11 @@ class _ShColors(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, deg, shs, shs_rest, xyz, campos):
-        from . import _lib as L
-        ts = [None if t is None else t.detach().contiguous() for t in (shs, shs_rest, xyz, campos)]
+        ts = [L.as_f32c(t) for t in (shs, shs_rest, xyz, campos)]                # (float32 already: sh_colors checks)
         P = ts[2].shape[0]
         K = ts[0].shape[1] + (0 if ts[1] is None else ts[1].shape[1])
         rgb = torch.empty(P, 3, dtype=torch.float32, device=ts[2].device)
-        args = L.BagsShColors(P, K, deg, 0, *[None if t is None else t.data_ptr() for t in ts])
-        with torch.cuda.device(rgb.device):
-            L.check(L.load().bags_sh_colors_forward(args, rgb.data_ptr(), torch.cuda.current_stream().cuda_stream), "bags_sh_colors_forward")
+        L.call("bags_sh_colors_forward", rgb.device, L.BagsShColors(P, K, deg, 0, *[L.ptr(t) for t in ts]), rgb.data_ptr())
         ctx.deg, ctx.split = deg, ts[1] is not None
         ctx.save_for_backward(*[t for t in ts if t is not None])       # the inputs and nothing else: the clamp mask is recomputed
         ctx.set_materialize_grads(False)
@@ -423,7 +396,6 @@ class _ShColors(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_rgb):
-        from . import _lib as L
         if g_rgb is None:
             return None, None, None, None, None
         ts = list(ctx.saved_tensors)
@@ -433,16 +405,11 @@ class _ShColors(torch.autograd.Function):
         P = xyz.shape[0]
         K = shs.shape[1] + (0 if rest is None else rest.shape[1])
         need = ctx.needs_input_grad
-        g_rgb = g_rgb.to(torch.float32).contiguous()
+        g_rgb = L.as_f32c(g_rgb)
         out = [torch.empty_like(t) if (t is not None and need[k]) else None for k, t in ((1, shs), (2, rest), (3, xyz), (4, campos))]
-        p = lambda t: None if t is None else t.data_ptr()
-        args = L.BagsShColors(P, K, ctx.deg, 0, p(shs), p(rest), p(xyz), p(campos))
-        lib = L.load()
-        with torch.cuda.device(xyz.device):
-            ws_bytes = lib.bags_sh_colors_workspace_size(P) if out[3] is not None else 0
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=xyz.device) if ws_bytes else None
-            L.check(lib.bags_sh_colors_backward(args, g_rgb.data_ptr(), p(ws), ws_bytes, *[p(o) for o in out],
-                                                torch.cuda.current_stream().cuda_stream), "bags_sh_colors_backward")
+        args = L.BagsShColors(P, K, ctx.deg, 0, L.ptr(shs), L.ptr(rest), L.ptr(xyz), L.ptr(campos))
+        ws = L.workspace(L.load().bags_sh_colors_workspace_size(P) if out[3] is not None else 0, xyz.device)      # (only dL/dcampos needs one)
+        L.call("bags_sh_colors_backward", xyz.device, args, g_rgb.data_ptr(), ws.data_ptr(), ws.numel(), *[L.ptr(o) for o in out])
         return (None,) + tuple(out)
 
 
@@ -459,10 +426,7 @@ def sh_colors(deg: int, shs: torch.Tensor, xyz: torch.Tensor, campos: torch.Tens
         raise ValueError(f"{what}: SH degree must be in 0..3, got {deg}")
     named = [("shs", shs), ("xyz", xyz), ("campos", campos)] + ([("shs_rest", shs_rest)] if shs_rest is not None else [])
     for name, t in named:
-        if not torch.is_tensor(t):
-            raise TypeError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
-        if t.dtype != torch.float32:
-            raise TypeError(f"{what}: {name} must be float32, got {t.dtype}")
+        L.require(what, name, t, f32=True)
     if xyz.dim() != 2 or xyz.shape[1] != 3:
         raise RuntimeError(f"{what}: xyz must be (P,3), got {tuple(xyz.shape)}")
     P = xyz.shape[0]
@@ -485,9 +449,5 @@ def sh_colors(deg: int, shs: torch.Tensor, xyz: torch.Tensor, campos: torch.Tens
         raise RuntimeError(f"{what}: degree {deg} needs {(deg + 1) ** 2} coefficients, shs"
                            + (" + shs_rest hold " if shs_rest is not None else " holds ") + f"{K} (shs {tuple(shs.shape)})")
     for name, t in named:
-        if not t.is_cuda:
-            raise RuntimeError(f"{what} runs only on an AMD GPU: {name} must be on a 'cuda' (ROCm) device, got {t.device}; there is no CPU "
-                               f"fallback (bags_raster.eval_sh is the host-side evaluation)")
-        if t.device != xyz.device:
-            raise RuntimeError(f"{what}: {name} is on {t.device}, xyz on {xyz.device}")
+        L.require(what, name, t, gpu=True, on=xyz, host=" (bags_raster.eval_sh is the host-side evaluation)")
     return _ShColors.apply(deg, shs, shs_rest, xyz, campos)

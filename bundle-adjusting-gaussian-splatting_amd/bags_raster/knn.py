@@ -11,19 +11,14 @@ from . import _lib as L
 
 
 def distCUDA2(points: torch.Tensor) -> torch.Tensor:
-    if not points.is_cuda:
-        raise RuntimeError("distCUDA2: points must be a GPU tensor (no CPU path)")
+    L.require("distCUDA2", "points", points, gpu=True)
     if points.dim() != 2 or points.shape[1] != 3:
         raise RuntimeError(f"distCUDA2: expected (P,3) points, got {tuple(points.shape)}")
-    pts = points.detach().to(torch.float32).contiguous()
+    pts = L.as_f32c(points)
     P = pts.shape[0]
     out = torch.empty(P, dtype=torch.float32, device=pts.device)
     if P == 0:
         return out
-    lib = L.load()
-    with torch.cuda.device(pts.device):
-        nbytes = lib.bags_knn_workspace_size(P)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=pts.device)
-        L.check(lib.bags_knn_mean_dist2(pts.data_ptr(), P, ws.data_ptr(), nbytes, out.data_ptr(),
-                                        torch.cuda.current_stream().cuda_stream), "bags_knn_mean_dist2")
+    ws = L.workspace(L.load().bags_knn_workspace_size(P), pts.device)
+    L.call("bags_knn_mean_dist2", pts.device, pts.data_ptr(), P, ws.data_ptr(), ws.numel(), out.data_ptr())
     return out

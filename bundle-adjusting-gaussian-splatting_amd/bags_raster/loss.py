@@ -15,6 +15,8 @@ import math
 import torch
 import torch.nn.functional as F
 
+from . import _lib as L
+
 
 def l1_loss(x: torch.Tensor, gt: torch.Tensor) -> torch.Tensor:
     return torch.abs(x - gt).mean()
@@ -49,65 +51,51 @@ def photometric_loss(image: torch.Tensor, gt: torch.Tensor, lambda_dssim: float 
 
 
 # ------------------------------------------------------------------------------------------------ fused HIP path
+def _fused_forward(ctx, op: str, entry: str, n_out: int, image: torch.Tensor, gt: torch.Tensor, *scalars) -> torch.Tensor:
+    """The forward both fused losses share: the checked pair, the workspace, ``n_out`` floats out of ``entry``."""
+    for name, t in (("image", image), ("gt", gt)):
+        L.require(op, name, t, gpu=True, f32=True, type_error=RuntimeError, host=" (use bags_raster.loss.l1_loss / ssim on the host)")
+    if image.shape != gt.shape or image.dim() != 3:
+        raise RuntimeError(f"{op}: expected two (C,H,W) tensors of one shape, got {tuple(image.shape)} and {tuple(gt.shape)}")
+    image, gt = image.contiguous(), gt.contiguous()
+    Cn, H, W = image.shape
+    ws = L.workspace(L.load().bags_loss_workspace_size(Cn, H, W), image.device)
+    out = torch.empty(n_out, dtype=torch.float32, device=image.device)
+    L.call(entry, image.device, image.data_ptr(), gt.data_ptr(), Cn, H, W, ws.data_ptr(), ws.numel(), *scalars, out.data_ptr())
+    ctx.save_for_backward(image, gt, ws)
+    return out
+
+
+def _fused_backward(ctx, entry: str, cotangent: torch.Tensor, *scalars) -> torch.Tensor:
+    """dL/dimage out of ``entry`` for the float32 ``cotangent`` of the forward's outputs."""
+    image, gt, ws = ctx.saved_tensors
+    Cn, H, W = image.shape
+    grad = torch.empty_like(image)
+    L.call(entry, image.device, image.data_ptr(), gt.data_ptr(), Cn, H, W, ws.data_ptr(), ws.numel(), *scalars, cotangent.data_ptr(),
+           grad.data_ptr())
+    return grad
+
+
 class _FusedL1SSIM(torch.autograd.Function):
     """(image, gt) -> (mean |image - gt|, mean SSIM), differentiable w.r.t. ``image``."""
 
     @staticmethod
     def forward(ctx, image: torch.Tensor, gt: torch.Tensor):
-        from . import _lib as L
-        for name, t in (("image", image), ("gt", gt)):
-            if not t.is_cuda:
-                raise RuntimeError(f"fused_l1_ssim: {name} must be a GPU tensor (the fused loss has no CPU path; "
-                                   f"use bags_raster.loss.l1_loss / ssim on the host)")
-            if t.dtype != torch.float32:
-                raise RuntimeError(f"fused_l1_ssim: {name} must be float32, got {t.dtype}")
-        if image.shape != gt.shape or image.dim() != 3:
-            raise RuntimeError(f"fused_l1_ssim: expected two (C,H,W) tensors of one shape, got {tuple(image.shape)} and {tuple(gt.shape)}")
-        lib = L.load()
-        image, gt = image.contiguous(), gt.contiguous()
-        Cn, H, W = image.shape
-        with torch.cuda.device(image.device):
-            nbytes = lib.bags_loss_workspace_size(Cn, H, W)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=image.device)
-            terms = torch.empty(2, dtype=torch.float32, device=image.device)
-            stream = torch.cuda.current_stream().cuda_stream
-            L.check(lib.bags_loss_forward(image.data_ptr(), gt.data_ptr(), Cn, H, W, ws.data_ptr(), nbytes,
-                                          terms.data_ptr(), stream), "bags_loss_forward")
-        ctx.save_for_backward(image, gt, ws)
+        terms = _fused_forward(ctx, "fused_l1_ssim", "bags_loss_forward", 2, image, gt)
         return terms[0], terms[1]
 
     @staticmethod
     def backward(ctx, g_l1, g_ssim):
-        from . import _lib as L
-        image, gt, ws = ctx.saved_tensors
-        if not ctx.needs_input_grad[0]:
+        if not ctx.needs_input_grad[0] or (g_l1 is None and g_ssim is None):
             return None, None
-        lib = L.load()
-        Cn, H, W = image.shape
-        z = torch.zeros((), dtype=torch.float32, device=image.device)
-        gt_terms = torch.stack([z if g_l1 is None else g_l1.to(torch.float32), z if g_ssim is None else g_ssim.to(torch.float32)]).contiguous()
-        grad = torch.empty_like(image)
-        with torch.cuda.device(image.device):
-            stream = torch.cuda.current_stream().cuda_stream
-            L.check(lib.bags_loss_backward(image.data_ptr(), gt.data_ptr(), Cn, H, W, ws.data_ptr(), ws.numel(),
-                                           gt_terms.data_ptr(), grad.data_ptr(), stream), "bags_loss_backward")
-        return grad, None
+        z = torch.zeros((), dtype=torch.float32, device=(g_l1 if g_l1 is not None else g_ssim).device)
+        g = torch.stack([z if g_l1 is None else g_l1.to(torch.float32), z if g_ssim is None else g_ssim.to(torch.float32)])
+        return _fused_backward(ctx, "bags_loss_backward", g), None
 
 
 def fused_l1_ssim(image: torch.Tensor, gt: torch.Tensor):
     """(l1_loss(image, gt), ssim(image, gt)) of utils/loss_utils.py in one HIP kernel; both scalars carry gradient."""
     return _FusedL1SSIM.apply(image, gt)
-
-
-def _check_pair(fn: str, image: torch.Tensor, gt: torch.Tensor) -> None:
-    for name, t in (("image", image), ("gt", gt)):
-        if not t.is_cuda:
-            raise RuntimeError(f"{fn}: {name} must be a GPU tensor (the fused loss has no CPU path; "
-                               f"use bags_raster.loss.l1_loss / ssim on the host)")
-        if t.dtype != torch.float32:
-            raise RuntimeError(f"{fn}: {name} must be float32, got {t.dtype}")
-    if image.shape != gt.shape or image.dim() != 3:
-        raise RuntimeError(f"{fn}: expected two (C,H,W) tensors of one shape, got {tuple(image.shape)} and {tuple(gt.shape)}")
 
 
 class _FusedPhotometric(torch.autograd.Function):
@@ -117,20 +105,8 @@ class _FusedPhotometric(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, image: torch.Tensor, gt: torch.Tensor, lambda_dssim: float):
-        from . import _lib as L
-        _check_pair("fused_photometric_loss", image, gt)
-        lib = L.load()
-        image, gt = image.contiguous(), gt.contiguous()
-        Cn, H, W = image.shape
-        with torch.cuda.device(image.device):
-            nbytes = lib.bags_loss_workspace_size(Cn, H, W)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=image.device)
-            out = torch.empty(3, dtype=torch.float32, device=image.device)
-            stream = torch.cuda.current_stream().cuda_stream
-            L.check(lib.bags_photometric_loss_forward(image.data_ptr(), gt.data_ptr(), Cn, H, W, ws.data_ptr(), nbytes,
-                                                      float(lambda_dssim), out.data_ptr(), stream), "bags_photometric_loss_forward")
-        ctx.save_for_backward(image, gt, ws)
         ctx.lambda_dssim = float(lambda_dssim)
+        out = _fused_forward(ctx, "fused_photometric_loss", "bags_photometric_loss_forward", 3, image, gt, ctx.lambda_dssim)
         loss, l1, s = out[0], out[1], out[2]
         ctx.mark_non_differentiable(l1, s)
         ctx.set_materialize_grads(False)          # no zero-fill launches for the two logging terms' absent gradients
@@ -138,20 +114,9 @@ class _FusedPhotometric(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_loss, _g_l1, _g_ssim):
-        from . import _lib as L
-        image, gt, ws = ctx.saved_tensors
         if not ctx.needs_input_grad[0] or g_loss is None:
             return None, None, None
-        lib = L.load()
-        Cn, H, W = image.shape
-        g = g_loss.to(torch.float32).contiguous()
-        grad = torch.empty_like(image)
-        with torch.cuda.device(image.device):
-            stream = torch.cuda.current_stream().cuda_stream
-            L.check(lib.bags_photometric_loss_backward(image.data_ptr(), gt.data_ptr(), Cn, H, W, ws.data_ptr(), ws.numel(),
-                                                       ctx.lambda_dssim, g.data_ptr(), grad.data_ptr(), stream),
-                    "bags_photometric_loss_backward")
-        return grad, None, None
+        return _fused_backward(ctx, "bags_photometric_loss_backward", L.as_f32c(g_loss), ctx.lambda_dssim), None, None
 
 
 def fused_photometric_loss(image: torch.Tensor, gt: torch.Tensor, lambda_dssim: float = 0.2, return_terms: bool = False):

@@ -20,6 +20,7 @@ import torch
 from . import _lib as L
 
 _UNSUPPORTED = (("amsgrad", False), ("maximize", False), ("capturable", False), ("differentiable", False))
+_ARG = dict(gpu=True, f32=True, contiguous=True, host=" (use torch.optim.Adam on the host)")      # what the kernel takes (_lib.require)
 
 
 class GaussianAdam(torch.optim.Optimizer):
@@ -46,18 +47,6 @@ class GaussianAdam(torch.optim.Optimizer):
                 raise RuntimeError(f"GaussianAdam: {key}={g[key]!r} is not supported (the fused kernel implements "
                                    f"torch.optim.Adam with amsgrad=False, maximize=False, capturable=False, differentiable=False)")
 
-    @staticmethod
-    def _check_tensor(what: str, t: torch.Tensor) -> None:
-        if not t.is_cuda:
-            raise RuntimeError(f"GaussianAdam runs only on an AMD GPU: {what} must be on a 'cuda' (ROCm) device, got {t.device}; "
-                               f"there is no CPU fallback (use torch.optim.Adam on the host)")
-        if t.is_sparse:
-            raise RuntimeError(f"GaussianAdam: {what} is sparse; only dense tensors are supported")
-        if t.dtype != torch.float32:
-            raise TypeError(f"GaussianAdam: {what} must be float32, got {t.dtype}")
-        if not t.is_contiguous():
-            raise RuntimeError(f"GaussianAdam: {what} must be contiguous (shape {tuple(t.shape)}, strides {t.stride()})")
-
     def _stats_block(self, stats):
         bag, viewspace, radii = stats
         grad = viewspace.grad
@@ -68,10 +57,10 @@ class GaussianAdam(torch.optim.Optimizer):
             raise TypeError("GaussianAdam: stats: radii must be the rasterizer's contiguous int32 GPU tensor")
         if grad.dim() != 2 or grad.shape[0] != P or grad.shape[1] < 2:
             raise RuntimeError(f"GaussianAdam: stats: the screen-space gradient must be (P, >= 2) with P = {P}, got {tuple(grad.shape)}")
-        self._check_tensor("stats: the screen-space gradient", grad)
+        L.require("GaussianAdam", "stats: the screen-space gradient", grad, **_ARG)
         for name in ("xyz_gradient_accum", "denom", "max_radii2D"):
             t = getattr(bag, name)
-            self._check_tensor(f"stats: {name}", t)
+            L.require("GaussianAdam", f"stats: {name}", t, **_ARG)
             if t.numel() != P:
                 raise RuntimeError(f"GaussianAdam: stats: {name} has {t.numel()} elements, radii {P}")
             if t.device != radii.device:
@@ -82,8 +71,7 @@ class GaussianAdam(torch.optim.Optimizer):
     def _visible(self, visibility: torch.Tensor) -> torch.Tensor:
         if visibility.dim() != 1:
             raise RuntimeError(f"GaussianAdam: visibility must be a (P,) tensor, got shape {tuple(visibility.shape)}")
-        if not visibility.is_cuda:
-            raise RuntimeError("GaussianAdam runs only on an AMD GPU: visibility must be on a 'cuda' (ROCm) device")
+        L.require("GaussianAdam", "visibility", visibility, gpu=True)
         if visibility.dtype == torch.int32 and visibility.is_contiguous():
             return visibility                                   # the op's radii: used as it is
         if visibility.dtype not in (torch.bool, torch.int32):
@@ -122,8 +110,8 @@ class GaussianAdam(torch.optim.Optimizer):
                 if p.grad is None:
                     continue
                 g = p.grad
-                self._check_tensor("a parameter", p)
-                self._check_tensor("a gradient", g)
+                L.require("GaussianAdam", "a parameter", p, **_ARG)
+                L.require("GaussianAdam", "a gradient", g, **_ARG)
                 state = self.state[p]
                 if len(state) == 0:
                     state["step"] = torch.tensor(0.0, dtype=torch.float64 if torch.get_default_dtype() == torch.float64 else torch.float32)
@@ -131,7 +119,7 @@ class GaussianAdam(torch.optim.Optimizer):
                     state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                 m, v = state["exp_avg"], state["exp_avg_sq"]
                 for name, t in (("exp_avg", m), ("exp_avg_sq", v)):
-                    self._check_tensor(name, t)
+                    L.require("GaussianAdam", name, t, **_ARG)
                     if t.shape != p.shape:
                         raise RuntimeError(f"GaussianAdam: {name} has shape {tuple(t.shape)}, its parameter {tuple(p.shape)}")
                 if g.shape != p.shape or g.device != p.device or m.device != p.device or v.device != p.device:
@@ -155,16 +143,12 @@ class GaussianAdam(torch.optim.Optimizer):
             if not any(key[0] == stats_P and key[4] == stats_dev for key in batches):
                 raise RuntimeError(f"GaussianAdam: stats were given, but no parameter with a gradient has as many rows as radii "
                                    f"({stats_P}) on {stats_dev}")
-        lib = L.load()
         for (P, beta1, beta2, eps, dev), groups in batches.items():
-            with torch.cuda.device(dev):
-                stream = torch.cuda.current_stream().cuda_stream
-                for i in range(0, len(groups), L.ADAM_MAX_GROUPS):
-                    part = groups[i:i + L.ADAM_MAX_GROUPS]
-                    args = L.BagsAdamArgs(P, len(part), beta1, beta2, eps, None if vis is None else vis.data_ptr(),
-                                          (L.BagsAdamGroup * L.ADAM_MAX_GROUPS)(*part))
-                    fold = stats_block is not None and P == stats_P and dev == stats_dev      # into exactly one launch
-                    L.check(lib.bags_adam_step(args, stats_block if fold else None, stream), "bags_adam_step")
-                    if fold:
-                        stats_block = None
+            for i in range(0, len(groups), L.ADAM_MAX_GROUPS):
+                part = groups[i:i + L.ADAM_MAX_GROUPS]
+                args = L.BagsAdamArgs(P, len(part), beta1, beta2, eps, L.ptr(vis), (L.BagsAdamGroup * L.ADAM_MAX_GROUPS)(*part))
+                fold = stats_block is not None and P == stats_P and dev == stats_dev      # into exactly one launch
+                L.call("bags_adam_step", dev, args, stats_block if fold else None)
+                if fold:
+                    stats_block = None
         return loss

@@ -61,8 +61,7 @@ class GaussianRasterizationSettings(NamedTuple):
     depth_weights_grad: bool = False
 
 
-def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
-    return None if t is None else t.data_ptr()
+_ptr = L.ptr
 
 
 def _f32c(t: Optional[torch.Tensor], name: str, device: torch.device, shape=None, empty_ok: bool = False) -> Optional[torch.Tensor]:
@@ -89,10 +88,8 @@ class _Packed:
 
     def __init__(self, settings: GaussianRasterizationSettings, means3D, means2D, shift_factors, sh, colors_precomp,
                  opacities, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, intrinsic, campos, sh_rest=None):
+        _require_gpu(means3D)
         dev = means3D.device
-        if dev.type != "cuda":
-            raise RuntimeError("bags_raster runs only on an AMD GPU: tensors must be on a 'cuda' (ROCm) device; "
-                               "there is no CPU path")
         P = means3D.shape[0]
         self.device, self.P = dev, P
         k = {}
@@ -166,13 +163,10 @@ class _Packed:
 
 
 def _require_gpu(t: torch.Tensor) -> None:
-    if not torch.is_tensor(t) or t.device.type != "cuda":
-        raise RuntimeError("bags_raster runs only on an AMD GPU: tensors must be on a 'cuda' (ROCm) device; "
-                           "there is no CPU path")
+    L.require("bags_raster", "means3D", t, gpu=True, type_error=RuntimeError)
 
 
-def _bytes(n: int, device) -> torch.Tensor:
-    return torch.empty(int(n), dtype=torch.uint8, device=device)
+_bytes = L.workspace
 
 
 LAST_NUM_RENDERED = 0      # instance count of the most recent forward whose count has been read (bench/diagnostics)
@@ -265,7 +259,6 @@ class FactoredSH:
         lent, self.target = self.target, None
         if not views:
             return
-        lib = L.load()
         dev, P = means3D.device, means3D.shape[0]
         deg = views[0][2]
         if any(v[2] != deg for v in views):
@@ -286,27 +279,23 @@ class FactoredSH:
         if shs_rest is not None and targets[0][1] != targets[1][1]:
             raise RuntimeError("FactoredSH.finish: shs and shs_rest must both hold a gradient, or neither")
         accumulate = 0 if targets[0][1] else 1
-        m3 = means3D.detach()
-        if m3.dtype != torch.float32 or not m3.is_contiguous():
-            m3 = m3.to(torch.float32).contiguous()
-        with torch.cuda.device(dev):
-            cur = torch.cuda.current_stream(dev)
-            for v in views:                                   # the views' backwards may have run on other streams
+        m3 = L.as_f32c(means3D)
+        cur = torch.cuda.current_stream(dev)                  # (the stream L.call launches on)
+        for v in views:                                       # the views' backwards may have run on other streams
+            if v[3] != cur:
+                cur.wait_stream(v[3])
+        for b in range(0, len(views), L.MAX_SH_VIEWS):
+            part = views[b:b + L.MAX_SH_VIEWS]
+            sv = L.BagsShViews()
+            sv.n_views = len(part)
+            for j, v in enumerate(part):
+                sv.campos[j], sv.dldc[j] = v[0].data_ptr(), v[1].data_ptr()
+            L.call("bags_sh_gradient_from_views", dev, P, M, deg, m3.data_ptr(), C.byref(sv), targets[0][0].data_ptr(),
+                   None if targets[1] is None else targets[1][0].data_ptr(), accumulate)
+            accumulate = 1
+            for v in part:                                    # the factored tensors are read on `cur`: tell their allocator streams
                 if v[3] != cur:
-                    cur.wait_stream(v[3])
-            for b in range(0, len(views), L.MAX_SH_VIEWS):
-                part = views[b:b + L.MAX_SH_VIEWS]
-                sv = L.BagsShViews()
-                sv.n_views = len(part)
-                for j, v in enumerate(part):
-                    sv.campos[j], sv.dldc[j] = v[0].data_ptr(), v[1].data_ptr()
-                L.check(lib.bags_sh_gradient_from_views(P, M, deg, m3.data_ptr(), C.byref(sv), targets[0][0].data_ptr(),
-                                                        None if targets[1] is None else targets[1][0].data_ptr(), accumulate, cur.cuda_stream),
-                        "bags_sh_gradient_from_views")
-                accumulate = 1
-                for v in part:                                # the factored tensors are read on `cur`: tell their allocator streams
-                    if v[3] != cur:
-                        v[1].record_stream(cur)
+                    v[1].record_stream(cur)
 
 
 FACTORED_SH: Optional[FactoredSH] = None
@@ -809,8 +798,7 @@ def debug_views(settings: GaussianRasterizationSettings, means3D, means2D, shift
         views = L.BagsDebugViews(*[v[n].data_ptr() for n in ("tiles_touched", "rect", "depth_bits", "point_list",
                                                              "keys_sorted", "ranges", "n_contrib", "final_T")])
         state = _state_of(fw)
-        L.check(lib.bags_debug_views(C.byref(pk.settings), C.byref(pk.inputs), C.byref(state), I, C.byref(views),
-                                     torch.cuda.current_stream(dev).cuda_stream), "bags_debug_views")
+        L.call("bags_debug_views", dev, C.byref(pk.settings), C.byref(pk.inputs), C.byref(state), I, C.byref(views))
         v["point_list"], v["keys_sorted"] = v["point_list"][:I], v["keys_sorted"][:I]
         v["num_rendered"] = I
         v["outputs"] = outs

@@ -1,5 +1,5 @@
 """No-GPU checks of the operator's host logic (bags_raster/rasterizer.py): capacity hints of the speculative forward, the
-parking / collection of lazy forwards nobody differentiated, argument validation of the settings added in round 4."""
+parking / collection of lazy forwards nobody differentiated, argument validation of the settings added in round 4; and the helpers every wrapper crosses the C boundary with (bags_raster/_lib.py)."""
 import warnings
 
 import pytest
@@ -94,6 +94,68 @@ def test_settings_reject_unknown_modes_before_touching_the_device():
     assert st.clamp_grad == "stock" and st.tile_bounds == "opacity" and st.binning == "auto"      # the operator's defaults
     with pytest.raises(RuntimeError, match="AMD GPU"):                                             # CPU tensors: no fallback
         GaussianRasterizer(st)(means3D=z(2, 3), means2D=z(2, 3), opacities=z(2, 1), shs=z(2, 1, 3), scales=z(2, 3), rotations=z(2, 4))
+
+def test_boundary_helpers_prepare_arguments_without_copies():
+    from bags_raster import _lib as L
+    assert L.ptr(None) is None and L.as_f32c(None) is None
+    x = torch.arange(12, dtype=torch.float32).view(3, 4)
+    assert L.ptr(x) == x.data_ptr()
+    assert L.as_f32c(x) is x                                          # already float32 and contiguous: the argument itself
+    leaf = x.clone().requires_grad_(True)
+    got = L.as_f32c(leaf)
+    assert got.data_ptr() == leaf.data_ptr() and not got.requires_grad          # detached, still no copy
+    for other in (x.double(), x.t()):
+        got = L.as_f32c(other)
+        assert got.dtype == torch.float32 and got.is_contiguous() and got.data_ptr() != other.data_ptr()
+        assert got.shape == other.shape and torch.equal(got, other.to(torch.float32))
+    ws = L.workspace(0, "cpu")                                        # the zero-size rule: an empty tensor, NULL at the boundary
+    assert ws.numel() == 0 and ws.dtype == torch.uint8 and ws.data_ptr() == 0
+    assert L.workspace(33, "cpu").numel() == 33
+
+
+def test_require_names_operation_and_argument_and_keeps_each_call_sites_exception_type():
+    from bags_raster import _lib as L
+    x = torch.zeros(3, 4)
+    L.require("op", "x", x, f32=True, contiguous=True, on=x)         # qualifies: nothing raised
+    with pytest.raises(RuntimeError, match=r"op runs only on an AMD GPU: x must be on a 'cuda' \(ROCm\) device, got cpu.*GPU tensor.*no CPU fallback \(use y\)"):
+        L.require("op", "x", x, gpu=True, host=" (use y)")
+    for kw, exc in ((dict(), TypeError), (dict(type_error=RuntimeError), RuntimeError)):
+        with pytest.raises(exc, match="op: x must be float32, got torch.float64"):
+            L.require("op", "x", x.double(), f32=True, **kw)
+        with pytest.raises(exc, match="op: x must be a tensor, got list"):
+            L.require("op", "x", [1.0], **kw)
+    for kw, exc in ((dict(), RuntimeError), (dict(layout_error=TypeError), TypeError)):
+        with pytest.raises(exc, match="op: x must be contiguous"):
+            L.require("op", "x", x.t(), contiguous=True, **kw)
+    with pytest.raises(RuntimeError, match="op: x is sparse"):
+        L.require("op", "x", x.to_sparse(), contiguous=True)
+    with pytest.raises(RuntimeError, match="op: x is on meta, expected cpu"):
+        L.require("op", "x", torch.empty(1, device="meta"), on=x)
+
+
+def test_call_refuses_an_unknown_symbol_before_touching_the_device(monkeypatch):
+    from bags_raster import _lib as L
+
+    def no_device(*a, **k):
+        raise AssertionError("the device was touched")
+    monkeypatch.setattr(torch.cuda, "device", no_device)
+    monkeypatch.setattr(torch.cuda, "current_stream", no_device)
+    assert "bags_no_such_entry_point" not in L.SYMBOLS
+    with pytest.raises(AttributeError, match="bags_no_such_entry_point"):
+        L.call("bags_no_such_entry_point", torch.device("cuda", 0), 1, 2)
+
+
+def test_check_names_the_symbol_and_the_library_error():
+    from bags_raster import _lib as L
+    lib = L.load()
+    L.check(0, "bags_sh_colors_forward")                              # success: nothing raised
+    rc = lib.bags_sh_colors_forward(L.BagsShColors(P=0, K=16, sh_degree=4, reserved=0), None, None)      # refused in validation: no launch
+    assert rc != 0
+    said = lib.bags_last_error().decode()
+    assert "sh_degree 4" in said
+    with pytest.raises(RuntimeError) as e:
+        L.check(rc, "bags_sh_colors_forward")
+    assert "bags_sh_colors_forward" in str(e.value) and said in str(e.value) and f"(code {rc})" in str(e.value)
 
 
 
