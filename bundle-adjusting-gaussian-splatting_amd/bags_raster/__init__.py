@@ -6,11 +6,11 @@ Mirrors the operator API of the reference's ``diff_gaussian_rasterization`` pack
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, rasterize_gaussians, debug_views,
                          compute_relocation)
 
-from .render import render, PipelineParams
-from .gaussians import GaussianBag, eval_sh, sh_colors
+from .render import render, render_views, PipelineParams
+from .gaussians import GaussianBag, eval_sh, sh_colors, sh_colors_views
 from .io import save_ply, load_ply, save_checkpoint, load_checkpoint
 from .optim import GaussianAdam
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "debug_views",
-           "compute_relocation", "render", "PipelineParams", "GaussianBag", "eval_sh", "sh_colors",
+           "compute_relocation", "render", "render_views", "PipelineParams", "GaussianBag", "eval_sh", "sh_colors", "sh_colors_views",
            "save_ply", "load_ply", "save_checkpoint", "load_checkpoint", "GaussianAdam"]

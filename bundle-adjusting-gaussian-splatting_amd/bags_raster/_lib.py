@@ -95,6 +95,11 @@ class BagsShColors(C.Structure):
                 ("xyz", c_fp), ("campos", c_fp)]
 
 
+class BagsShColorsViews(C.Structure):       # the V <= MAX_SH_VIEWS views of one step; the pointer tables of its entry points: c_fp * V
+    _fields_ = [("P", C.c_int32), ("K", C.c_int32), ("sh_degree", C.c_int32), ("V", C.c_int32), ("shs", c_fp), ("shs_rest", c_fp),
+                ("xyz", c_fp), ("campos", c_fp * MAX_SH_VIEWS)]
+
+
 ADAM_MAX_GROUPS = 8
 
 
@@ -178,6 +183,10 @@ SYMBOLS = {    "bags_abi_version": (C.c_int, []),
     "bags_sh_colors_workspace_size": (C.c_size_t, [C.c_int32]),
     "bags_sh_colors_forward": (C.c_int, [C.POINTER(BagsShColors), c_fp, C.c_void_p]),
     "bags_sh_colors_backward": (C.c_int, [C.POINTER(BagsShColors), c_fp, C.c_void_p, C.c_size_t, c_fp, c_fp, c_fp, c_fp, C.c_void_p]),
+    "bags_sh_colors_views_workspace_size": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "bags_sh_colors_views_forward": (C.c_int, [C.POINTER(BagsShColorsViews), C.POINTER(c_fp), C.c_void_p]),
+    "bags_sh_colors_views_backward": (C.c_int, [C.POINTER(BagsShColorsViews), C.POINTER(c_fp), C.c_void_p, C.c_size_t, c_fp, c_fp, c_fp,
+                                                C.POINTER(c_fp), C.c_void_p]),
     "bags_adam_step": (C.c_int, [C.POINTER(BagsAdamArgs), C.POINTER(BagsDensifyStats), C.c_void_p]),
     "bags_densify_workspace_size": (C.c_size_t, [C.c_int32]),
     "bags_densify_plan": (C.c_int, [C.POINTER(BagsDensifyRule), C.c_void_p, C.c_size_t, C.POINTER(C.c_int64), C.c_void_p]),
@@ -241,6 +250,11 @@ def profile_read():
 def ptr(t):
     """What a ``c_void_p`` parameter or struct field takes for an optional tensor: None (NULL) or its device address."""
     return None if t is None else t.data_ptr()
+
+
+def ptr_table(ts):
+    """A ``const float* const []`` parameter or struct field: the device addresses of ``ts`` (None entries are NULL), host side."""
+    return (c_fp * len(ts))(*[ptr(t) for t in ts])
 
 
 def workspace(nbytes: int, device) -> torch.Tensor:

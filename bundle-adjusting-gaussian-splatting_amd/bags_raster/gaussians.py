@@ -19,7 +19,7 @@ fused HIP calls (csrc/densify.hip) and, unlike the rest of this module, run only
 from __future__ import annotations
 
 import math
-from typing import Dict, Optional
+from typing import Dict, Optional, Tuple
 
 import torch
 
@@ -451,3 +451,90 @@ def sh_colors(deg: int, shs: torch.Tensor, xyz: torch.Tensor, campos: torch.Tens
     for name, t in named:
         L.require(what, name, t, gpu=True, on=xyz, host=" (bags_raster.eval_sh is the host-side evaluation)")
     return _ShColors.apply(deg, shs, shs_rest, xyz, campos)
+
+
+class _ShColorsViews(torch.autograd.Function):
+    """``sh_colors`` for the V views of one step: V separate ``(P,3)`` outputs, one launch each way.  A view no loss depends on
+    arrives in ``backward`` as None (``set_materialize_grads(False)``) and goes down as a NULL pointer."""
+
+    @staticmethod
+    def forward(ctx, deg, shs, shs_rest, xyz, *camposes):
+        ts = [L.as_f32c(t) for t in (shs, shs_rest, xyz) + camposes]
+        V, P = len(camposes), ts[2].shape[0]
+        K = ts[0].shape[1] + (0 if ts[1] is None else ts[1].shape[1])
+        rgb = tuple(torch.empty(P, 3, dtype=torch.float32, device=ts[2].device) for _ in range(V))
+        args = L.BagsShColorsViews(P, K, deg, V, L.ptr(ts[0]), L.ptr(ts[1]), L.ptr(ts[2]), L.ptr_table(ts[3:] + [None] * (L.MAX_SH_VIEWS - V)))
+        L.call("bags_sh_colors_views_forward", ts[2].device, args, L.ptr_table(rgb))
+        ctx.deg, ctx.split = deg, ts[1] is not None
+        ctx.save_for_backward(*[t for t in ts if t is not None])       # the inputs and nothing else, as _ShColors
+        ctx.set_materialize_grads(False)
+        return rgb
+
+    @staticmethod
+    def backward(ctx, *g_rgb):
+        ts = list(ctx.saved_tensors)
+        if not ctx.split:
+            ts.insert(1, None)
+        shs, rest, xyz, camposes = ts[0], ts[1], ts[2], ts[3:]
+        V, P = len(camposes), xyz.shape[0]
+        if all(g is None for g in g_rgb):
+            return (None,) * (4 + V)
+        K = shs.shape[1] + (0 if rest is None else rest.shape[1])
+        need = ctx.needs_input_grad
+        g_rgb = [L.as_f32c(g) for g in g_rgb]
+        out = [torch.empty_like(t) if (t is not None and need[k]) else None for k, t in ((1, shs), (2, rest), (3, xyz))]
+        g_campos = [torch.empty_like(c) if need[4 + v] else None for v, c in enumerate(camposes)]
+        args = L.BagsShColorsViews(P, K, ctx.deg, V, L.ptr(shs), L.ptr(rest), L.ptr(xyz), L.ptr_table(camposes + [None] * (L.MAX_SH_VIEWS - V)))
+        wanted = any(g is not None for g in g_campos)                  # (only dL/dcampos needs a workspace)
+        ws = L.workspace(L.load().bags_sh_colors_views_workspace_size(P, V) if wanted else 0, xyz.device)
+        L.call("bags_sh_colors_views_backward", xyz.device, args, L.ptr_table(g_rgb), ws.data_ptr(), ws.numel(), *[L.ptr(o) for o in out],
+               L.ptr_table(g_campos))
+        return (None,) + tuple(out) + tuple(g_campos)
+
+
+def sh_colors_views(deg: int, shs: torch.Tensor, xyz: torch.Tensor, camposes, shs_rest: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, ...]:
+    """``sh_colors`` for the V views of one step over the same Gaussians: ``camposes`` is a sequence of V ``(3,)`` camera centres
+    (1 <= V <= 16), the result a tuple of V ``(P,3)`` tensors, view v's the bits ``sh_colors(deg, shs, xyz, camposes[v])`` gives.
+
+    One HIP launch each way for all the views: the coefficient rows are read once in the forward and once in the backward, and the
+    gradients of ``shs`` / ``shs_rest`` / ``xyz`` are summed over the views on the chip, in view order, and written once -- the bits
+    of the fp32 fold of the per-view gradients, without autograd's ``grad += g`` per view.  Each camera centre gets its own
+    gradient.  A view whose colours no loss uses costs nothing in the backward.  Layouts and limits as ``sh_colors``."""
+    what = "sh_colors_views"
+    deg = int(deg)
+    if not 0 <= deg <= 3:
+        raise ValueError(f"{what}: SH degree must be in 0..3, got {deg}")
+    if isinstance(camposes, torch.Tensor) or not isinstance(camposes, (list, tuple)):
+        raise TypeError(f"{what}: camposes must be a list or tuple of (3,) tensors, got {type(camposes).__name__}")
+    V = len(camposes)
+    if not 1 <= V <= L.MAX_SH_VIEWS:
+        raise ValueError(f"{what}: the number of views must be in 1..{L.MAX_SH_VIEWS}, got {V} (more views: one call per chunk)")
+    named = ([("shs", shs), ("xyz", xyz)] + [(f"camposes[{v}]", c) for v, c in enumerate(camposes)]
+             + ([("shs_rest", shs_rest)] if shs_rest is not None else []))
+    for name, t in named:
+        L.require(what, name, t, f32=True)
+    if xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise RuntimeError(f"{what}: xyz must be (P,3), got {tuple(xyz.shape)}")
+    P = xyz.shape[0]
+    for v, c in enumerate(camposes):
+        if tuple(c.shape) != (3,):
+            raise RuntimeError(f"{what}: camposes[{v}] must be (3,), got {tuple(c.shape)}")
+    if shs_rest is None:
+        if shs.dim() != 3 or shs.shape[0] != P or shs.shape[2] != 3:
+            raise RuntimeError(f"{what}: shs must be ({P},K,3) for xyz {tuple(xyz.shape)}, got {tuple(shs.shape)}")
+        K = shs.shape[1]
+    else:
+        if tuple(shs.shape) != (P, 1, 3):
+            raise RuntimeError(f"{what}: with shs_rest, shs must be the ({P},1,3) DC part for xyz {tuple(xyz.shape)}, got {tuple(shs.shape)}")
+        if shs_rest.dim() != 3 or shs_rest.shape[0] != P or shs_rest.shape[2] != 3 or shs_rest.shape[1] < 1:
+            raise RuntimeError(f"{what}: shs_rest must be ({P},K-1,3) with K >= 2 for shs {tuple(shs.shape)}, got {tuple(shs_rest.shape)}")
+        K = 1 + shs_rest.shape[1]
+    if K not in (1, 4, 9, 16):
+        raise RuntimeError(f"{what}: K = {K} stored coefficients (shs {tuple(shs.shape)}"
+                           + (f", shs_rest {tuple(shs_rest.shape)}" if shs_rest is not None else "") + "): K must be 1, 4, 9 or 16")
+    if K < (deg + 1) ** 2:
+        raise RuntimeError(f"{what}: degree {deg} needs {(deg + 1) ** 2} coefficients, shs"
+                           + (" + shs_rest hold " if shs_rest is not None else " holds ") + f"{K} (shs {tuple(shs.shape)})")
+    for name, t in named:
+        L.require(what, name, t, gpu=True, on=xyz, host=" (bags_raster.eval_sh is the host-side evaluation)")
+    return _ShColorsViews.apply(deg, shs, shs_rest, xyz, *camposes)

@@ -12,6 +12,9 @@ arguments, same choice of covariance path (``pipe.compute_cov3D_python``) and co
   * the two screen-space gradient sinks are leaf tensors (the reference: ``zeros + 0`` with ``retain_grad()``, :37-44);
   * on a GPU the Python-side SH colours (``hybrid`` / ``pipe.convert_SHs_python``) come from ``bags_raster.sh_colors``, one HIP
     launch each way, fed with ``_features_dc`` / ``_features_rest`` as stored; ``_python_colors`` is the host path.
+
+``render_views()`` is ``render()`` for the V cameras of one step: the same dictionaries, the activations once, and on the fused
+colour path one ``bags_raster.sh_colors_views`` call for the colours of all the cameras.
 """
 from __future__ import annotations
 
@@ -21,7 +24,8 @@ from typing import Optional
 
 import torch
 
-from .gaussians import eval_sh, sh_colors
+from ._lib import MAX_SH_VIEWS
+from .gaussians import eval_sh, sh_colors, sh_colors_views
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer
 
 
@@ -54,12 +58,8 @@ def _python_colors(pc, xyz, feats, campos: torch.Tensor, mlp_color) -> torch.Ten
     return rgb + mlp_color
 
 
-def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, mlp_color, shift_factors, hybrid: bool = True,
-           scaling_modifier: float = 1.0, override_color: Optional[torch.Tensor] = None, iteration: Optional[int] = None,
-           global_alignment=None, depth_key: str = "z", depth_weights_grad: bool = False):
-    """Signature and defaults of gaussian_renderer/__init__.py:30: ``mlp_color`` and ``shift_factors`` are positional and
-    required, ``hybrid`` defaults to True (Python-side SH colours + ``mlp_color``).  ``shift_factors=None`` stands for the
-    zero vector the reference keeps (train.py:125-126: its optimizer is never stepped)."""
+def _activate(pc, pipe, hybrid: bool, override_color) -> SimpleNamespace:
+    """What a call needs from the Gaussian set, whichever camera it is for: the colour path and the activated parameters."""
     # activations: one fused launch when the container offers it (GaussianBag on a GPU), else the reference's properties
     # rasterizer-side SH colours and, on a GPU, the Python-side ones (bags_raster.sh_colors): the two feature parameters go to the
     # kernel as they are stored (shs = features_dc, shs_rest = features_rest), without get_features' torch.cat; every other colour
@@ -74,20 +74,33 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, mlp_color, shift_
     else:                                                      # any container with the reference's properties (GaussianModel)
         xyz, opacity, scaling, rotation = pc.get_xyz, pc.get_opacity, pc.get_scaling, pc.get_rotation
         features = None if split else pc.get_features
+    return SimpleNamespace(fused_colors=fused_colors, split=split, xyz=xyz, features=features, opacity=opacity, scaling=scaling,
+                           rotation=rotation)
+
+
+def _camera_chain(viewpoint_camera, global_alignment):
+    """viewmatrix, projmatrix, intrinsic, campos of one camera (gaussian_renderer/__init__.py:57,58,61)."""
+    ga = global_alignment if global_alignment is not None else (None, None)
+    if hasattr(viewpoint_camera, "get_matrices"):              # one HIP launch (bags_raster.camera.PoseCamera)
+        return viewpoint_camera.get_matrices(ga[0], ga[1])
+    # any camera object with the reference's four getters
+    viewmatrix = viewpoint_camera.get_world_view_transform(ga[0], ga[1])
+    intrinsic = viewpoint_camera.get_intrinsic()
+    projmatrix = (viewmatrix.unsqueeze(0).bmm(intrinsic.unsqueeze(0))).squeeze(0)
+    return viewmatrix, projmatrix, intrinsic, viewmatrix.inverse()[3, :3]
+
+
+def _rasterize_view(viewpoint_camera, pc, pipe, bg_color, mlp_color, shift_factors, hybrid, scaling_modifier, override_color, iteration,
+                    depth_key, depth_weights_grad, act, matrices, fused_rgb):
+    """One camera's rasterizer call and the returned dictionary.  ``act``: ``_activate``'s result; ``matrices``: ``_camera_chain``'s;
+    ``fused_rgb``: this view's ``sh_colors`` / ``sh_colors_views`` output where ``act.fused_colors``, else None."""
+    xyz = act.xyz
     # zero tensors whose .grad receives the screen-space gradients (:37-44)
     # (leaves: `.grad` is populated as with the reference's `zeros + 0` / retain_grad() pair, without the two adds and the two
     # 6 MB gradient copies that pair costs per call)
     screenspace_points = torch.zeros_like(xyz, requires_grad=True)
     screenspace_points_densify = torch.zeros_like(xyz, requires_grad=True)
-
-    ga = global_alignment if global_alignment is not None else (None, None)
-    if hasattr(viewpoint_camera, "get_matrices"):              # one HIP launch (bags_raster.camera.PoseCamera)
-        viewmatrix, projmatrix, intrinsic, campos = viewpoint_camera.get_matrices(ga[0], ga[1])
-    else:                                                      # any camera object with the reference's four getters
-        viewmatrix = viewpoint_camera.get_world_view_transform(ga[0], ga[1])
-        intrinsic = viewpoint_camera.get_intrinsic()
-        projmatrix = (viewmatrix.unsqueeze(0).bmm(intrinsic.unsqueeze(0))).squeeze(0)
-        campos = viewmatrix.inverse()[3, :3]
+    viewmatrix, projmatrix, intrinsic, campos = matrices
 
     raster_settings = GaussianRasterizationSettings(
         image_height=int(viewpoint_camera.image_height),
@@ -113,24 +126,21 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, mlp_color, shift_
     if pipe.compute_cov3D_python:
         cov3D_precomp = pc.get_covariance(scaling_modifier)
     else:
-        scales, rotations = scaling, rotation
+        scales, rotations = act.scaling, act.rotation
 
     shs = shs_rest = colors_precomp = None
     if override_color is not None:
         colors_precomp = override_color
-    elif fused_colors:                                         # one HIP launch each way; `+ mlp_color` stays in PyTorch
-        if split:
-            colors_precomp = sh_colors(pc.active_sh_degree, pc._features_dc, xyz, campos, shs_rest=pc._features_rest)
-        else:
-            colors_precomp = sh_colors(pc.active_sh_degree, features, xyz, campos)
+    elif act.fused_colors:                                     # one HIP launch each way; `+ mlp_color` stays in PyTorch
+        colors_precomp = fused_rgb
         if not (isinstance(mlp_color, (int, float)) and mlp_color == 0):          # the reference passes 0
             colors_precomp = colors_precomp + mlp_color
     elif hybrid or pipe.convert_SHs_python:
-        colors_precomp = _python_colors(pc, xyz, features, campos, mlp_color)
-    elif split:
+        colors_precomp = _python_colors(pc, xyz, act.features, campos, mlp_color)
+    elif act.split:
         shs, shs_rest = pc._features_dc, pc._features_rest
     else:
-        shs = features
+        shs = act.features
 
     if shift_factors is None:
         shift_factors = _ZERO3.get(xyz.device)
@@ -139,7 +149,7 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, mlp_color, shift_
 
     rendered_image, radii, depth, weights, mean2D = rasterizer(
         means3D=xyz, means2D=screenspace_points, means2D_densify=screenspace_points_densify,
-        shift_factors=shift_factors, shs=shs, colors_precomp=colors_precomp, opacities=opacity,
+        shift_factors=shift_factors, shs=shs, colors_precomp=colors_precomp, opacities=act.opacity,
         scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp, **({"shs_rest": shs_rest} if shs_rest is not None else {}))
 
     return {"render": rendered_image,
@@ -150,3 +160,53 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, mlp_color, shift_
             "depth": depth,
             "weights": weights,
             "means2D": mean2D}
+
+
+def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, mlp_color, shift_factors, hybrid: bool = True,
+           scaling_modifier: float = 1.0, override_color: Optional[torch.Tensor] = None, iteration: Optional[int] = None,
+           global_alignment=None, depth_key: str = "z", depth_weights_grad: bool = False):
+    """Signature and defaults of gaussian_renderer/__init__.py:30: ``mlp_color`` and ``shift_factors`` are positional and
+    required, ``hybrid`` defaults to True (Python-side SH colours + ``mlp_color``).  ``shift_factors=None`` stands for the
+    zero vector the reference keeps (train.py:125-126: its optimizer is never stepped)."""
+    act = _activate(pc, pipe, hybrid, override_color)
+    matrices = _camera_chain(viewpoint_camera, global_alignment)
+    fused_rgb = None
+    if act.fused_colors:
+        if act.split:
+            fused_rgb = sh_colors(pc.active_sh_degree, pc._features_dc, act.xyz, matrices[3], shs_rest=pc._features_rest)
+        else:
+            fused_rgb = sh_colors(pc.active_sh_degree, act.features, act.xyz, matrices[3])
+    return _rasterize_view(viewpoint_camera, pc, pipe, bg_color, mlp_color, shift_factors, hybrid, scaling_modifier, override_color,
+                           iteration, depth_key, depth_weights_grad, act, matrices, fused_rgb)
+
+
+# render_views' fused colour branch: True = one sh_colors_views call per chunk of cameras, False = one sh_colors call per camera.
+# (profiles/sh_colors/NOTES.md holds the measurement this default rests on.)
+MULTI_VIEW_COLORS = True
+
+
+def render_views(cameras, pc, pipe, bg_color: torch.Tensor, mlp_color, shift_factors, hybrid: bool = True,
+                 scaling_modifier: float = 1.0, override_color: Optional[torch.Tensor] = None, iteration: Optional[int] = None,
+                 global_alignment=None, depth_key: str = "z", depth_weights_grad: bool = False):
+    """``[render(cam, pc, ...) for cam in cameras]`` for the views of ONE step (a cubemap's faces, a rank's V views): a list of
+    ``render()``'s dictionaries, every tensor in them the bits ``render()`` gives for that camera.
+
+    The activations are evaluated once for the list and the camera chain once per camera.  On ``render()``'s fused colour branch
+    (a GPU, ``hybrid`` or ``pipe.convert_SHs_python``, no ``override_color``) the colours of up to 16 cameras come from one
+    ``sh_colors_views`` call: the coefficient rows are read once each way for all of them, and one backward through the summed
+    loss writes each Gaussian gradient once instead of accumulating it view by view.  On every other colour path each camera
+    takes the path ``render()`` takes."""
+    cameras = list(cameras)
+    act = _activate(pc, pipe, hybrid, override_color)
+    matrices = [_camera_chain(cam, global_alignment) for cam in cameras]
+    fused_rgb = [None] * len(cameras)
+    if act.fused_colors:
+        shs, rest = (pc._features_dc, pc._features_rest) if act.split else (act.features, None)
+        if MULTI_VIEW_COLORS:
+            for b in range(0, len(cameras), MAX_SH_VIEWS):
+                fused_rgb[b:b + MAX_SH_VIEWS] = sh_colors_views(pc.active_sh_degree, shs, act.xyz, [m[3] for m in matrices[b:b + MAX_SH_VIEWS]],
+                                                                shs_rest=rest)
+        else:
+            fused_rgb = [sh_colors(pc.active_sh_degree, shs, act.xyz, m[3], shs_rest=rest) for m in matrices]
+    return [_rasterize_view(cam, pc, pipe, bg_color, mlp_color, shift_factors, hybrid, scaling_modifier, override_color, iteration,
+                            depth_key, depth_weights_grad, act, m, rgb) for cam, m, rgb in zip(cameras, matrices, fused_rgb)]

@@ -203,6 +203,14 @@ static size_t carve_sh_colors(void* base, int P, float** slab)
     return c.used();
 }
 
+static size_t carve_sh_colors_views(void* base, int P, int V, float** slab)
+{
+    Carver c(base);
+    float* s = c.take<float>((size_t)(V > 0 ? V : 1) * cdiv(P > 0 ? P : 1, 256) * SH_SLAB);   // view-major: one row per (view, workgroup)
+    if (slab) *slab = s;
+    return c.used();
+}
+
 // ---------------------------------------------------------------------------------------------- validation
 static int check_common(const BagsSettings* s, const BagsInputs* in, const BagsState* stt)
 {
@@ -776,6 +784,57 @@ int bags_sh_colors_backward(const BagsShColors* a, const float* grad_rgb, void* 
         carve_sh_colors(workspace, a->P, &slab);
     }
     HIP_TRY(launch_sh_colors_bwd(*a, grad_rgb, slab, grad_shs, grad_shs_rest, grad_xyz, grad_campos, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
+// the V views of one step: the single-view rules for everything the views share, then the table
+static int check_sh_colors_views(const BagsShColorsViews* a)
+{
+    if (!a) return fail(BAGS_ERR_ARG, "sh_colors_views: null struct");
+    if (a->V < 1 || a->V > BAGS_MAX_SH_VIEWS)
+        return fail(BAGS_ERR_ARG, "sh_colors_views: V %d not in 1..%d (more views: one call per chunk)", a->V, BAGS_MAX_SH_VIEWS);
+    const BagsShColors one{a->P, a->K, a->sh_degree, 0, a->shs, a->shs_rest, a->xyz, a->campos[0]};
+    int rc = check_sh_colors(&one);
+    if (rc) return rc;
+    for (int v = 0; a->P > 0 && v < a->V; ++v)
+        if (!a->campos[v]) return fail(BAGS_ERR_ARG, "sh_colors_views: campos[%d] is NULL (V = %d)", v, a->V);
+    return BAGS_OK;
+}
+
+size_t bags_sh_colors_views_workspace_size(int32_t P, int32_t V) { return carve_sh_colors_views(nullptr, P, V, nullptr) + BASE_SLACK; }
+
+int bags_sh_colors_views_forward(const BagsShColorsViews* a, float* const rgb[], void* stream)
+{
+    int rc = check_sh_colors_views(a);
+    if (rc) return rc;
+    if (a->P == 0) return BAGS_OK;
+    if (!rgb) return fail(BAGS_ERR_ARG, "sh_colors_views_forward: null rgb table");
+    for (int v = 0; v < a->V; ++v)
+        if (!rgb[v]) return fail(BAGS_ERR_ARG, "sh_colors_views_forward: rgb[%d] is NULL (V = %d)", v, a->V);
+    HIP_TRY(launch_sh_colors_views_fwd(*a, rgb, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
+int bags_sh_colors_views_backward(const BagsShColorsViews* a, const float* const grad_rgb[], void* workspace, size_t workspace_bytes,
+                                  float* grad_shs, float* grad_shs_rest, float* grad_xyz, float* const grad_campos[], void* stream)
+{
+    int rc = check_sh_colors_views(a);
+    if (rc) return rc;
+    bool any_campos = false;
+    for (int v = 0; grad_campos && v < a->V; ++v) any_campos = any_campos || grad_campos[v] != nullptr;
+    if (!grad_shs && !grad_shs_rest && !grad_xyz && !any_campos) return BAGS_OK;
+    if (a->P > 0 && !grad_rgb) return fail(BAGS_ERR_ARG, "sh_colors_views_backward: null grad_rgb table (its entries may be NULL, the table not)");
+    if (grad_shs_rest && !a->shs_rest) return fail(BAGS_ERR_ARG, "sh_colors_views_backward: grad_shs_rest without shs_rest");
+    if ((reinterpret_cast<size_t>(grad_shs) | reinterpret_cast<size_t>(grad_shs_rest)) & 15)
+        return fail(BAGS_ERR_ARG, "sh_colors_views_backward: grad_shs / grad_shs_rest must be 16-byte aligned");
+    float* slab = nullptr;
+    if (any_campos) {
+        const size_t need = bags_sh_colors_views_workspace_size(a->P, a->V);
+        if (!workspace || workspace_bytes < need)
+            return fail(BAGS_ERR_SIZE, "sh_colors_views_backward: grad_campos needs a workspace of %zu bytes", need);
+        carve_sh_colors_views(workspace, a->P, a->V, &slab);
+    }
+    HIP_TRY(launch_sh_colors_views_bwd(*a, grad_rgb, slab, grad_shs, grad_shs_rest, grad_xyz, any_campos ? grad_campos : nullptr, (hipStream_t)stream));
     return BAGS_OK;
 }
 

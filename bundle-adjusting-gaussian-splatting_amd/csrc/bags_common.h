@@ -256,6 +256,10 @@ hipError_t launch_activations_bwd(int P, int K, const float* dc, const float* re
 hipError_t launch_sh_colors_fwd(const BagsShColors& a, float* rgb, hipStream_t st);
 hipError_t launch_sh_colors_bwd(const BagsShColors& a, const float* g_rgb, float* slab, float* g_shs, float* g_shs_rest, float* g_xyz,
                                 float* g_campos, hipStream_t st);
+// ... and the V views of one step in one pass each way; slab: V x SH_SLAB floats per workgroup, view-major (carve_sh_colors_views)
+hipError_t launch_sh_colors_views_fwd(const BagsShColorsViews& a, float* const* rgb, hipStream_t st);
+hipError_t launch_sh_colors_views_bwd(const BagsShColorsViews& a, const float* const* g_rgb, float* slab, float* g_shs, float* g_shs_rest,
+                                      float* g_xyz, float* const* g_campos, hipStream_t st);
 // adam.hip: torch.optim.Adam step of up to BAGS_ADAM_MAX_GROUPS parameter groups (+ densification statistics) in one launch
 hipError_t launch_adam(const BagsAdamArgs& args, const BagsDensifyStats* stats, hipStream_t st);
 // densify.hip: densify-and-prune (decide + scan, then map + gather) and the opacity reset

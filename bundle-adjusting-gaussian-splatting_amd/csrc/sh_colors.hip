@@ -18,6 +18,12 @@
 // zeros.  The SH gradient rows leave as whole lines through LDS (K9's store pass); the campos sums go wave (DPP) -> workgroup ->
 // one slab row, and sh_campos_reduce_kernel adds the rows in fp64 in a fixed order (a last-workgroup tail inside the kernel is the
 // fold that lost twice for pose_reduce).  No atomics: every gradient is bitwise reproducible.
+//
+// Multi-view form (sh_colors_views_*_kernel): the V <= BAGS_MAX_SH_VIEWS views of one step over the same Gaussians.
+// The row is read once each way; the forward stores 12 bytes per view, the backward adds the views' gradient rows in registers, in
+// view order, each product and each add rounded once -- the bits of the fp32 fold ((g_0 + g_1) + g_2) ... of the single-view
+// kernel's gradients -- and writes the row once.  The camera centres, the outputs and the cotangents travel as pointer tables by
+// value in the kernel arguments (adam.hip's group table): nothing is uploaded.
 #include "bags_common.h"
 #include "sh_basis.h"
 
@@ -199,11 +205,9 @@ sh_colors_bwd_kernel(const ShcIn A, const float* __restrict__ g_rgb, float* __re
 
 // slab rows -> dL/dcampos in fp64: one workgroup per component, thread t adds rows t, t + 256, ... in row order, the lanes of a
 // wave by a fixed shuffle tree, the four waves in wave order (pose_reduce_kernel's scheme, clamped batched loads included)
-__global__ void __launch_bounds__(256)
-sh_campos_reduce_kernel(const float* __restrict__ slab, const int nblocks, float* __restrict__ g_campos)
+__device__ __forceinline__ void shc_campos_reduce(const float* __restrict__ slab, const int nblocks, const int t, float* __restrict__ g_campos)
 {
     __shared__ double wsum[4];
-    const int t = blockIdx.x;
     double acc = 0.0;
     for (int b = threadIdx.x; b < nblocks; b += 8 * 256) {
         float v[8];
@@ -217,6 +221,185 @@ sh_campos_reduce_kernel(const float* __restrict__ slab, const int nblocks, float
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) g_campos[t] = (float)(((wsum[0] + wsum[1]) + wsum[2]) + wsum[3]);
+}
+
+__global__ void __launch_bounds__(256)
+sh_campos_reduce_kernel(const float* __restrict__ slab, const int nblocks, float* __restrict__ g_campos)
+{
+    shc_campos_reduce(slab, nblocks, blockIdx.x, g_campos);
+}
+
+// ---------------------------------------------------------------------------------------------- the views of one step
+struct ShcViewsIn { int P, deg, V; const float *shs, *shs_rest, *xyz; const float* campos[BAGS_MAX_SH_VIEWS]; };
+struct ShcViewsOut { float* p[BAGS_MAX_SH_VIEWS]; };            // rgb (forward), dL/dcampos (reduction); an entry may be null
+struct ShcViewsCot { const float* p[BAGS_MAX_SH_VIEWS]; };      // dL/drgb per view; null = no loss depends on that view
+
+template <int K, bool SPLIT>
+__global__ void __launch_bounds__(256)
+sh_colors_views_fwd_kernel(const ShcViewsIn A, const ShcViewsOut O)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= A.P) return;
+    const int nb = (A.deg + 1) * (A.deg + 1);
+    const float x = A.xyz[3 * (size_t)i], y = A.xyz[3 * (size_t)i + 1], z = A.xyz[3 * (size_t)i + 2];
+    const ShcIn S{A.P, A.deg, A.shs, A.shs_rest, A.xyz, nullptr};
+    float c[48];
+    shc_load_row<K, SPLIT>(S, (size_t)i, nb, c);
+    for (int v = 0; v < A.V; ++v) {                      // per view: the single-view kernel's operations on campos_v
+        const float* __restrict__ cp = A.campos[v];
+        const float dx = x - cp[0], dy = y - cp[1], dz = z - cp[2];
+        const float dl = sqrtf(dx * dx + dy * dy + dz * dz);
+        float b[16];
+        sh_basis(A.deg, dx / dl, dy / dl, dz / dl, b);
+        float r, g, bl;
+        shc_raw<K>(nb, b, c, r, g, bl);
+        float* __restrict__ rgb = O.p[v];
+        rgb[3 * (size_t)i] = r < 0.f ? 0.f : r; rgb[3 * (size_t)i + 1] = g < 0.f ? 0.f : g; rgb[3 * (size_t)i + 2] = bl < 0.f ? 0.f : bl;
+    }
+}
+
+#define SHC_ROW 49       // floats per Gaussian in the backward's LDS stage: 48 + 1, so that the 64 lanes' own rows fall on distinct banks
+
+// The workgroup's 256 summed gradient rows of one tensor, R floats each starting at float F0 of the staged row, as whole lines
+// (shc_store_span's mapping: thread t owns float4 number t, t + 256, ... of the workgroup's span)
+template <u32 R, u32 F0>
+__device__ __forceinline__ void shc_store_sum_span(const float (*sacc)[SHC_ROW], float* __restrict__ out, const int P)
+{
+    const size_t first_f = (size_t)blockIdx.x * 256u * R, total = (size_t)P * R;
+#pragma unroll
+    for (u32 k = 0; k < (64u * R + 255u) / 256u; ++k) {
+        const u32 el = k * 256u + threadIdx.x;
+        const size_t g0 = first_f + (size_t)el * 4u;
+        if (el < 64u * R && g0 < total) {
+            float o4[4];
+#pragma unroll
+            for (u32 u = 0; u < 4; ++u) {
+                const u32 f = el * 4u + u, row = f / R, r = f - row * R;
+                o4[u] = sacc[row][F0 + r];
+            }
+            if (g0 + 3 < total) *reinterpret_cast<float4*>(out + g0) = make_float4(o4[0], o4[1], o4[2], o4[3]);
+            else {                                    // the tensor's last float4 may be partial (P R not a multiple of 4)
+                out[g0] = o4[0];
+                if (g0 + 1 < total) out[g0 + 1] = o4[1];
+                if (g0 + 2 < total) out[g0 + 2] = o4[2];
+            }
+        }
+    }
+}
+
+// One thread per Gaussian.  A thread's LDS row first holds its V cotangent triples (zeros for a view that contributes nothing: a
+// null pointer or an all-zero triple), so the view loop indexes them without a register array; after the loop it holds the summed
+// gradient row for the store pass.  slab: V x gridDim.x rows of 4 floats, view-major.
+template <int K, bool SPLIT>
+__global__ void __launch_bounds__(256)
+sh_colors_views_bwd_kernel(const ShcViewsIn A, const ShcViewsCot G, float* __restrict__ g_shs, float* __restrict__ g_shs_rest,
+                           float* __restrict__ g_xyz, float* __restrict__ slab, const int need_dir)
+{
+    __shared__ float sacc[256][SHC_ROW];
+    __shared__ float wsum[BAGS_MAX_SH_VIEWS][4][4];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const bool on = i < A.P;
+    const size_t ic = (size_t)(on ? i : A.P - 1);
+    const int nb = (A.deg + 1) * (A.deg + 1);
+    float* __restrict__ mine = &sacc[threadIdx.x][0];
+
+    // the cotangents first, four views' loads in flight together (a view without one reads the position instead: any valid triple)
+    u32 live = 0;
+#pragma unroll
+    for (int q = 0; q < BAGS_MAX_SH_VIEWS / 4; ++q)
+        if (4 * q < A.V) {
+            float t[4][3];
+            bool have[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const float* p = (4 * q + u < A.V) ? G.p[4 * q + u] : nullptr;
+                have[u] = p != nullptr;
+                const float* __restrict__ src = (have[u] ? p : A.xyz) + 3 * ic;
+                t[u][0] = src[0]; t[u][1] = src[1]; t[u][2] = src[2];
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const bool ok = on && have[u] && (t[u][0] != 0.f || t[u][1] != 0.f || t[u][2] != 0.f);
+                mine[3 * (4 * q + u)] = ok ? t[u][0] : 0.f; mine[3 * (4 * q + u) + 1] = ok ? t[u][1] : 0.f; mine[3 * (4 * q + u) + 2] = ok ? t[u][2] : 0.f;
+                live |= ok ? (1u << (4 * q + u)) : 0u;
+            }
+        }
+
+    float acc[48];
+#pragma unroll
+    for (int k = 0; k < 48; ++k) acc[k] = 0.f;
+    float gx = 0.f, gy = 0.f, gz = 0.f, x = 0.f, y = 0.f, z = 0.f;
+    float c[48];
+#pragma unroll
+    for (int k = 0; k < 48; ++k) c[k] = 0.f;
+    if (live) {                                          // a Gaussian no view contributes to reads nothing else and writes zeros
+        x = A.xyz[3 * ic]; y = A.xyz[3 * ic + 1]; z = A.xyz[3 * ic + 2];
+        const ShcIn S{A.P, A.deg, A.shs, A.shs_rest, A.xyz, nullptr};
+        shc_load_row<K, SPLIT>(S, ic, nb, c);
+    }
+    for (int v = 0; v < A.V; ++v) {
+        float nx = 0.f, ny = 0.f, nz = 0.f;              // this view's dL/dd, for its dL/dcampos
+        if ((live >> v) & 1u) {
+            const float* __restrict__ cp = A.campos[v];
+            const float g0 = mine[3 * v], g1 = mine[3 * v + 1], g2 = mine[3 * v + 2];
+            const float dx = x - cp[0], dy = y - cp[1], dz = z - cp[2];
+            const float dl = sqrtf(dx * dx + dy * dy + dz * dz);
+            const float ux = dx / dl, uy = dy / dl, uz = dz / dl;
+            float b[16];
+            sh_basis(A.deg, ux, uy, uz, b);
+            float r, g, bl;
+            shc_raw<K>(nb, b, c, r, g, bl);              // the forward's bits, hence the forward's clamp decision for this view
+            const float m0 = r < 0.f ? 0.f : g0, m1 = g < 0.f ? 0.f : g1, m2 = bl < 0.f ? 0.f : g2;
+#pragma unroll
+            for (int t = 0; t < K; ++t)
+                if (t < nb) { acc[3 * t] += b[t] * m0; acc[3 * t + 1] += b[t] * m1; acc[3 * t + 2] += b[t] * m2; }
+            if (need_dir && (m0 != 0.f || m1 != 0.f || m2 != 0.f)) {
+                float bx[16], by[16], bz[16];
+                sh_basis_grad(A.deg, ux, uy, uz, bx, by, bz);
+                float dux = 0.f, duy = 0.f, duz = 0.f;
+#pragma unroll
+                for (int t = 1; t < K; ++t)
+                    if (t < nb) {
+                        const float s = c[3 * t] * m0 + c[3 * t + 1] * m1 + c[3 * t + 2] * m2;
+                        dux += bx[t] * s; duy += by[t] * s; duz += bz[t] * s;
+                    }
+                const float dot = ux * dux + uy * duy + uz * duz;
+                nx = (dux - ux * dot) / dl; ny = (duy - uy * dot) / dl; nz = (duz - uz * dot) / dl;
+                gx += nx; gy += ny; gz += nz;
+            }
+        }
+        if (slab) {                                      // (a kernel argument inside a uniform loop: every lane is here)
+            const float r0 = shc_wave_total(-nx), r1 = shc_wave_total(-ny), r2 = shc_wave_total(-nz);
+            const int wave = threadIdx.x >> 6;
+            if ((threadIdx.x & 63) == 63) { wsum[v][wave][0] = r0; wsum[v][wave][1] = r1; wsum[v][wave][2] = r2; wsum[v][wave][3] = 0.f; }
+        }
+    }
+    if (g_xyz && on) { g_xyz[3 * ic] = gx; g_xyz[3 * ic + 1] = gy; g_xyz[3 * ic + 2] = gz; }
+
+    if (g_shs || g_shs_rest) {                           // the row's own thread was the only reader of its cotangents
+#pragma unroll
+        for (int k = 0; k < 3 * K; ++k) mine[k] = acc[k];
+    }
+    __syncthreads();
+    if constexpr (SPLIT) {
+        if (g_shs) shc_store_sum_span<3u, 0u>(sacc, g_shs, A.P);
+        if (g_shs_rest) shc_store_sum_span<3u * (K - 1), 3u>(sacc, g_shs_rest, A.P);
+    } else if (g_shs) {
+        shc_store_sum_span<3u * K, 0u>(sacc, g_shs, A.P);
+    }
+    if (slab && threadIdx.x < 4 * A.V) {                 // one slab row per (view, workgroup), the single-view kernel's sum of the waves
+        const int v = threadIdx.x >> 2, t = threadIdx.x & 3;
+        slab[((size_t)v * gridDim.x + blockIdx.x) * 4 + t] = (wsum[v][0][t] + wsum[v][1][t]) + (wsum[v][2][t] + wsum[v][3][t]);
+    }
+}
+
+// grid (3, V): view v's slab rows -> its dL/dcampos; nblocks == 0 writes zeros (degree 0, P == 0: no direction gradient)
+__global__ void __launch_bounds__(256)
+sh_campos_views_reduce_kernel(const float* __restrict__ slab, const int nblocks, const ShcViewsOut O)
+{
+    float* out = O.p[blockIdx.y];
+    if (!out) return;
+    shc_campos_reduce(slab + (size_t)blockIdx.y * nblocks * 4, nblocks, blockIdx.x, out);
 }
 
 #define SHC_DISPATCH(CALL)                                                                  \
@@ -256,5 +439,43 @@ hipError_t launch_sh_colors_bwd(const BagsShColors& a, const float* g_rgb, float
         if (rows) hipLaunchKernelGGL(sh_campos_reduce_kernel, dim3(3), dim3(256), 0, st, rows, nb, g_campos);
         else { const hipError_t e = hipMemsetAsync(g_campos, 0, 3 * sizeof(float), st); if (e != hipSuccess) return e; }   // degree 0: no direction
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_sh_colors_views_fwd(const BagsShColorsViews& a, float* const* rgb, hipStream_t st)
+{
+    if (a.P <= 0) return hipSuccess;
+    ShcViewsIn A{a.P, a.sh_degree, a.V, a.shs, a.shs_rest, a.xyz, {}};
+    ShcViewsOut O{};
+    for (int v = 0; v < a.V; ++v) { A.campos[v] = a.campos[v]; O.p[v] = rgb[v]; }
+    const int K = a.K; const bool split = a.shs_rest != nullptr;
+    const dim3 grid((unsigned)cdiv(a.P, 256));
+#define SHC_FWD(K_, S_) hipLaunchKernelGGL((sh_colors_views_fwd_kernel<K_, S_>), grid, dim3(256), 0, st, A, O);
+    SHC_DISPATCH(SHC_FWD)
+#undef SHC_FWD
+    return hipGetLastError();
+}
+
+hipError_t launch_sh_colors_views_bwd(const BagsShColorsViews& a, const float* const* g_rgb, float* slab, float* g_shs, float* g_shs_rest,
+                                      float* g_xyz, float* const* g_campos, hipStream_t st)
+{
+    ShcViewsIn A{a.P, a.sh_degree, a.V, a.shs, a.shs_rest, a.xyz, {}};
+    ShcViewsCot G{};
+    ShcViewsOut C{};
+    bool any_campos = false;
+    for (int v = 0; v < a.V; ++v) {
+        A.campos[v] = a.campos[v]; G.p[v] = g_rgb ? g_rgb[v] : nullptr; C.p[v] = g_campos ? g_campos[v] : nullptr;
+        any_campos = any_campos || C.p[v] != nullptr;
+    }
+    const int K = a.K; const bool split = a.shs_rest != nullptr;
+    const int need_dir = (a.P > 0 && a.sh_degree > 0 && (g_xyz || any_campos)) ? 1 : 0;
+    float* const rows = (need_dir && any_campos) ? slab : nullptr;
+    const int nb = cdiv(a.P > 0 ? a.P : 1, 256);
+    if (a.P > 0 && (g_shs || g_shs_rest || g_xyz || rows)) {
+#define SHC_BWD(K_, S_) hipLaunchKernelGGL((sh_colors_views_bwd_kernel<K_, S_>), dim3(nb), dim3(256), 0, st, A, G, g_shs, g_shs_rest, g_xyz, rows, need_dir);
+        SHC_DISPATCH(SHC_BWD)
+#undef SHC_BWD
+    }
+    if (any_campos) hipLaunchKernelGGL(sh_campos_views_reduce_kernel, dim3(3, a.V), dim3(256), 0, st, rows, rows ? nb : 0, C);
     return hipGetLastError();
 }

@@ -381,6 +381,29 @@ int bags_sh_colors_forward(const BagsShColors* a, float* rgb, void* stream);
 int bags_sh_colors_backward(const BagsShColors* a, const float* grad_rgb, void* workspace, size_t workspace_bytes, float* grad_shs,
                             float* grad_shs_rest, float* grad_xyz, float* grad_campos, void* stream);
 
+/* The same colours for the V views of one step over the same Gaussians (1 <= V <= BAGS_MAX_SH_VIEWS; more views: one call per
+ * chunk), one launch each way: the coefficient rows are read once in the forward and once in the backward, and the gradient rows
+ * are summed over the views on the chip and written once.  campos[v]: the v-th view's camera centre, 3 floats in device memory.
+ * Forward: rgb[v] (P,3), v < V, all given; view v's colours are the bits bags_sh_colors_forward gives for campos[v].
+ * Backward: grad_rgb has V entries, any of which may be NULL (no loss depends on that view); a view contributes to a Gaussian
+ * when its cotangent triple there is not all zero.  grad_shs / grad_shs_rest / grad_xyz receive the fp32 sum over the
+ * contributing views in view order, ((g_0 + g_1) + g_2) ..., of what bags_sh_colors_backward gives per view, bit for bit; a
+ * Gaussian without a contributing view gets zeros and costs 12 V bytes of reads.  grad_campos: NULL, or V entries, any of which
+ * may be NULL; entry v receives view v's dL/dcampos (zeros for a view without a cotangent).  The workspace
+ * (bags_sh_colors_views_workspace_size bytes) is only touched when some grad_campos entry is given.  Alignment rules as above.
+ * No atomics: the gradients are bitwise reproducible. */
+typedef struct BagsShColorsViews {
+    int32_t P, K, sh_degree, V;
+    const float* shs;                /* (P,K,3), or (P,1,3) when shs_rest is given */
+    const float* shs_rest;           /* (P,K-1,3) or NULL */
+    const float* xyz;                /* (P,3) */
+    const float* campos[BAGS_MAX_SH_VIEWS];   /* (3) each, the first V given */
+} BagsShColorsViews;
+size_t bags_sh_colors_views_workspace_size(int32_t P, int32_t V);
+int bags_sh_colors_views_forward(const BagsShColorsViews* a, float* const rgb[], void* stream);
+int bags_sh_colors_views_backward(const BagsShColorsViews* a, const float* const grad_rgb[], void* workspace, size_t workspace_bytes,
+                                  float* grad_shs, float* grad_shs_rest, float* grad_xyz, float* const grad_campos[], void* stream);
+
 /* One optimizer step of the Gaussian parameters: torch.optim.Adam (amsgrad = False, weight_decay = 0, maximize = False) over up to
  * BAGS_ADAM_MAX_GROUPS parameter groups of one Gaussian count P in ONE launch (csrc/adam.hip).  The reference builds
  * torch.optim.Adam(l, lr=0.0, eps=1e-15) over xyz, f_dc, f_rest, opacity, scaling, rotation (scene/gaussian_model.py:192-210)
