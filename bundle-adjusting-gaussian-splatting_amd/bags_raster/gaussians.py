@@ -379,6 +379,19 @@ def fused_activations(features_dc, features_rest, opacity, scaling, rotation):
     return _FusedActivations.apply(features_dc, features_rest, opacity, scaling, rotation)
 
 
+def _sh_saved(ctx):
+    """The backward half both SH colour operators share: ``ctx``'s saved inputs as ``(shs, rest, xyz, camposes)``, ``K``, and the
+    gradients of the first three, allocated where autograd needs them (None elsewhere)."""
+    ts = list(ctx.saved_tensors)
+    if not ctx.split:
+        ts.insert(1, None)
+    shs, rest, xyz, camposes = ts[0], ts[1], ts[2], ts[3:]
+    K = shs.shape[1] + (0 if rest is None else rest.shape[1])
+    need = ctx.needs_input_grad
+    out = [torch.empty_like(t) if (t is not None and need[k]) else None for k, t in ((1, shs), (2, rest), (3, xyz))]
+    return shs, rest, xyz, camposes, K, out
+
+
 class _ShColors(torch.autograd.Function):
     """``shs_rest`` None: ``shs`` is the packed (P,K,3) tensor; otherwise ``shs`` (P,1,3) and ``shs_rest`` (P,K-1,3)."""
 
@@ -398,40 +411,35 @@ class _ShColors(torch.autograd.Function):
     def backward(ctx, g_rgb):
         if g_rgb is None:
             return None, None, None, None, None
-        ts = list(ctx.saved_tensors)
-        if not ctx.split:
-            ts.insert(1, None)
-        shs, rest, xyz, campos = ts
+        shs, rest, xyz, (campos,), K, out = _sh_saved(ctx)
         P = xyz.shape[0]
-        K = shs.shape[1] + (0 if rest is None else rest.shape[1])
-        need = ctx.needs_input_grad
         g_rgb = L.as_f32c(g_rgb)
-        out = [torch.empty_like(t) if (t is not None and need[k]) else None for k, t in ((1, shs), (2, rest), (3, xyz), (4, campos))]
+        out.append(torch.empty_like(campos) if ctx.needs_input_grad[4] else None)
         args = L.BagsShColors(P, K, ctx.deg, 0, L.ptr(shs), L.ptr(rest), L.ptr(xyz), L.ptr(campos))
         ws = L.workspace(L.load().bags_sh_colors_workspace_size(P) if out[3] is not None else 0, xyz.device)      # (only dL/dcampos needs one)
         L.call("bags_sh_colors_backward", xyz.device, args, g_rgb.data_ptr(), ws.data_ptr(), ws.numel(), *[L.ptr(o) for o in out])
         return (None,) + tuple(out)
 
 
-def sh_colors(deg: int, shs: torch.Tensor, xyz: torch.Tensor, campos: torch.Tensor, shs_rest: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """``clamp_min(eval_sh(deg, shs, normalize(xyz - campos)) + 0.5, 0)`` -> ``(P,3)``: the Python colour path of ``render()``
-    (gaussian_renderer/__init__.py:90-95) in one HIP launch each way, gradients to the coefficients, ``xyz`` and ``campos``.
-
-    ``shs`` is the ``(P,K,3)`` feature tensor, or, with ``shs_rest (P,K-1,3)``, the ``(P,1,3)`` DC part: the two stored parameters
-    go in as they are, without ``get_features``' concatenation.  K is 1, 4, 9 or 16 and at least ``(deg+1)^2``; the gradient of the
-    stored rows beyond the active degree is exactly zero.  float32 tensors on a GPU; there is no CPU fallback (use ``eval_sh``)."""
-    what = "sh_colors"
+def _sh_degree(what: str, deg) -> int:
     deg = int(deg)
     if not 0 <= deg <= 3:
         raise ValueError(f"{what}: SH degree must be in 0..3, got {deg}")
-    named = [("shs", shs), ("xyz", xyz), ("campos", campos)] + ([("shs_rest", shs_rest)] if shs_rest is not None else [])
+    return deg
+
+
+def _sh_operands(what: str, deg: int, shs, xyz, shs_rest, cams) -> int:
+    """What ``sh_colors`` and ``sh_colors_views`` ask of their operands, in the order the errors are raised; ``cams``: the camera
+    centres as ``(name, tensor)`` pairs.  Returns K, the number of stored coefficients."""
+    named = [("shs", shs), ("xyz", xyz)] + cams + ([("shs_rest", shs_rest)] if shs_rest is not None else [])
     for name, t in named:
         L.require(what, name, t, f32=True)
     if xyz.dim() != 2 or xyz.shape[1] != 3:
         raise RuntimeError(f"{what}: xyz must be (P,3), got {tuple(xyz.shape)}")
     P = xyz.shape[0]
-    if tuple(campos.shape) != (3,):
-        raise RuntimeError(f"{what}: campos must be (3,), got {tuple(campos.shape)}")
+    for name, c in cams:
+        if tuple(c.shape) != (3,):
+            raise RuntimeError(f"{what}: {name} must be (3,), got {tuple(c.shape)}")
     if shs_rest is None:
         if shs.dim() != 3 or shs.shape[0] != P or shs.shape[2] != 3:
             raise RuntimeError(f"{what}: shs must be ({P},K,3) for xyz {tuple(xyz.shape)}, got {tuple(shs.shape)}")
@@ -450,6 +458,19 @@ def sh_colors(deg: int, shs: torch.Tensor, xyz: torch.Tensor, campos: torch.Tens
                            + (" + shs_rest hold " if shs_rest is not None else " holds ") + f"{K} (shs {tuple(shs.shape)})")
     for name, t in named:
         L.require(what, name, t, gpu=True, on=xyz, host=" (bags_raster.eval_sh is the host-side evaluation)")
+    return K
+
+
+def sh_colors(deg: int, shs: torch.Tensor, xyz: torch.Tensor, campos: torch.Tensor, shs_rest: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``clamp_min(eval_sh(deg, shs, normalize(xyz - campos)) + 0.5, 0)`` -> ``(P,3)``: the Python colour path of ``render()``
+    (gaussian_renderer/__init__.py:90-95) in one HIP launch each way, gradients to the coefficients, ``xyz`` and ``campos``.
+
+    ``shs`` is the ``(P,K,3)`` feature tensor, or, with ``shs_rest (P,K-1,3)``, the ``(P,1,3)`` DC part: the two stored parameters
+    go in as they are, without ``get_features``' concatenation.  K is 1, 4, 9 or 16 and at least ``(deg+1)^2``; the gradient of the
+    stored rows beyond the active degree is exactly zero.  float32 tensors on a GPU; there is no CPU fallback (use ``eval_sh``)."""
+    what = "sh_colors"
+    deg = _sh_degree(what, deg)
+    _sh_operands(what, deg, shs, xyz, shs_rest, [("campos", campos)])
     return _ShColors.apply(deg, shs, shs_rest, xyz, campos)
 
 
@@ -472,17 +493,13 @@ class _ShColorsViews(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *g_rgb):
-        ts = list(ctx.saved_tensors)
-        if not ctx.split:
-            ts.insert(1, None)
-        shs, rest, xyz, camposes = ts[0], ts[1], ts[2], ts[3:]
-        V, P = len(camposes), xyz.shape[0]
+        V = len(g_rgb)
         if all(g is None for g in g_rgb):
             return (None,) * (4 + V)
-        K = shs.shape[1] + (0 if rest is None else rest.shape[1])
+        shs, rest, xyz, camposes, K, out = _sh_saved(ctx)
+        P = xyz.shape[0]
         need = ctx.needs_input_grad
         g_rgb = [L.as_f32c(g) for g in g_rgb]
-        out = [torch.empty_like(t) if (t is not None and need[k]) else None for k, t in ((1, shs), (2, rest), (3, xyz))]
         g_campos = [torch.empty_like(c) if need[4 + v] else None for v, c in enumerate(camposes)]
         args = L.BagsShColorsViews(P, K, ctx.deg, V, L.ptr(shs), L.ptr(rest), L.ptr(xyz), L.ptr_table(camposes + [None] * (L.MAX_SH_VIEWS - V)))
         wanted = any(g is not None for g in g_campos)                  # (only dL/dcampos needs a workspace)
@@ -501,40 +518,11 @@ def sh_colors_views(deg: int, shs: torch.Tensor, xyz: torch.Tensor, camposes, sh
     of the fp32 fold of the per-view gradients, without autograd's ``grad += g`` per view.  Each camera centre gets its own
     gradient.  A view whose colours no loss uses costs nothing in the backward.  Layouts and limits as ``sh_colors``."""
     what = "sh_colors_views"
-    deg = int(deg)
-    if not 0 <= deg <= 3:
-        raise ValueError(f"{what}: SH degree must be in 0..3, got {deg}")
+    deg = _sh_degree(what, deg)
     if isinstance(camposes, torch.Tensor) or not isinstance(camposes, (list, tuple)):
         raise TypeError(f"{what}: camposes must be a list or tuple of (3,) tensors, got {type(camposes).__name__}")
     V = len(camposes)
     if not 1 <= V <= L.MAX_SH_VIEWS:
         raise ValueError(f"{what}: the number of views must be in 1..{L.MAX_SH_VIEWS}, got {V} (more views: one call per chunk)")
-    named = ([("shs", shs), ("xyz", xyz)] + [(f"camposes[{v}]", c) for v, c in enumerate(camposes)]
-             + ([("shs_rest", shs_rest)] if shs_rest is not None else []))
-    for name, t in named:
-        L.require(what, name, t, f32=True)
-    if xyz.dim() != 2 or xyz.shape[1] != 3:
-        raise RuntimeError(f"{what}: xyz must be (P,3), got {tuple(xyz.shape)}")
-    P = xyz.shape[0]
-    for v, c in enumerate(camposes):
-        if tuple(c.shape) != (3,):
-            raise RuntimeError(f"{what}: camposes[{v}] must be (3,), got {tuple(c.shape)}")
-    if shs_rest is None:
-        if shs.dim() != 3 or shs.shape[0] != P or shs.shape[2] != 3:
-            raise RuntimeError(f"{what}: shs must be ({P},K,3) for xyz {tuple(xyz.shape)}, got {tuple(shs.shape)}")
-        K = shs.shape[1]
-    else:
-        if tuple(shs.shape) != (P, 1, 3):
-            raise RuntimeError(f"{what}: with shs_rest, shs must be the ({P},1,3) DC part for xyz {tuple(xyz.shape)}, got {tuple(shs.shape)}")
-        if shs_rest.dim() != 3 or shs_rest.shape[0] != P or shs_rest.shape[2] != 3 or shs_rest.shape[1] < 1:
-            raise RuntimeError(f"{what}: shs_rest must be ({P},K-1,3) with K >= 2 for shs {tuple(shs.shape)}, got {tuple(shs_rest.shape)}")
-        K = 1 + shs_rest.shape[1]
-    if K not in (1, 4, 9, 16):
-        raise RuntimeError(f"{what}: K = {K} stored coefficients (shs {tuple(shs.shape)}"
-                           + (f", shs_rest {tuple(shs_rest.shape)}" if shs_rest is not None else "") + "): K must be 1, 4, 9 or 16")
-    if K < (deg + 1) ** 2:
-        raise RuntimeError(f"{what}: degree {deg} needs {(deg + 1) ** 2} coefficients, shs"
-                           + (" + shs_rest hold " if shs_rest is not None else " holds ") + f"{K} (shs {tuple(shs.shape)})")
-    for name, t in named:
-        L.require(what, name, t, gpu=True, on=xyz, host=" (bags_raster.eval_sh is the host-side evaluation)")
+    _sh_operands(what, deg, shs, xyz, shs_rest, [(f"camposes[{v}]", c) for v, c in enumerate(camposes)])
     return _ShColorsViews.apply(deg, shs, shs_rest, xyz, *camposes)

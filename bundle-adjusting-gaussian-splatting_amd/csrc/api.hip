@@ -195,18 +195,11 @@ static size_t carve_backward(void* base, int P, long long I, BwdWorkView* v)
     return c.used();
 }
 
-static size_t carve_sh_colors(void* base, int P, float** slab)
+// one row of campos sums per (view, workgroup), view-major (sh_colors.hip); the single-view operator is V = 1
+static size_t carve_sh_colors(void* base, int P, int V, float** slab)
 {
     Carver c(base);
-    float* s = c.take<float>((size_t)cdiv(P > 0 ? P : 1, 256) * SH_SLAB);      // one row of campos sums per workgroup (sh_colors.hip)
-    if (slab) *slab = s;
-    return c.used();
-}
-
-static size_t carve_sh_colors_views(void* base, int P, int V, float** slab)
-{
-    Carver c(base);
-    float* s = c.take<float>((size_t)(V > 0 ? V : 1) * cdiv(P > 0 ? P : 1, 256) * SH_SLAB);   // view-major: one row per (view, workgroup)
+    float* s = c.take<float>((size_t)(V > 0 ? V : 1) * cdiv(P > 0 ? P : 1, 256) * SH_SLAB);
     if (slab) *slab = s;
     return c.used();
 }
@@ -755,7 +748,24 @@ static int check_sh_colors(const BagsShColors* a)
     return BAGS_OK;
 }
 
-size_t bags_sh_colors_workspace_size(int32_t P) { return carve_sh_colors(nullptr, P, nullptr) + BASE_SLACK; }
+// The gradient arguments of a backward entry point, `op` its name, `null_rgb` what it says of a missing grad_rgb.  want_campos:
+// some dL/dcampos is asked for, so the workspace must hold the slab of V views, which *slab then is.
+static int check_sh_grads(const char* op, const char* null_rgb, int P, bool split, int V, const void* grad_rgb, const float* grad_shs,
+                          const float* grad_shs_rest, bool want_campos, void* workspace, size_t workspace_bytes, float** slab)
+{
+    if (P > 0 && !grad_rgb) return fail(BAGS_ERR_ARG, "%s_backward: %s", op, null_rgb);
+    if (grad_shs_rest && !split) return fail(BAGS_ERR_ARG, "%s_backward: grad_shs_rest without shs_rest", op);
+    if ((reinterpret_cast<size_t>(grad_shs) | reinterpret_cast<size_t>(grad_shs_rest)) & 15)
+        return fail(BAGS_ERR_ARG, "%s_backward: grad_shs / grad_shs_rest must be 16-byte aligned", op);
+    if (want_campos) {
+        const size_t need = carve_sh_colors(nullptr, P, V, nullptr) + BASE_SLACK;
+        if (!workspace || workspace_bytes < need) return fail(BAGS_ERR_SIZE, "%s_backward: grad_campos needs a workspace of %zu bytes", op, need);
+        carve_sh_colors(workspace, P, V, slab);
+    }
+    return BAGS_OK;
+}
+
+size_t bags_sh_colors_workspace_size(int32_t P) { return carve_sh_colors(nullptr, P, 1, nullptr) + BASE_SLACK; }
 
 int bags_sh_colors_forward(const BagsShColors* a, float* rgb, void* stream)
 {
@@ -773,16 +783,9 @@ int bags_sh_colors_backward(const BagsShColors* a, const float* grad_rgb, void* 
     int rc = check_sh_colors(a);
     if (rc) return rc;
     if (!grad_shs && !grad_shs_rest && !grad_xyz && !grad_campos) return BAGS_OK;
-    if (a->P > 0 && !grad_rgb) return fail(BAGS_ERR_ARG, "sh_colors_backward: null grad_rgb");
-    if (grad_shs_rest && !a->shs_rest) return fail(BAGS_ERR_ARG, "sh_colors_backward: grad_shs_rest without shs_rest");
-    if ((reinterpret_cast<size_t>(grad_shs) | reinterpret_cast<size_t>(grad_shs_rest)) & 15)
-        return fail(BAGS_ERR_ARG, "sh_colors_backward: grad_shs / grad_shs_rest must be 16-byte aligned");
     float* slab = nullptr;
-    if (grad_campos) {
-        if (!workspace || workspace_bytes < bags_sh_colors_workspace_size(a->P))
-            return fail(BAGS_ERR_SIZE, "sh_colors_backward: grad_campos needs a workspace of %zu bytes", bags_sh_colors_workspace_size(a->P));
-        carve_sh_colors(workspace, a->P, &slab);
-    }
+    rc = check_sh_grads("sh_colors", "null grad_rgb", a->P, a->shs_rest != nullptr, 1, grad_rgb, grad_shs, grad_shs_rest, grad_campos != nullptr, workspace, workspace_bytes, &slab);
+    if (rc) return rc;
     HIP_TRY(launch_sh_colors_bwd(*a, grad_rgb, slab, grad_shs, grad_shs_rest, grad_xyz, grad_campos, (hipStream_t)stream));
     return BAGS_OK;
 }
@@ -801,7 +804,7 @@ static int check_sh_colors_views(const BagsShColorsViews* a)
     return BAGS_OK;
 }
 
-size_t bags_sh_colors_views_workspace_size(int32_t P, int32_t V) { return carve_sh_colors_views(nullptr, P, V, nullptr) + BASE_SLACK; }
+size_t bags_sh_colors_views_workspace_size(int32_t P, int32_t V) { return carve_sh_colors(nullptr, P, V, nullptr) + BASE_SLACK; }
 
 int bags_sh_colors_views_forward(const BagsShColorsViews* a, float* const rgb[], void* stream)
 {
@@ -823,17 +826,10 @@ int bags_sh_colors_views_backward(const BagsShColorsViews* a, const float* const
     bool any_campos = false;
     for (int v = 0; grad_campos && v < a->V; ++v) any_campos = any_campos || grad_campos[v] != nullptr;
     if (!grad_shs && !grad_shs_rest && !grad_xyz && !any_campos) return BAGS_OK;
-    if (a->P > 0 && !grad_rgb) return fail(BAGS_ERR_ARG, "sh_colors_views_backward: null grad_rgb table (its entries may be NULL, the table not)");
-    if (grad_shs_rest && !a->shs_rest) return fail(BAGS_ERR_ARG, "sh_colors_views_backward: grad_shs_rest without shs_rest");
-    if ((reinterpret_cast<size_t>(grad_shs) | reinterpret_cast<size_t>(grad_shs_rest)) & 15)
-        return fail(BAGS_ERR_ARG, "sh_colors_views_backward: grad_shs / grad_shs_rest must be 16-byte aligned");
     float* slab = nullptr;
-    if (any_campos) {
-        const size_t need = bags_sh_colors_views_workspace_size(a->P, a->V);
-        if (!workspace || workspace_bytes < need)
-            return fail(BAGS_ERR_SIZE, "sh_colors_views_backward: grad_campos needs a workspace of %zu bytes", need);
-        carve_sh_colors_views(workspace, a->P, a->V, &slab);
-    }
+    rc = check_sh_grads("sh_colors_views", "null grad_rgb table (its entries may be NULL, the table not)", a->P, a->shs_rest != nullptr, a->V, grad_rgb,
+                        grad_shs, grad_shs_rest, any_campos, workspace, workspace_bytes, &slab);
+    if (rc) return rc;
     HIP_TRY(launch_sh_colors_views_bwd(*a, grad_rgb, slab, grad_shs, grad_shs_rest, grad_xyz, any_campos ? grad_campos : nullptr, (hipStream_t)stream));
     return BAGS_OK;
 }

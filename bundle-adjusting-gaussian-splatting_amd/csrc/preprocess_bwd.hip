@@ -19,15 +19,6 @@ struct CamConstB {
     float sf[3];
 };
 
-// sum over the 64 lanes on DPP (row_shr 1/2/4/8 inside the 16-lane rows, row_bcast:15 / row_bcast:31 across them: six
-// v_add_f32_dpp); the total is valid in lane 63.  Every lane must be active.
-__device__ __forceinline__ float wave_total_f(float x)
-{
-#define DPP_ADD(ctrl, rmask) x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), ctrl, rmask, 0xf, false))
-    DPP_ADD(0x111, 0xf); DPP_ADD(0x112, 0xf); DPP_ADD(0x114, 0xf); DPP_ADD(0x118, 0xf); DPP_ADD(0x142, 0xa); DPP_ADD(0x143, 0xc);
-#undef DPP_ADD
-    return x;
-}
 __device__ __forceinline__ float wave_sum(float x)
 {
 #pragma unroll

@@ -24,6 +24,12 @@
 // view order, each product and each add rounded once -- the bits of the fp32 fold ((g_0 + g_1) + g_2) ... of the single-view
 // kernel's gradients -- and writes the row once.  The camera centres, the outputs and the cotangents travel as pointer tables by
 // value in the kernel arguments (adam.hip's group table): nothing is uploaded.
+//
+// The four colour kernels are built from the same statements, spelled once where that leaves the generated code as it is:
+// shc_load_row (the coefficient row), shc_eval (a view's direction, basis and raw colour) and shc_store_span (the SH gradient rows
+// as whole lines).  The direction gradient is spelled in each backward kernel: as a function of its own it compiles to other code
+// (profiles/sh_colors/NOTES.md), so a change to it is made in both.  They share statements, not kernels: the views backward stages
+// 51200 bytes of LDS and needs twice the registers of the single-view one, which is render()'s default path.
 #include "bags_common.h"
 #include "sh_basis.h"
 
@@ -31,10 +37,10 @@ struct ShcIn { int P, deg; const float *shs, *shs_rest, *xyz, *campos; };
 
 // the first 3 * nb floats of a Gaussian's coefficients into c[]; K == 16 loads the whole 192-byte row with wide loads
 template <int K, bool SPLIT>
-__device__ __forceinline__ void shc_load_row(const ShcIn& A, const size_t i, const int nb, float* __restrict__ c)
+__device__ __forceinline__ void shc_load_row(const float* shs, const float* shs_rest, const size_t i, const int nb, float* __restrict__ c)
 {
-    const float* __restrict__ dcp = SPLIT ? A.shs + 3 * i : A.shs + i * (size_t)(K * 3);
-    const float* __restrict__ rsp = SPLIT ? A.shs_rest + i * (size_t)((K - 1) * 3) : dcp + 3;
+    const float* __restrict__ dcp = SPLIT ? shs + 3 * i : shs + i * (size_t)(K * 3);
+    const float* __restrict__ rsp = SPLIT ? shs_rest + i * (size_t)((K - 1) * 3) : dcp + 3;
     if (K == 16) {
         if (SPLIT) {                      // 12 + 180 bytes, the second row only 4-byte aligned (dwordx4 loads at any dword)
             struct __attribute__((packed, aligned(4))) UF4 { float x, y, z, w; };
@@ -60,10 +66,20 @@ __device__ __forceinline__ void shc_load_row(const ShcIn& A, const size_t i, con
     }
 }
 
-// raw colour: the ONE spelling of the sum, shared by the forward and the backward's clamp mask
+// One view of one Gaussian: the distance dl and the direction u from the camera centre cp, the basis b[16] and the raw colour.
+// The ONE spelling of the direction and of the sum, shared by both forwards and by the backwards' clamp masks.  (c and b carry no
+// __restrict__, and sh_basis gets the direction from locals, not through the references: either changes what the compiler makes
+// of the kernels, profiles/sh_colors/NOTES.md.)
 template <int K>
-__device__ __forceinline__ void shc_raw(const int nb, const float* __restrict__ b, const float* __restrict__ c, float& r, float& g, float& bl)
+__device__ __forceinline__ void shc_eval(const float x, const float y, const float z, const float* cp, const int deg, const int nb,
+                                         const float* c, float& dl, float& ux, float& uy, float& uz, float* b,
+                                         float& r, float& g, float& bl)
 {
+    const float dx = x - cp[0], dy = y - cp[1], dz = z - cp[2];
+    dl = sqrtf(dx * dx + dy * dy + dz * dz);
+    const float vx = dx / dl, vy = dy / dl, vz = dz / dl;
+    ux = vx; uy = vy; uz = vz;
+    sh_basis(deg, vx, vy, vz, b);
     r = 0.f; g = 0.f; bl = 0.f;
 #pragma unroll
     for (int t = 0; t < K; ++t)
@@ -80,30 +96,22 @@ sh_colors_fwd_kernel(const ShcIn A, float* __restrict__ rgb)
     const int nb = (A.deg + 1) * (A.deg + 1);
     const float x = A.xyz[3 * (size_t)i], y = A.xyz[3 * (size_t)i + 1], z = A.xyz[3 * (size_t)i + 2];
     float c[48];
-    shc_load_row<K, SPLIT>(A, (size_t)i, nb, c);
-    const float dx = x - A.campos[0], dy = y - A.campos[1], dz = z - A.campos[2];
-    const float dl = sqrtf(dx * dx + dy * dy + dz * dz);
-    float b[16];
-    sh_basis(A.deg, dx / dl, dy / dl, dz / dl, b);
-    float r, g, bl;
-    shc_raw<K>(nb, b, c, r, g, bl);
+    shc_load_row<K, SPLIT>(A.shs, A.shs_rest, (size_t)i, nb, c);
+    float dl, ux, uy, uz, b[16], r, g, bl;
+    shc_eval<K>(x, y, z, A.campos, A.deg, nb, c, dl, ux, uy, uz, b, r, g, bl);
     rgb[3 * (size_t)i] = r < 0.f ? 0.f : r; rgb[3 * (size_t)i + 1] = g < 0.f ? 0.f : g; rgb[3 * (size_t)i + 2] = bl < 0.f ? 0.f : bl;
 }
 
-// sum over the 64 lanes on DPP, valid in lane 63, every lane active (the reduction preprocess_bwd.hip uses for the pose sums)
-__device__ __forceinline__ float shc_wave_total(float x)
-{
-#define DPP_ADD(ctrl, rmask) x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), ctrl, rmask, 0xf, false))
-    DPP_ADD(0x111, 0xf); DPP_ADD(0x112, 0xf); DPP_ADD(0x114, 0xf); DPP_ADD(0x118, 0xf); DPP_ADD(0x142, 0xa); DPP_ADD(0x143, 0xc);
-#undef DPP_ADD
-    return x;
-}
+#define SHC_ROW 49       // floats per Gaussian in the views backward's LDS stage: 48 + 1, so that the 64 lanes' own rows fall on distinct banks
 
-// The workgroup's 256 gradient rows of one tensor, R floats each starting at coefficient T0, as whole lines: thread t owns float4
-// number t, t + 256, ... of the workgroup's span (256 R floats: a multiple of 16 bytes from a 16-byte aligned base).
-// srow[g] = basis[16] (zero beyond the active degree and for a Gaussian that writes zeros), masked cotangent[3], pad.
-template <u32 R, u32 T0>
-__device__ __forceinline__ void shc_store_span(const float (*srow)[20], float* __restrict__ out, const int P)
+// The workgroup's 256 gradient rows of one tensor, R floats each, as whole lines: thread t owns float4 number t, t + 256, ... of the
+// workgroup's span (256 R floats: a multiple of 16 bytes from a 16-byte aligned base).  The floats come from the kernel's LDS stage,
+// W floats per Gaussian, the tensor's row starting at coefficient T0:
+//   PRODUCT (single view, W = 20): stage[g] = basis[16] (zero beyond the active degree and for a Gaussian that writes zeros), masked
+//                                  cotangent[3], pad; a gradient is their product
+//   otherwise (views, W = SHC_ROW): stage[g] = the summed gradient row, packed
+template <u32 R, u32 T0, bool PRODUCT, u32 W>
+__device__ __forceinline__ void shc_store_span(const float (*stage)[W], float* __restrict__ out, const int P)
 {
     const size_t first_f = (size_t)blockIdx.x * 256u * R, total = (size_t)P * R;
 #pragma unroll
@@ -114,8 +122,13 @@ __device__ __forceinline__ void shc_store_span(const float (*srow)[20], float* _
             float o4[4];
 #pragma unroll
             for (u32 u = 0; u < 4; ++u) {
-                const u32 f = el * 4u + u, row = f / R, r = f - row * R, t = T0 + r / 3u, ch = r - 3u * (r / 3u);
-                o4[u] = srow[row][t] * srow[row][16u + ch];
+                if constexpr (PRODUCT) {
+                    const u32 f = el * 4u + u, row = f / R, r = f - row * R, t = T0 + r / 3u, ch = r - 3u * (r / 3u);
+                    o4[u] = stage[row][t] * stage[row][16u + ch];
+                } else {
+                    const u32 f = el * 4u + u, row = f / R, r = f - row * R;
+                    o4[u] = stage[row][3u * T0 + r];
+                }
             }
             if (g0 + 3 < total) *reinterpret_cast<float4*>(out + g0) = make_float4(o4[0], o4[1], o4[2], o4[3]);
             else {                                    // the tensor's last float4 may be partial (P R not a multiple of 4)
@@ -148,14 +161,9 @@ sh_colors_bwd_kernel(const ShcIn A, const float* __restrict__ g_rgb, float* __re
     if (any) {
         const float x = A.xyz[3 * ic], y = A.xyz[3 * ic + 1], z = A.xyz[3 * ic + 2];
         float c[48];
-        shc_load_row<K, SPLIT>(A, ic, nb, c);
-        const float dx = x - A.campos[0], dy = y - A.campos[1], dz = z - A.campos[2];
-        const float dl = sqrtf(dx * dx + dy * dy + dz * dz);
-        const float ux = dx / dl, uy = dy / dl, uz = dz / dl;
-        float b[16];
-        sh_basis(A.deg, ux, uy, uz, b);
-        float r, g, bl;
-        shc_raw<K>(nb, b, c, r, g, bl);                  // the forward's bits, hence the forward's clamp decision
+        shc_load_row<K, SPLIT>(A.shs, A.shs_rest, ic, nb, c);
+        float dl, ux, uy, uz, b[16], r, g, bl;
+        shc_eval<K>(x, y, z, A.campos, A.deg, nb, c, dl, ux, uy, uz, b, r, g, bl);   // the forward's bits, hence its clamp decision
         m0 = r < 0.f ? 0.f : g0; m1 = g < 0.f ? 0.f : g1; m2 = bl < 0.f ? 0.f : g2;
 #pragma unroll
         for (int t = 0; t < K; ++t) bs[t] = (t < nb) ? b[t] : 0.f;
@@ -184,15 +192,15 @@ sh_colors_bwd_kernel(const ShcIn A, const float* __restrict__ g_rgb, float* __re
         d4[4] = make_float4(m0, m1, m2, 0.f);
         __syncthreads();
         if constexpr (SPLIT) {
-            if (g_shs) shc_store_span<3u, 0u>(srow, g_shs, A.P);
-            if (g_shs_rest) shc_store_span<3u * (K - 1), 1u>(srow, g_shs_rest, A.P);
+            if (g_shs) shc_store_span<3u, 0u, true>(srow, g_shs, A.P);
+            if (g_shs_rest) shc_store_span<3u * (K - 1), 1u, true>(srow, g_shs_rest, A.P);
         } else if (g_shs) {
-            shc_store_span<3u * K, 0u>(srow, g_shs, A.P);
+            shc_store_span<3u * K, 0u, true>(srow, g_shs, A.P);
         }
     }
 
     if (slab) {                                          // dL/dcampos = -sum dL/dxyz: wave, workgroup, one slab row
-        const float r0 = shc_wave_total(-gx), r1 = shc_wave_total(-gy), r2 = shc_wave_total(-gz);
+        const float r0 = wave_total_f(-gx), r1 = wave_total_f(-gy), r2 = wave_total_f(-gz);
         const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
         if (lane == 63) { wsum[wave][0] = r0; wsum[wave][1] = r1; wsum[wave][2] = r2; wsum[wave][3] = 0.f; }
         __syncthreads();
@@ -242,48 +250,14 @@ sh_colors_views_fwd_kernel(const ShcViewsIn A, const ShcViewsOut O)
     if (i >= A.P) return;
     const int nb = (A.deg + 1) * (A.deg + 1);
     const float x = A.xyz[3 * (size_t)i], y = A.xyz[3 * (size_t)i + 1], z = A.xyz[3 * (size_t)i + 2];
-    const ShcIn S{A.P, A.deg, A.shs, A.shs_rest, A.xyz, nullptr};
     float c[48];
-    shc_load_row<K, SPLIT>(S, (size_t)i, nb, c);
+    shc_load_row<K, SPLIT>(A.shs, A.shs_rest, (size_t)i, nb, c);
     for (int v = 0; v < A.V; ++v) {                      // per view: the single-view kernel's operations on campos_v
         const float* __restrict__ cp = A.campos[v];
-        const float dx = x - cp[0], dy = y - cp[1], dz = z - cp[2];
-        const float dl = sqrtf(dx * dx + dy * dy + dz * dz);
-        float b[16];
-        sh_basis(A.deg, dx / dl, dy / dl, dz / dl, b);
-        float r, g, bl;
-        shc_raw<K>(nb, b, c, r, g, bl);
+        float dl, ux, uy, uz, b[16], r, g, bl;
+        shc_eval<K>(x, y, z, cp, A.deg, nb, c, dl, ux, uy, uz, b, r, g, bl);
         float* __restrict__ rgb = O.p[v];
         rgb[3 * (size_t)i] = r < 0.f ? 0.f : r; rgb[3 * (size_t)i + 1] = g < 0.f ? 0.f : g; rgb[3 * (size_t)i + 2] = bl < 0.f ? 0.f : bl;
-    }
-}
-
-#define SHC_ROW 49       // floats per Gaussian in the backward's LDS stage: 48 + 1, so that the 64 lanes' own rows fall on distinct banks
-
-// The workgroup's 256 summed gradient rows of one tensor, R floats each starting at float F0 of the staged row, as whole lines
-// (shc_store_span's mapping: thread t owns float4 number t, t + 256, ... of the workgroup's span)
-template <u32 R, u32 F0>
-__device__ __forceinline__ void shc_store_sum_span(const float (*sacc)[SHC_ROW], float* __restrict__ out, const int P)
-{
-    const size_t first_f = (size_t)blockIdx.x * 256u * R, total = (size_t)P * R;
-#pragma unroll
-    for (u32 k = 0; k < (64u * R + 255u) / 256u; ++k) {
-        const u32 el = k * 256u + threadIdx.x;
-        const size_t g0 = first_f + (size_t)el * 4u;
-        if (el < 64u * R && g0 < total) {
-            float o4[4];
-#pragma unroll
-            for (u32 u = 0; u < 4; ++u) {
-                const u32 f = el * 4u + u, row = f / R, r = f - row * R;
-                o4[u] = sacc[row][F0 + r];
-            }
-            if (g0 + 3 < total) *reinterpret_cast<float4*>(out + g0) = make_float4(o4[0], o4[1], o4[2], o4[3]);
-            else {                                    // the tensor's last float4 may be partial (P R not a multiple of 4)
-                out[g0] = o4[0];
-                if (g0 + 1 < total) out[g0 + 1] = o4[1];
-                if (g0 + 2 < total) out[g0 + 2] = o4[2];
-            }
-        }
     }
 }
 
@@ -334,21 +308,15 @@ sh_colors_views_bwd_kernel(const ShcViewsIn A, const ShcViewsCot G, float* __res
     for (int k = 0; k < 48; ++k) c[k] = 0.f;
     if (live) {                                          // a Gaussian no view contributes to reads nothing else and writes zeros
         x = A.xyz[3 * ic]; y = A.xyz[3 * ic + 1]; z = A.xyz[3 * ic + 2];
-        const ShcIn S{A.P, A.deg, A.shs, A.shs_rest, A.xyz, nullptr};
-        shc_load_row<K, SPLIT>(S, ic, nb, c);
+        shc_load_row<K, SPLIT>(A.shs, A.shs_rest, ic, nb, c);
     }
     for (int v = 0; v < A.V; ++v) {
         float nx = 0.f, ny = 0.f, nz = 0.f;              // this view's dL/dd, for its dL/dcampos
         if ((live >> v) & 1u) {
             const float* __restrict__ cp = A.campos[v];
             const float g0 = mine[3 * v], g1 = mine[3 * v + 1], g2 = mine[3 * v + 2];
-            const float dx = x - cp[0], dy = y - cp[1], dz = z - cp[2];
-            const float dl = sqrtf(dx * dx + dy * dy + dz * dz);
-            const float ux = dx / dl, uy = dy / dl, uz = dz / dl;
-            float b[16];
-            sh_basis(A.deg, ux, uy, uz, b);
-            float r, g, bl;
-            shc_raw<K>(nb, b, c, r, g, bl);              // the forward's bits, hence the forward's clamp decision for this view
+            float dl, ux, uy, uz, b[16], r, g, bl;
+            shc_eval<K>(x, y, z, cp, A.deg, nb, c, dl, ux, uy, uz, b, r, g, bl);   // the forward's bits, hence its clamp decision for this view
             const float m0 = r < 0.f ? 0.f : g0, m1 = g < 0.f ? 0.f : g1, m2 = bl < 0.f ? 0.f : g2;
 #pragma unroll
             for (int t = 0; t < K; ++t)
@@ -369,7 +337,7 @@ sh_colors_views_bwd_kernel(const ShcViewsIn A, const ShcViewsCot G, float* __res
             }
         }
         if (slab) {                                      // (a kernel argument inside a uniform loop: every lane is here)
-            const float r0 = shc_wave_total(-nx), r1 = shc_wave_total(-ny), r2 = shc_wave_total(-nz);
+            const float r0 = wave_total_f(-nx), r1 = wave_total_f(-ny), r2 = wave_total_f(-nz);
             const int wave = threadIdx.x >> 6;
             if ((threadIdx.x & 63) == 63) { wsum[v][wave][0] = r0; wsum[v][wave][1] = r1; wsum[v][wave][2] = r2; wsum[v][wave][3] = 0.f; }
         }
@@ -382,10 +350,10 @@ sh_colors_views_bwd_kernel(const ShcViewsIn A, const ShcViewsCot G, float* __res
     }
     __syncthreads();
     if constexpr (SPLIT) {
-        if (g_shs) shc_store_sum_span<3u, 0u>(sacc, g_shs, A.P);
-        if (g_shs_rest) shc_store_sum_span<3u * (K - 1), 3u>(sacc, g_shs_rest, A.P);
+        if (g_shs) shc_store_span<3u, 0u, false>(sacc, g_shs, A.P);
+        if (g_shs_rest) shc_store_span<3u * (K - 1), 1u, false>(sacc, g_shs_rest, A.P);
     } else if (g_shs) {
-        shc_store_sum_span<3u * K, 0u>(sacc, g_shs, A.P);
+        shc_store_span<3u * K, 0u, false>(sacc, g_shs, A.P);
     }
     if (slab && threadIdx.x < 4 * A.V) {                 // one slab row per (view, workgroup), the single-view kernel's sum of the waves
         const int v = threadIdx.x >> 2, t = threadIdx.x & 3;
@@ -402,21 +370,35 @@ sh_campos_views_reduce_kernel(const float* __restrict__ slab, const int nblocks,
     shc_campos_reduce(slab + (size_t)blockIdx.y * nblocks * 4, nblocks, blockIdx.x, out);
 }
 
-#define SHC_DISPATCH(CALL)                                                                  \
-    if (split) {                                                                            \
-        if (K == 16) { CALL(16, true) } else if (K == 9) { CALL(9, true) } else { CALL(4, true) } \
+// ---------------------------------------------------------------------------------------------- launchers
+// CALL(K, SPLIT) for the instance that fits the operands `a`: the stored coefficients and the layout (shs_rest given = split)
+#define SHC_DISPATCH(a, CALL)                                                               \
+    if ((a).shs_rest) {                                                                     \
+        if ((a).K == 16) { CALL(16, true) } else if ((a).K == 9) { CALL(9, true) } else { CALL(4, true) } \
     } else {                                                                                \
-        if (K == 16) { CALL(16, false) } else if (K == 9) { CALL(9, false) } else if (K == 4) { CALL(4, false) } else { CALL(1, false) } \
+        if ((a).K == 16) { CALL(16, false) } else if ((a).K == 9) { CALL(9, false) } else if ((a).K == 4) { CALL(4, false) } else { CALL(1, false) } \
     }
+
+// What a backward enqueues, from what it was asked for: need_dir as the kernels take it; rows = the slab if the campos sums are to
+// be written, else null (degree 0, P <= 0: no direction gradient, dL/dcampos is zero); main = does the colour kernel run at all
+struct ShcBwdPlan { int nb, need_dir; float* rows; bool main; };
+static ShcBwdPlan shc_bwd_plan(const int P, const int deg, const bool want_sh, const bool want_xyz, const bool want_campos, float* slab)
+{
+    ShcBwdPlan p;                                       // (the P > 0 guards serve the views launcher: the single-view one has returned by then)
+    p.nb = cdiv(P > 0 ? P : 1, 256);
+    p.need_dir = (P > 0 && deg > 0 && (want_xyz || want_campos)) ? 1 : 0;
+    p.rows = (p.need_dir && want_campos) ? slab : nullptr;
+    p.main = P > 0 && (want_sh || want_xyz || p.rows);
+    return p;
+}
 
 hipError_t launch_sh_colors_fwd(const BagsShColors& a, float* rgb, hipStream_t st)
 {
     if (a.P <= 0) return hipSuccess;
     const ShcIn A{a.P, a.sh_degree, a.shs, a.shs_rest, a.xyz, a.campos};
-    const int K = a.K; const bool split = a.shs_rest != nullptr;
     const dim3 grid((unsigned)cdiv(a.P, 256));
 #define SHC_FWD(K_, S_) hipLaunchKernelGGL((sh_colors_fwd_kernel<K_, S_>), grid, dim3(256), 0, st, A, rgb);
-    SHC_DISPATCH(SHC_FWD)
+    SHC_DISPATCH(a, SHC_FWD)
 #undef SHC_FWD
     return hipGetLastError();
 }
@@ -426,17 +408,14 @@ hipError_t launch_sh_colors_bwd(const BagsShColors& a, const float* g_rgb, float
 {
     if (a.P <= 0) return g_campos ? hipMemsetAsync(g_campos, 0, 3 * sizeof(float), st) : hipSuccess;
     const ShcIn A{a.P, a.sh_degree, a.shs, a.shs_rest, a.xyz, a.campos};
-    const int K = a.K; const bool split = a.shs_rest != nullptr;
-    const int need_dir = (a.sh_degree > 0 && (g_xyz || g_campos)) ? 1 : 0;
-    float* const rows = (need_dir && g_campos) ? slab : nullptr;
-    const int nb = cdiv(a.P, 256);
-    if (g_shs || g_shs_rest || g_xyz || rows) {
-#define SHC_BWD(K_, S_) hipLaunchKernelGGL((sh_colors_bwd_kernel<K_, S_>), dim3(nb), dim3(256), 0, st, A, g_rgb, g_shs, g_shs_rest, g_xyz, rows, need_dir);
-        SHC_DISPATCH(SHC_BWD)
+    const ShcBwdPlan p = shc_bwd_plan(A.P, A.deg, g_shs || g_shs_rest, g_xyz != nullptr, g_campos != nullptr, slab);
+    if (p.main) {
+#define SHC_BWD(K_, S_) hipLaunchKernelGGL((sh_colors_bwd_kernel<K_, S_>), dim3(p.nb), dim3(256), 0, st, A, g_rgb, g_shs, g_shs_rest, g_xyz, p.rows, p.need_dir);
+        SHC_DISPATCH(a, SHC_BWD)
 #undef SHC_BWD
     }
     if (g_campos) {
-        if (rows) hipLaunchKernelGGL(sh_campos_reduce_kernel, dim3(3), dim3(256), 0, st, rows, nb, g_campos);
+        if (p.rows) hipLaunchKernelGGL(sh_campos_reduce_kernel, dim3(3), dim3(256), 0, st, p.rows, p.nb, g_campos);
         else { const hipError_t e = hipMemsetAsync(g_campos, 0, 3 * sizeof(float), st); if (e != hipSuccess) return e; }   // degree 0: no direction
     }
     return hipGetLastError();
@@ -448,10 +427,9 @@ hipError_t launch_sh_colors_views_fwd(const BagsShColorsViews& a, float* const* 
     ShcViewsIn A{a.P, a.sh_degree, a.V, a.shs, a.shs_rest, a.xyz, {}};
     ShcViewsOut O{};
     for (int v = 0; v < a.V; ++v) { A.campos[v] = a.campos[v]; O.p[v] = rgb[v]; }
-    const int K = a.K; const bool split = a.shs_rest != nullptr;
     const dim3 grid((unsigned)cdiv(a.P, 256));
 #define SHC_FWD(K_, S_) hipLaunchKernelGGL((sh_colors_views_fwd_kernel<K_, S_>), grid, dim3(256), 0, st, A, O);
-    SHC_DISPATCH(SHC_FWD)
+    SHC_DISPATCH(a, SHC_FWD)
 #undef SHC_FWD
     return hipGetLastError();
 }
@@ -467,15 +445,12 @@ hipError_t launch_sh_colors_views_bwd(const BagsShColorsViews& a, const float* c
         A.campos[v] = a.campos[v]; G.p[v] = g_rgb ? g_rgb[v] : nullptr; C.p[v] = g_campos ? g_campos[v] : nullptr;
         any_campos = any_campos || C.p[v] != nullptr;
     }
-    const int K = a.K; const bool split = a.shs_rest != nullptr;
-    const int need_dir = (a.P > 0 && a.sh_degree > 0 && (g_xyz || any_campos)) ? 1 : 0;
-    float* const rows = (need_dir && any_campos) ? slab : nullptr;
-    const int nb = cdiv(a.P > 0 ? a.P : 1, 256);
-    if (a.P > 0 && (g_shs || g_shs_rest || g_xyz || rows)) {
-#define SHC_BWD(K_, S_) hipLaunchKernelGGL((sh_colors_views_bwd_kernel<K_, S_>), dim3(nb), dim3(256), 0, st, A, G, g_shs, g_shs_rest, g_xyz, rows, need_dir);
-        SHC_DISPATCH(SHC_BWD)
+    const ShcBwdPlan p = shc_bwd_plan(A.P, A.deg, g_shs || g_shs_rest, g_xyz != nullptr, any_campos, slab);
+    if (p.main) {
+#define SHC_BWD(K_, S_) hipLaunchKernelGGL((sh_colors_views_bwd_kernel<K_, S_>), dim3(p.nb), dim3(256), 0, st, A, G, g_shs, g_shs_rest, g_xyz, p.rows, p.need_dir);
+        SHC_DISPATCH(a, SHC_BWD)
 #undef SHC_BWD
     }
-    if (any_campos) hipLaunchKernelGGL(sh_campos_views_reduce_kernel, dim3(3, a.V), dim3(256), 0, st, rows, rows ? nb : 0, C);
+    if (any_campos) hipLaunchKernelGGL(sh_campos_views_reduce_kernel, dim3(3, a.V), dim3(256), 0, st, p.rows, p.rows ? p.nb : 0, C);
     return hipGetLastError();
 }

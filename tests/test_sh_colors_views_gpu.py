@@ -24,7 +24,7 @@ import torch
 from bags_raster import _lib, sh_colors, sh_colors_views
 from bags_raster.gaussians import eval_sh
 from scenes import make_case
-from test_sh_colors_gpu import FACTOR, FLOOR, MAX_LEFT_OUT, NEAR, make_inputs
+from test_sh_colors_gpu import FACTOR, FLOOR, MAX_LEFT_OUT, NEAR, _rel_l2, make_inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -198,13 +198,6 @@ def test_backward_is_the_fold_of_the_single_view_gradients(P, V, maxdeg, deg):
         assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and torch.equal(a[2], b[2])
         for x, y in zip(a[3], b[3]):
             assert torch.equal(x, y)
-
-
-def _rel_l2(a, b, keep=None):
-    a, b = a.double(), b.double()
-    if keep is not None:
-        a, b = a[keep], b[keep]
-    return ((a - b).norm() / b.norm()).item()
 
 
 @pytest.mark.parametrize("P,V,maxdeg,deg", CASES)
