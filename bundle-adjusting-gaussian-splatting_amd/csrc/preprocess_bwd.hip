@@ -12,19 +12,7 @@
 // The forward quantities are recomputed from the inputs (cheaper than 100+ B/Gaussian of saved state).
 #include "bags_common.h"
 #include "sh_basis.h"
-
-struct CamConstB {
-    float v[16], m[16], k[16];
-    float campos[3];
-    float sf[3];
-};
-
-__device__ __forceinline__ float wave_sum(float x)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d);
-    return x;
-}
+#include "projection.h"
 
 // K8a: each Gaussian's consecutive partial records (written by blend_bwd at its emission slots) summed in list order.
 // Light kernel (high occupancy, two records in flight per lane): the record stream is the only traffic.  Gaussians with
@@ -137,6 +125,8 @@ __device__ __forceinline__ void sum_records(u32 nrec, u32 first, const float* __
 // Slab column t (summed over all Gaussians) -> its place in the five pose tensors.
 // slab layout: [0..11] viewmatrix rows 0..3 x cols 0..2, [12..23] projmatrix rows 0..3 x cols 0,1,3,
 //              [24] k0 [25] k5 [26] k8 [27] k9 [28] k11, [29..31] campos, [32..34] shift_factors.
+// (Inside preprocess_bwd_kernel a wave's row has nine more slots, [35..43]: the second contribution to [0..8], added when the
+// slab row is written.)
 // The entries of the 4x4 outputs no Gaussian contributes to are written as zeros by the column next to them.
 __device__ __forceinline__ void pose_write_out(const int t, const float val, float* __restrict__ g_view, float* __restrict__ g_proj,
                                                float* __restrict__ g_intr, float* __restrict__ g_campos, float* __restrict__ g_shift)
@@ -276,19 +266,13 @@ preprocess_bwd_kernel(int P, int M, int deg, int W, int H, float tanfovx, float 
         // (the abs sums were taken on the conic pre-scaled by log2 e)
         gdx = s[9] * (0.6931471805599453f * 0.5f * (float)W); gdy = s[10] * (0.6931471805599453f * 0.5f * (float)H);
 
-        // ---- recompute the forward chain
-        const float tx = x * v[0] + y * v[4] + z * v[8] + v[12];
-        const float ty = x * v[1] + y * v[5] + z * v[9] + v[13];
-        const float tz = x * v[2] + y * v[6] + z * v[10] + v[14];
-        const float rho = sqrtf(tx * tx + ty * ty + 1e-20f);
-        const float theta = det_atan2_pos(rho, tz);
-        const float th2 = theta * theta, th3 = th2 * theta;
-        const float shift = sf0 * th3 + sf1 * (th3 * th2) + sf2 * (th3 * th2 * th2);
-        const float tzs = tz + shift;
-        const float hx = x * m[0] + y * m[4] + z * m[8] + m[12] + shift * k[8];
-        const float hy = x * m[1] + y * m[5] + z * m[9] + m[13] + shift * k[9];
-        const float hw = x * m[3] + y * m[7] + z * m[11] + m[15] + shift * k[11];
-        const float pw = 1.0f / (hw + 1e-7f);
+        // ---- recompute the forward chain: projection.h, the statements K1 (preprocess_fwd.hip) ran
+        const PjView vs = pj_view(v, x, y, z);
+        const float tx = vs.tx, ty = vs.ty, tz = vs.tz;
+        const PjShift sh = pj_shift(tx, ty, tz, sf0, sf1, sf2);
+        const float rho = sh.rho, th2 = sh.th2, th3 = sh.th3, shift = sh.shift, tzs = sh.tzs;
+        const PjClip hp = pj_clip(m, k[8], k[9], k[11], x, y, z, shift);
+        const float hx = hp.hx, hy = hp.hy, pw = hp.pw;
 
         float c0, c1, c2, c3, c4, c5;
         float s0 = 0, s1 = 0, s2 = 0, qr = 0, qx = 0, qy = 0, qz = 0;
@@ -299,48 +283,34 @@ preprocess_bwd_kernel(int P, int M, int deg, int W, int H, float tanfovx, float 
             s0 = in_s0 * mod; s1 = in_s1 * mod; s2 = in_s2 * mod;
             const float4 q = in_q;
             qr = q.x; qx = q.y; qy = q.z; qz = q.w;
-            r00 = 1.0f - 2.0f * (qy * qy + qz * qz); r01 = 2.0f * (qx * qy - qr * qz); r02 = 2.0f * (qx * qz + qr * qy);
-            r10 = 2.0f * (qx * qy + qr * qz); r11 = 1.0f - 2.0f * (qx * qx + qz * qz); r12 = 2.0f * (qy * qz - qr * qx);
-            r20 = 2.0f * (qx * qz - qr * qy); r21 = 2.0f * (qy * qz + qr * qx); r22 = 1.0f - 2.0f * (qx * qx + qy * qy);
-            const float l00 = r00 * s0, l01 = r01 * s1, l02 = r02 * s2;
-            const float l10 = r10 * s0, l11 = r11 * s1, l12 = r12 * s2;
-            const float l20 = r20 * s0, l21 = r21 * s1, l22 = r22 * s2;
-            c0 = l00 * l00 + l01 * l01 + l02 * l02; c1 = l00 * l10 + l01 * l11 + l02 * l12;
-            c2 = l00 * l20 + l01 * l21 + l02 * l22; c3 = l10 * l10 + l11 * l11 + l12 * l12;
-            c4 = l10 * l20 + l11 * l21 + l12 * l22; c5 = l20 * l20 + l21 * l21 + l22 * l22;
+            const PjCov3d S = pj_cov3d(s0, s1, s2, qr, qx, qy, qz);
+            r00 = S.r00; r01 = S.r01; r02 = S.r02; r10 = S.r10; r11 = S.r11; r12 = S.r12; r20 = S.r20; r21 = S.r21; r22 = S.r22;
+            c0 = S.c0; c1 = S.c1; c2 = S.c2; c3 = S.c3; c4 = S.c4; c5 = S.c5;
         }
-        const float fx = k[0] * (0.5f * (float)W), fy = k[5] * (0.5f * (float)H);
-        const float limx = 1.3f * tanfovx, limy = 1.3f * tanfovy;
-        const float itz = 1.0f / tzs;
-        const float txtz = tx / tzs, tytz = ty / tzs;                 // same expressions as preprocess_fwd
-        const bool clx = (txtz < -limx) || (txtz > limx), cly = (tytz < -limy) || (tytz > limy);
-        const float ux = fminf(limx, fmaxf(-limx, txtz)), uy = fminf(limy, fmaxf(-limy, tytz));
-        const float itz2 = itz * itz;
-        const float j00 = fx * itz, j02 = -(fx * (ux * tzs)) * itz2, j11 = fy * itz, j12 = -(fy * (uy * tzs)) * itz2;
-        const float a00 = j00 * v[0] + j02 * v[2], a01 = j00 * v[4] + j02 * v[6], a02 = j00 * v[8] + j02 * v[10];
-        const float a10 = j11 * v[1] + j12 * v[2], a11 = j11 * v[5] + j12 * v[6], a12 = j11 * v[9] + j12 * v[10];
-        const float b00 = a00 * c0 + a01 * c1 + a02 * c2, b01 = a00 * c1 + a01 * c3 + a02 * c4, b02 = a00 * c2 + a01 * c4 + a02 * c5;
-        const float b10 = a10 * c0 + a11 * c1 + a12 * c2, b11 = a10 * c1 + a11 * c3 + a12 * c4, b12 = a10 * c2 + a11 * c4 + a12 * c5;
-        const float cxx = b00 * a00 + b01 * a01 + b02 * a02 + 0.3f;
-        const float cxy = b00 * a10 + b01 * a11 + b02 * a12;
-        const float cyy = b10 * a10 + b11 * a11 + b12 * a12 + 0.3f;
+        const PjCov2d C = pj_cov2d(v, k[0], k[5], W, H, tanfovx, tanfovy, tx, ty, tzs, c0, c1, c2, c3, c4, c5);
+        const float fx = C.fx, fy = C.fy, itz = C.itz, ux = C.ux, uy = C.uy;
+        const bool clx = (C.txtz < -C.limx) || (C.txtz > C.limx), cly = (C.tytz < -C.limy) || (C.tytz > C.limy);
+        const float j00 = C.j00, j02 = C.j02, j11 = C.j11, j12 = C.j12;
+        const float a00 = C.a00, a01 = C.a01, a02 = C.a02, a10 = C.a10, a11 = C.a11, a12 = C.a12;
+        const float b00 = C.b00, b01 = C.b01, b02 = C.b02, b10 = C.b10, b11 = C.b11, b12 = C.b12;
+        const float cxx = C.cxx, cxy = C.cxy, cyy = C.cyy;
         // ---- 3. conic -> cov2D.  For needle-shaped splats (lambda1 >> lambda2) dL/dcov2D is ~ g n n^T (n = thin axis) and
         // the next step multiplies it by B = A Sigma, whose component along the long axis is lambda1/lambda2 times larger
         // than the one that matters: the long-axis component of dL/dcov2D must be accurate to ~1e-7 of the WHOLE matrix.
         // The expanded polynomial -Q G Q (three products of size |G|/lambda2^2 per entry) is not, and gave O(1) errors at
         // 1500:1 anisotropy; the two-step form below (trace term first, then one two-term difference per entry) keeps
         // that component at rounding level.  It is the order reverse-mode differentiation of the forward lines produces.
-        // The file is compiled with -ffp-contract=off so cov2D and det are bit-identical to what preprocess_fwd used.
-        const float det = cxx * cyy - cxy * cxy;
-        const float di = 1.0f / det;
+        // cov2D, det and the conic are projection.h's statements, rounded as in preprocess_fwd (-ffp-contract=off in both files).
+        const PjConic Q = pj_conic(cxx, cxy, cyy);
+        const float det = Q.det, di = Q.det_inv;
         // BagsSettings.conic_grad (decision D9).  Upstream's computeCov2DCUDA backward multiplies every term by denom2inv =
         // 1 / (det^2 + 1e-7) where the derivative of the inverse has 1 / det^2 -- in the two-step form below that is 1 / det ->
         // det * denom2inv and 1 / det^2 -> denom2inv (the same three sums as upstream's expanded polynomial, term for term).
         // BAGS_CONIC_GRAD_EXACT: the exact derivative.  The forward's conic keeps the exact 1 / det either way.
         const float di2 = conic_stock ? 1.0f / (det * det + 1.0e-7f) : di * di;
         const float dig = conic_stock ? det * di2 : di;
-        {   // K1's conic = (cyy, -cxy, cxx) / det from the same operations (contraction off in both files): bit-identical
-            const float con_a = cyy * di, con_b = -cxy * di, con_c = cxx * di;
+        {   // K1's conic (projection.h: pj_conic)
+            const float con_a = Q.con_a, con_b = Q.con_b, con_c = Q.con_c;
             const float dpx = -(con_a * Mx + con_b * My);     // dL/d centre (pixel units)
             const float dpy = -(con_c * My + con_b * Mx);
             gm2x = dpx * (0.5f * (float)W); gm2y = dpy * (0.5f * (float)H);
@@ -364,9 +334,7 @@ preprocess_bwd_kernel(int P, int M, int deg, int W, int H, float tanfovx, float 
         const float dj02 = dA00 * v[2] + dA01 * v[6] + dA02 * v[10];
         const float dj11 = dA10 * v[1] + dA11 * v[5] + dA12 * v[9];
         const float dj12 = dA10 * v[2] + dA11 * v[6] + dA12 * v[10];
-        // pose slab: [0..11] viewmatrix (rows 0..3 x cols 0..2), [12..23] projmatrix (rows 0..3 x cols 0,1,3),
-        //            [24] k0 [25] k5 [26] k8 [27] k9 [28] k11, [29..31] campos, [32..34] shift_factors;
-        //            [35..43] second contribution to [0..8] (added when the slab row is written)
+        // pose slab columns: the layout above pose_write_out
         red(0, dA00 * j00); red(1, dA10 * j11); red(2, dA00 * j02 + dA10 * j12);      // v[0], v[1], v[2]
         red(3, dA01 * j00); red(4, dA11 * j11); red(5, dA01 * j02 + dA11 * j12);      // v[4], v[5], v[6]
         red(6, dA02 * j00); red(7, dA12 * j11); red(8, dA02 * j02 + dA12 * j12);      // v[8], v[9], v[10]

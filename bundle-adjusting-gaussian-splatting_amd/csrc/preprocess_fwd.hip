@@ -2,12 +2,14 @@
 //
 // COMPILED WITH -ffp-contract=off: the integer artefacts (radius, tile rectangle, depth key) must be bit-identical
 // to the fp32 oracle (oracle/raster_oracle.py: preprocess), so every expression here is the same sequence of
-// individually rounded IEEE fp32 mul/add/div/sqrt, left to right.  Algorithm: SURVEY.md Appendix A.1; conventions:
+// individually rounded IEEE fp32 mul/add/div/sqrt, left to right.  The geometry from the view-space point to the conic is
+// projection.h's (shared with preprocess_bwd.hip, which re-derives it).  Algorithm: SURVEY.md Appendix A.1; conventions:
 // utils/graphics_utils.py:26-33 (row-vector transforms), utils/general_utils.py:130-163 (quaternion order, R.S),
 // utils/sh_utils.py:57-112 (SH basis), gaussian_renderer/__init__.py:92-95 (+0.5, clamp at 0).
 #include "bags_common.h"
 #include "sh_basis.h"
 #include "binning_common.h"
+#include "projection.h"
 
 struct CamConst {
     float v[16], m[16], k[16];
@@ -65,6 +67,20 @@ struct K1Result {
     u32 key, tiles; int radius; uint2 rect; u64 keep; float2 pxy; float4 q0, rgbz_v;
     u32 rtiles; uint2 rrect; u64 rkeep;          // the tiles a partial-gradient record exists for (= tiles / rect / keep unless rec_opacity)
 };
+// what K1 stores for a Gaussian that is culled (or lies past the end of the last block)
+__device__ __forceinline__ K1Result k1_culled()
+{
+    K1Result R;
+    R.key = KEY_CULLED; R.tiles = 0; R.radius = 0; R.rect = make_uint2(0u, 0u); R.keep = ~0ull; R.pxy = make_float2(0.f, 0.f);
+    R.q0 = make_float4(0.f, 0.f, 0.f, 0.f); R.rgbz_v = R.q0; R.rtiles = 0; R.rrect = make_uint2(0u, 0u); R.rkeep = ~0ull;
+    return R;
+}
+// tile coordinate of pixel coordinate v / 16 (+ add), clamped to [0, g]; the float clamp keeps a huge v inside the int conversion
+__device__ __forceinline__ int tile_coord(const float v, const int add, const int g)
+{
+    const float big = 1.0e9f;
+    return min(g, max(0, (int)fminf(big, fmaxf(-big, v / 16.0f)) + add));
+}
 struct K1Outputs {
     u32* depth_key; float4* g2d; uint2* rect; u32* tiles_touched; u64* keep; int32_t* radii; float* mean2D; u32* rec_count;
 };
@@ -74,7 +90,6 @@ __device__ __forceinline__ K1Result k1_project(const K1Args& A, const CamConst& 
 {
     const int M = A.M, deg = A.deg, W = A.W, H = A.H, depth_mode = A.depth_mode, tile_bounds = A.tile_bounds;
     const bool want_opacity = (tile_bounds == BAGS_TILES_OPACITY) || (A.rec_opacity != 0);
-    u32 rtiles = 0; uint2 rrect = make_uint2(0u, 0u); u64 rkeep = ~0ull;
     const float tanfovx = A.tanfovx, tanfovy = A.tanfovy, mod = A.mod;
     const float* __restrict__ means3D = A.means3D; const float* __restrict__ means2D = A.means2D;
     const float* __restrict__ shs = A.shs; const float* __restrict__ colors_precomp = A.colors_precomp;
@@ -83,32 +98,19 @@ __device__ __forceinline__ K1Result k1_project(const K1Args& A, const CamConst& 
     float* __restrict__ shjac = A.shjac;
     const float* v = cam.v; const float* m = cam.m; const float* k = cam.k;
 
-    // defaults for a culled Gaussian
-    u32 key = KEY_CULLED; u32 tiles = 0; int radius = 0;
-    uint2 rect = make_uint2(0u, 0u);
-    u64 keep = ~0ull; bool masked = false;
-    float2 pxy = make_float2(0.f, 0.f);
-    float4 q0 = make_float4(0.f, 0.f, 0.f, 0.f), rgbz_v = q0;
+    K1Result R = k1_culled();
+    bool masked = false;
 
     const float x = means3D[3 * i + 0], y = means3D[3 * i + 1], z = means3D[3 * i + 2];
-    const float tx = x * v[0] + y * v[4] + z * v[8] + v[12];
-    const float ty = x * v[1] + y * v[5] + z * v[9] + v[13];
-    const float tz = x * v[2] + y * v[6] + z * v[10] + v[14];
-    bool ok = tz > 0.2f;                                   // near-plane cull
+    // the geometry from here to the conic is projection.h's: the one statement K9 re-derives bit for bit
+    const PjView vs = pj_view(v, x, y, z);
+    const float tx = vs.tx, ty = vs.ty;
+    bool ok = vs.tz > 0.2f;                                // near-plane cull
     if (ok) {
-        // D2: entrance-pupil shift (zero factors => exact identity)
-        const float rho = sqrtf(tx * tx + ty * ty + 1e-20f);
-        const float theta = det_atan2_pos(rho, tz);
-        const float th2 = theta * theta;
-        const float th3 = th2 * theta;
-        const float shift = cam.sf[0] * th3 + cam.sf[1] * (th3 * th2) + cam.sf[2] * (th3 * th2 * th2);
-        const float tzs = tz + shift;
-
-        const float hx = x * m[0] + y * m[4] + z * m[8] + m[12] + shift * k[8];
-        const float hy = x * m[1] + y * m[5] + z * m[9] + m[13] + shift * k[9];
-        const float hw = x * m[3] + y * m[7] + z * m[11] + m[15] + shift * k[11];
-        const float pw = 1.0f / (hw + 1e-7f);
-        float ndc_x = hx * pw, ndc_y = hy * pw;
+        const PjShift sh = pj_shift(tx, ty, vs.tz, cam.sf[0], cam.sf[1], cam.sf[2]);
+        const float tzs = sh.tzs;
+        const PjClip h = pj_clip(m, k[8], k[9], k[11], x, y, z, sh.shift);
+        float ndc_x = h.hx * h.pw, ndc_y = h.hy * h.pw;
         if (means2D) { ndc_x = ndc_x + means2D[3 * i + 0]; ndc_y = ndc_y + means2D[3 * i + 1]; }
         const float px = ((ndc_x + 1.0f) * (float)W - 1.0f) * 0.5f;
         const float py = ((ndc_y + 1.0f) * (float)H - 1.0f) * 0.5f;
@@ -118,71 +120,25 @@ __device__ __forceinline__ K1Result k1_project(const K1Args& A, const CamConst& 
             const float* c = cov3D_precomp + 6 * (size_t)i;
             c0 = c[0]; c1 = c[1]; c2 = c[2]; c3 = c[3]; c4 = c[4]; c5 = c[5];
         } else {
-            const float s0 = scales[3 * i + 0] * mod, s1 = scales[3 * i + 1] * mod, s2 = scales[3 * i + 2] * mod;
             const float4 q = reinterpret_cast<const float4*>(rotations)[i];
-            const float qr = q.x, qx = q.y, qy = q.z, qz = q.w;
-            const float r00 = 1.0f - 2.0f * (qy * qy + qz * qz);
-            const float r01 = 2.0f * (qx * qy - qr * qz);
-            const float r02 = 2.0f * (qx * qz + qr * qy);
-            const float r10 = 2.0f * (qx * qy + qr * qz);
-            const float r11 = 1.0f - 2.0f * (qx * qx + qz * qz);
-            const float r12 = 2.0f * (qy * qz - qr * qx);
-            const float r20 = 2.0f * (qx * qz - qr * qy);
-            const float r21 = 2.0f * (qy * qz + qr * qx);
-            const float r22 = 1.0f - 2.0f * (qx * qx + qy * qy);
-            const float l00 = r00 * s0, l01 = r01 * s1, l02 = r02 * s2;
-            const float l10 = r10 * s0, l11 = r11 * s1, l12 = r12 * s2;
-            const float l20 = r20 * s0, l21 = r21 * s1, l22 = r22 * s2;
-            c0 = l00 * l00 + l01 * l01 + l02 * l02;
-            c1 = l00 * l10 + l01 * l11 + l02 * l12;
-            c2 = l00 * l20 + l01 * l21 + l02 * l22;
-            c3 = l10 * l10 + l11 * l11 + l12 * l12;
-            c4 = l10 * l20 + l11 * l21 + l12 * l22;
-            c5 = l20 * l20 + l21 * l21 + l22 * l22;
+            const PjCov3d S = pj_cov3d(scales[3 * i + 0] * mod, scales[3 * i + 1] * mod, scales[3 * i + 2] * mod, q.x, q.y, q.z, q.w);
+            c0 = S.c0; c1 = S.c1; c2 = S.c2; c3 = S.c3; c4 = S.c4; c5 = S.c5;
         }
-        const float fx = k[0] * (0.5f * (float)W);          // D1
-        const float fy = k[5] * (0.5f * (float)H);
-        const float limx = 1.3f * tanfovx, limy = 1.3f * tanfovy;
-        const float txtz = tx / tzs, tytz = ty / tzs;
-        const float cx_ = fminf(limx, fmaxf(-limx, txtz)) * tzs;
-        const float cy_ = fminf(limy, fmaxf(-limy, tytz)) * tzs;
-        const float itz = 1.0f / tzs;
-        const float itz2 = itz * itz;
-        const float j00 = fx * itz;
-        const float j02 = -(fx * cx_) * itz2;
-        const float j11 = fy * itz;
-        const float j12 = -(fy * cy_) * itz2;
-        const float a00 = j00 * v[0] + j02 * v[2];
-        const float a01 = j00 * v[4] + j02 * v[6];
-        const float a02 = j00 * v[8] + j02 * v[10];
-        const float a10 = j11 * v[1] + j12 * v[2];
-        const float a11 = j11 * v[5] + j12 * v[6];
-        const float a12 = j11 * v[9] + j12 * v[10];
-        const float b00 = a00 * c0 + a01 * c1 + a02 * c2;
-        const float b01 = a00 * c1 + a01 * c3 + a02 * c4;
-        const float b02 = a00 * c2 + a01 * c4 + a02 * c5;
-        const float b10 = a10 * c0 + a11 * c1 + a12 * c2;
-        const float b11 = a10 * c1 + a11 * c3 + a12 * c4;
-        const float b12 = a10 * c2 + a11 * c4 + a12 * c5;
-        const float cxx = b00 * a00 + b01 * a01 + b02 * a02 + 0.3f;
-        const float cxy = b00 * a10 + b01 * a11 + b02 * a12;
-        const float cyy = b10 * a10 + b11 * a11 + b12 * a12 + 0.3f;
-        const float det = cxx * cyy - cxy * cxy;
+        const PjCov2d C = pj_cov2d(v, k[0], k[5], W, H, tanfovx, tanfovy, tx, ty, tzs, c0, c1, c2, c3, c4, c5);
+        const float cxx = C.cxx, cyy = C.cyy;
+        const PjConic Q = pj_conic(cxx, C.cxy, cyy);
+        const float det = Q.det;
         ok = (det != 0.0f);
         if (ok) {
-            const float det_inv = 1.0f / det;
-            const float con_a = cyy * det_inv, con_b = -cxy * det_inv, con_c = cxx * det_inv;
+            const float con_a = Q.con_a, con_b = Q.con_b, con_c = Q.con_c;
             const float mid = 0.5f * (cxx + cyy);
             const float lam = mid + sqrtf(fmaxf(mid * mid - det, 0.1f));
             const float rad_f = ceilf(3.0f * sqrtf(lam));
             ok = isfinite(px) && isfinite(py) && isfinite(rad_f);
             if (ok) {
                 const int gx = (W + BAGS_TILE - 1) / BAGS_TILE, gy = (H + BAGS_TILE - 1) / BAGS_TILE;
-                const float big = 1.0e9f;
-                const int minx = min(gx, max(0, (int)fminf(big, fmaxf(-big, (px - rad_f) / 16.0f))));
-                const int miny = min(gy, max(0, (int)fminf(big, fmaxf(-big, (py - rad_f) / 16.0f))));
-                const int maxx = min(gx, max(0, (int)fminf(big, fmaxf(-big, (px + rad_f + 15.0f) / 16.0f))));
-                const int maxy = min(gy, max(0, (int)fminf(big, fmaxf(-big, (py + rad_f + 15.0f) / 16.0f))));
+                const int minx = tile_coord(px - rad_f, 0, gx), miny = tile_coord(py - rad_f, 0, gy);
+                const int maxx = tile_coord(px + rad_f + 15.0f, 0, gx), maxy = tile_coord(py + rad_f + 15.0f, 0, gy);
                 const int nt = (maxx - minx) * (maxy - miny);
                 if (nt > 0) {                                // "visible" (radii > 0) is decided by the stock rectangle
                     int ex0 = minx, ey0 = miny, ex1 = maxx, ey1 = maxy;      // rectangle the instances are emitted for
@@ -202,34 +158,32 @@ __device__ __forceinline__ K1Result k1_project(const K1Args& A, const CamConst& 
                             const float lnu = (float)e2 * 0.6931472f + poly + 1.0e-3f;
                             const float tau2 = 2.0f * lnu + 0.02f;
                             const float rx = sqrtf(tau2 * cxx) * 1.02f + 0.1f, ry = sqrtf(tau2 * cyy) * 1.02f + 0.1f;
-                            ex0 = max(ex0, min(gx, max(0, (int)fminf(big, fmaxf(-big, (px - rx) / 16.0f)))));
-                            ey0 = max(ey0, min(gy, max(0, (int)fminf(big, fmaxf(-big, (py - ry) / 16.0f)))));
-                            ex1 = min(ex1, min(gx, max(0, (int)fminf(big, fmaxf(-big, (px + rx) / 16.0f)) + 1)));
-                            ey1 = min(ey1, min(gy, max(0, (int)fminf(big, fmaxf(-big, (py + ry) / 16.0f)) + 1)));
+                            ex0 = max(ex0, tile_coord(px - rx, 0, gx)); ey0 = max(ey0, tile_coord(py - ry, 0, gy));
+                            ex1 = min(ex1, tile_coord(px + rx, 1, gx)); ey1 = min(ey1, tile_coord(py + ry, 1, gy));
                             if (ex1 <= ex0 || ey1 <= ey0) { ex1 = ex0; ey1 = ey0; }
 #ifndef NO_TILE_MASKS            // experiment switch (tools/ab_masks.sh): rectangles only, as before the masks
                             else if (ex1 - ex0 <= 8 && ey1 - ey0 <= 8 && con_a > 0.0f && con_c > 0.0f &&
                                      con_a * con_c - con_b * con_b > 0.0f) {
-                                keep = tile_reach(px, py, con_a, con_b, con_c, tau2 * 1.02f, ex0, ey0, ex1 - ex0, ey1 - ey0);
+                                R.keep = tile_reach(px, py, con_a, con_b, con_c, tau2 * 1.02f, ex0, ey0, ex1 - ex0, ey1 - ey0);
                                 masked = true;
                             }
 #endif
                         }
                     }
-                    if (!masked) keep = rect_full_mask(ex1 - ex0, ey1 - ey0);
-                    tiles = masked ? (u32)__popcll(keep) : (u32)((ex1 - ex0) * (ey1 - ey0));
-                    radius = (int)rad_f;
-                    rect = make_uint2((u32)ex0 | ((u32)ey0 << 16), (u32)ex1 | ((u32)ey1 << 16));
-                    rtiles = tiles; rrect = rect; rkeep = keep;                 // records: the opacity rule's tiles
+                    if (!masked) R.keep = rect_full_mask(ex1 - ex0, ey1 - ey0);
+                    R.tiles = masked ? (u32)__popcll(R.keep) : (u32)((ex1 - ex0) * (ey1 - ey0));
+                    R.radius = (int)rad_f;
+                    R.rect = make_uint2((u32)ex0 | ((u32)ey0 << 16), (u32)ex1 | ((u32)ey1 << 16));
+                    R.rtiles = R.tiles; R.rrect = R.rect; R.rkeep = R.keep;     // records: the opacity rule's tiles
                     if (tile_bounds != BAGS_TILES_OPACITY) {                    // lists: the stock square, every tile of it
-                        keep = rect_full_mask(maxx - minx, maxy - miny);
-                        tiles = (u32)nt;
-                        rect = make_uint2((u32)minx | ((u32)miny << 16), (u32)maxx | ((u32)maxy << 16));
-                        if (!A.rec_opacity) { rtiles = tiles; rrect = rect; rkeep = keep; }
+                        R.keep = rect_full_mask(maxx - minx, maxy - miny);
+                        R.tiles = (u32)nt;
+                        R.rect = make_uint2((u32)minx | ((u32)miny << 16), (u32)maxx | ((u32)maxy << 16));
+                        if (!A.rec_opacity) { R.rtiles = R.tiles; R.rrect = R.rect; R.rkeep = R.keep; }
                     }
-                    pxy = make_float2(px, py);
+                    R.pxy = make_float2(px, py);
                     const float dsort = (depth_mode == BAGS_DEPTH_DISTANCE) ? sqrtf(tx * tx + ty * ty + tzs * tzs) : tzs;
-                    key = __float_as_uint(dsort);
+                    R.key = __float_as_uint(dsort);
                     // colour
                     float r, g, b; u32 cl = 0;
                     if (colors_precomp) {
@@ -316,15 +270,12 @@ __device__ __forceinline__ K1Result k1_project(const K1Args& A, const CamConst& 
                         if (b < 0.f) { cl |= 4u; b = 0.f; }
                         mj[9] = __uint_as_float(cl);
                     }
-                    q0 = make_float4(con_a, con_b, con_c, opacities[i]);
-                    rgbz_v = make_float4(r, g, b, tzs);
+                    R.q0 = make_float4(con_a, con_b, con_c, opacities[i]);
+                    R.rgbz_v = make_float4(r, g, b, tzs);
                 }
             }
         }
     }
-    K1Result R;
-    R.key = key; R.tiles = tiles; R.radius = radius; R.rect = rect; R.keep = keep; R.pxy = pxy; R.q0 = q0; R.rgbz_v = rgbz_v;
-    R.rtiles = rtiles; R.rrect = rrect; R.rkeep = rkeep;
     return R;
 }
 
@@ -411,9 +362,7 @@ preprocess_fwd_count_kernel(const K1Args A, const float* __restrict__ viewmatrix
         const long long gi = (long long)blockIdx.x * per_block + (long long)pass * BIN_THREADS + threadIdx.x;
         const bool valid = gi < (long long)A.P;
         const int i = (int)(valid ? gi : 0);
-        K1Result R;
-        R.key = KEY_CULLED; R.tiles = 0; R.radius = 0; R.rect = make_uint2(0u, 0u); R.keep = ~0ull; R.pxy = make_float2(0.f, 0.f);
-        R.q0 = make_float4(0.f, 0.f, 0.f, 0.f); R.rgbz_v = R.q0; R.rtiles = 0; R.rrect = make_uint2(0u, 0u); R.rkeep = ~0ull;
+        K1Result R = k1_culled();
         if (valid) R = k1_project<SPLIT>(A, cam, i);
         __builtin_amdgcn_sched_barrier(0);
         // ---- (block, tile) counts: small rectangles by their tile mask, larger ones tile by tile, huge ones by the whole wave
@@ -448,6 +397,30 @@ preprocess_fwd_count_kernel(const K1Args A, const float* __restrict__ viewmatrix
     for (int t = threadIdx.x; t < T2; t += BIN_THREADS) row[t] = cnt[t];
 }
 
+// SPLIT (BagsInputs.shs_rest given) picks the instance; count_into != nullptr the kernel that also counts the (block, tile) matrix
+template <bool SPLIT>
+static hipError_t k1_launch(const BagsSettings& s, const BagsInputs& in, const GeomView& g, const K1Args& A, const K1Outputs& O,
+                            hipStream_t st, const ImgView* count_into, int grid_x)
+{
+    const int P = in.P;
+    if (!count_into) {
+        LAUNCH_K(preprocess_fwd_kernel<SPLIT>, dim3(cdiv(P, 256)), dim3(256), 0, st, A, s.viewmatrix, s.projmatrix, s.intrinsic,
+                           s.campos, in.shift_factors, O);
+        return hipGetLastError();
+    }
+    const int gy = cdiv(s.image_height, BAGS_TILE), T = grid_x * gy, T2 = (T + 1) / 2;
+    const int per = binned_per_block(P), B = cdiv(P, per);
+    const size_t lds = (size_t)T2 * 4;
+    if (lds + 1024 > 65536) {                                // beyond the default 64 KB of LDS per workgroup the launch has to opt in
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(preprocess_fwd_count_kernel<SPLIT>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    LAUNCH_K(preprocess_fwd_count_kernel<SPLIT>, dim3(B), dim3(BIN_THREADS), lds, st, A, s.viewmatrix, s.projmatrix,
+                       s.intrinsic, s.campos, in.shift_factors, O, per, grid_x, T2, count_into->cnt_rows, g.local_off, g.block_total);
+    return hipGetLastError();
+}
+
 hipError_t launch_preprocess_fwd(const BagsSettings& s, const BagsInputs& in, const GeomView& g, int32_t* radii,
                                  float* mean2D, hipStream_t st, const ImgView* count_into, int grid_x)
 {
@@ -462,28 +435,5 @@ hipError_t launch_preprocess_fwd(const BagsSettings& s, const BagsInputs& in, co
     K1Outputs O;
     O.depth_key = g.depth_key; O.g2d = g.g2d; O.rect = g.rect; O.tiles_touched = g.tiles_touched; O.keep = g.keep; O.radii = radii;
     O.mean2D = mean2D; O.rec_count = g.rec_count;
-    if (count_into) {                                        // tile-binned path: K1 also counts the (block, tile) matrix
-        const int gy = cdiv(s.image_height, BAGS_TILE), T = grid_x * gy, T2 = (T + 1) / 2;
-        const int per = binned_per_block(P), B = cdiv(P, per);
-        const size_t lds = (size_t)T2 * 4;
-        const void* fn = in.shs_rest ? reinterpret_cast<const void*>(preprocess_fwd_count_kernel<true>)
-                                     : reinterpret_cast<const void*>(preprocess_fwd_count_kernel<false>);
-        if (lds + 1024 > 65536) {                            // beyond the default 64 KB of LDS per workgroup the launch has to opt in
-            hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
-#define LAUNCH_COUNT(SP)                                                                                                       \
-        LAUNCH_K(preprocess_fwd_count_kernel<SP>, dim3(B), dim3(BIN_THREADS), lds, st, A, s.viewmatrix, s.projmatrix,  \
-                           s.intrinsic, s.campos, in.shift_factors, O, per, grid_x, T2, count_into->cnt_rows, g.local_off, g.block_total)
-        if (in.shs_rest) LAUNCH_COUNT(true); else LAUNCH_COUNT(false);
-#undef LAUNCH_COUNT
-        return hipGetLastError();
-    }
-    if (in.shs_rest)
-        LAUNCH_K(preprocess_fwd_kernel<true>, dim3(cdiv(P, 256)), dim3(256), 0, st, A, s.viewmatrix, s.projmatrix, s.intrinsic,
-                           s.campos, in.shift_factors, O);
-    else
-        LAUNCH_K(preprocess_fwd_kernel<false>, dim3(cdiv(P, 256)), dim3(256), 0, st, A, s.viewmatrix, s.projmatrix, s.intrinsic,
-                           s.campos, in.shift_factors, O);
-    return hipGetLastError();
+    return in.shs_rest ? k1_launch<true>(s, in, g, A, O, st, count_into, grid_x) : k1_launch<false>(s, in, g, A, O, st, count_into, grid_x);
 }

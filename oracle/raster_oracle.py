@@ -259,7 +259,8 @@ def preprocess(means3D, means2D, shift_factors, shs, colors_precomp, opacities, 
     """Per-Gaussian projection, EWA covariance, radius, tile rectangle, colour  (SURVEY Appendix A.1).
 
     Every expression below is the exact fp32 operation sequence of the HIP kernel ``preprocess_fwd``
-    (csrc/bags_raster.hip): a*b + c*d is two rounded products and one rounded sum, evaluated left to right.
+    (csrc/preprocess_fwd.hip; the chain from the view-space point to the conic is csrc/projection.h, the kernel side this
+    function mirrors): a*b + c*d is two rounded products and one rounded sum, evaluated left to right.
     The differentiable graph is built on the near-plane survivors only, so culled Gaussians can never leak a
     0*inf into the pose-gradient sums.
     """
