@@ -10,7 +10,9 @@ from .render import render, render_views, PipelineParams
 from .gaussians import GaussianBag, eval_sh, sh_colors, sh_colors_views
 from .io import save_ply, load_ply, save_checkpoint, load_checkpoint
 from .optim import GaussianAdam
+from .pose_bank import PoseBank, PoseAdam
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "debug_views",
            "compute_relocation", "render", "render_views", "PipelineParams", "GaussianBag", "eval_sh", "sh_colors", "sh_colors_views",
-           "save_ply", "load_ply", "save_checkpoint", "load_checkpoint", "GaussianAdam"]
+           "save_ply", "load_ply", "save_checkpoint", "load_checkpoint", "GaussianAdam",
+           "PoseBank", "PoseAdam"]

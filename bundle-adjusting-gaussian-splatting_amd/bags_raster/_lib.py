@@ -85,6 +85,25 @@ class BagsCamera(C.Structure):
                 ("znear", C.c_float), ("zfar", C.c_float)]
 
 
+MAX_POSE_ROWS = 16
+POSE_LEAVES = 9                             # a row of the bank's tables: delta_quaternion 0..3 | delta_translation 4..6 | fovx 7 | fovy 8
+
+
+class BagsPoseBank(C.Structure):            # the cameras of one step out of a bank of N; the row list travels by value
+    _fields_ = [("N", C.c_int32), ("init_quaternion", c_fp), ("init_translation", c_fp), ("near_far", c_fp), ("leaves", c_fp),
+                ("global_rotation", c_fp), ("global_translation_scale", c_fp), ("n_rows", C.c_int32), ("rows", C.c_int32 * MAX_POSE_ROWS)]
+
+
+class BagsPoseAdamGroup(C.Structure):
+    _fields_ = [("enabled", C.c_int32), ("step_size", C.c_float), ("bias_correction2_sqrt", C.c_float)]
+
+
+class BagsPoseAdamArgs(C.Structure):
+    _fields_ = [("N", C.c_int32), ("n_rows", C.c_int32), ("leaves", c_fp), ("grad", c_fp), ("exp_avg", c_fp), ("exp_avg_sq", c_fp),
+                ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("rows", C.c_int32 * MAX_POSE_ROWS),
+                ("groups", (BagsPoseAdamGroup * 3) * MAX_POSE_ROWS)]
+
+
 class BagsRawGaussians(C.Structure):
     _fields_ = [("P", C.c_int32), ("K", C.c_int32), ("features_dc", C.c_void_p), ("features_rest", C.c_void_p),
                 ("opacity", C.c_void_p), ("scaling", C.c_void_p), ("rotation", C.c_void_p)]
@@ -174,6 +193,9 @@ SYMBOLS = {    "bags_abi_version": (C.c_int, []),
                                                  C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bags_camera_forward": (C.c_int, [C.POINTER(BagsCamera), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bags_camera_backward": (C.c_int, [C.POINTER(BagsCamera)] + [C.c_void_p] * 11),
+    "bags_pose_bank_forward": (C.c_int, [C.POINTER(BagsPoseBank), c_fp, c_fp, c_fp, c_fp, C.c_void_p]),
+    "bags_pose_bank_backward": (C.c_int, [C.POINTER(BagsPoseBank)] + [c_fp] * 7 + [C.c_void_p]),
+    "bags_pose_adam_step": (C.c_int, [C.POINTER(BagsPoseAdamArgs), C.c_void_p]),
     "bags_resample_forward": (C.c_int, [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p] + [C.c_int32] * 6 + [C.c_void_p] * 4),
     "bags_resample_workspace_size": (C.c_size_t, [C.c_int32] * 4),
     "bags_resample_backward": (C.c_int, [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p] + [C.c_int32] * 6 +

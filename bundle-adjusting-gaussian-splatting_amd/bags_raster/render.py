@@ -13,8 +13,9 @@ arguments, same choice of covariance path (``pipe.compute_cov3D_python``) and co
   * on a GPU the Python-side SH colours (``hybrid`` / ``pipe.convert_SHs_python``) come from ``bags_raster.sh_colors``, one HIP
     launch each way, fed with ``_features_dc`` / ``_features_rest`` as stored; ``_python_colors`` is the host path.
 
-``render_views()`` is ``render()`` for the V cameras of one step: the same dictionaries, the activations once, and on the fused
-colour path one ``bags_raster.sh_colors_views`` call for the colours of all the cameras.
+``render_views()`` is ``render()`` for the V cameras of one step: the same dictionaries, the activations once, on the fused
+colour path one ``bags_raster.sh_colors_views`` call for the colours of all the cameras, and for the cameras of a
+``bags_raster.PoseBank`` one chain launch each way for all of them.
 """
 from __future__ import annotations
 
@@ -24,8 +25,9 @@ from typing import Optional
 
 import torch
 
-from ._lib import MAX_SH_VIEWS
+from ._lib import MAX_POSE_ROWS, MAX_SH_VIEWS
 from .gaussians import eval_sh, sh_colors, sh_colors_views
+from .pose_bank import PoseBankCamera
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer
 
 
@@ -180,6 +182,20 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, mlp_color, shift_
                            iteration, depth_key, depth_weights_grad, act, matrices, fused_rgb)
 
 
+def _camera_chains(cameras, global_alignment):
+    """``_camera_chain`` of every camera of a step.  Distinct rows of ONE ``PoseBank`` (``bank.camera(i)``) on a GPU go through the
+    chain together, one launch each way per 16 cameras, and are unbound per view; any other list takes the per-camera path."""
+    if cameras and all(isinstance(c, PoseBankCamera) and c.bank is cameras[0].bank for c in cameras):
+        bank, rows = cameras[0].bank, [c.row for c in cameras]
+        if bank.leaves.is_cuda and len(set(rows)) == len(rows):
+            ga = global_alignment if global_alignment is not None else (None, None)
+            matrices = []
+            for b in range(0, len(rows), MAX_POSE_ROWS):
+                matrices.extend(zip(*(t.unbind(0) for t in bank.get_matrices(rows[b:b + MAX_POSE_ROWS], ga[0], ga[1]))))
+            return matrices
+    return [_camera_chain(cam, global_alignment) for cam in cameras]
+
+
 # render_views' fused colour branch: True = one sh_colors_views call per chunk of cameras, False = one sh_colors call per camera.
 # (profiles/sh_colors/NOTES.md holds the measurement this default rests on.)
 MULTI_VIEW_COLORS = True
@@ -191,14 +207,15 @@ def render_views(cameras, pc, pipe, bg_color: torch.Tensor, mlp_color, shift_fac
     """``[render(cam, pc, ...) for cam in cameras]`` for the views of ONE step (a cubemap's faces, a rank's V views): a list of
     ``render()``'s dictionaries, every tensor in them the bits ``render()`` gives for that camera.
 
-    The activations are evaluated once for the list and the camera chain once per camera.  On ``render()``'s fused colour branch
+    The activations are evaluated once for the list and the camera chain once per camera -- or, for the ``camera(i)`` objects of
+    one ``PoseBank``, once per 16 cameras.  On ``render()``'s fused colour branch
     (a GPU, ``hybrid`` or ``pipe.convert_SHs_python``, no ``override_color``) the colours of up to 16 cameras come from one
     ``sh_colors_views`` call: the coefficient rows are read once each way for all of them, and one backward through the summed
     loss writes each Gaussian gradient once instead of accumulating it view by view.  On every other colour path each camera
     takes the path ``render()`` takes."""
     cameras = list(cameras)
     act = _activate(pc, pipe, hybrid, override_color)
-    matrices = [_camera_chain(cam, global_alignment) for cam in cameras]
+    matrices = _camera_chains(cameras, global_alignment)
     fused_rgb = [None] * len(cameras)
     if act.fused_colors:
         shs, rest = (pc._features_dc, pc._features_rest) if act.split else (act.features, None)

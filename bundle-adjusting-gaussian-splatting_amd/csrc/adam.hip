@@ -226,3 +226,54 @@ hipError_t launch_adam(const BagsAdamArgs& args, const BagsDensifyStats* stats, 
     else hipLaunchKernelGGL(adam_kernel<false>, dim3((unsigned)blocks), dim3(ADAM_BLOCK), 0, st, a);
     return hipGetLastError();
 }
+
+// ---------------------------------------------------------------------------------------------- the camera bank's Adam (bags_pose_adam_step)
+// One thread per (listed row, column) of the (N,9) pose tables, 16 x 9 at most: one workgroup.  Camera rows[v] has three groups
+// (columns 0..3, 4..6, 7..8), each with its own step count, so the constants of adam_element arrive per (row, group) by value.
+// A thread whose group is not enabled returns before it reads anything; rows that are not listed have no thread.
+#define POSE_ADAM_BLOCK 192
+struct PoseAdamDev {
+    float* p; const float* g; float* m; float* v;
+    float w1, b2, w2, eps;
+    int n_rows;
+    int rows[BAGS_MAX_POSE_ROWS];
+    BagsPoseAdamGroup grp[BAGS_MAX_POSE_ROWS][3];
+};
+
+__global__ void __launch_bounds__(POSE_ADAM_BLOCK) pose_adam_kernel(const PoseAdamDev a)
+{
+    const int t = threadIdx.x;
+    if (blockIdx.x != 0 || t >= a.n_rows * 9) return;
+    const int v = t / 9, c = t - 9 * v, grp = c < 4 ? 0 : (c < 7 ? 1 : 2);
+    // selects over the by-value tables (v is not uniform over a wave)
+    int r = a.rows[0];
+    BagsPoseAdamGroup G{0, 0.f, 1.f};
+#pragma unroll
+    for (int k = 0; k < BAGS_MAX_POSE_ROWS; ++k) {
+        if (v == k) {
+            r = a.rows[k];
+            G = grp == 0 ? a.grp[k][0] : (grp == 1 ? a.grp[k][1] : a.grp[k][2]);
+        }
+    }
+    if (!G.enabled) return;
+    const AdamConst k{a.w1, a.b2, a.w2, a.eps, -G.step_size, G.bias_correction2_sqrt};
+    const size_t e = (size_t)r * 9 + c;
+    float p = a.p[e], m = a.m[e], s = a.v[e];
+    adam_element(p, a.g[e], m, s, k);
+    a.p[e] = p; a.m[e] = m; a.v[e] = s;
+}
+
+// validated by the caller (api.hip)
+hipError_t launch_pose_adam(const BagsPoseAdamArgs& args, hipStream_t st)
+{
+    PoseAdamDev a;
+    a.p = args.leaves; a.g = args.grad; a.m = args.exp_avg; a.v = args.exp_avg_sq;
+    a.w1 = (float)(1.0 - args.beta1); a.b2 = (float)args.beta2; a.w2 = (float)(1.0 - args.beta2); a.eps = (float)args.eps;
+    a.n_rows = args.n_rows;
+    for (int k = 0; k < BAGS_MAX_POSE_ROWS; ++k) {
+        a.rows[k] = k < args.n_rows ? args.rows[k] : 0;
+        for (int g = 0; g < 3; ++g) a.grp[k][g] = k < args.n_rows ? args.groups[k][g] : BagsPoseAdamGroup{0, 0.f, 1.f};
+    }
+    hipLaunchKernelGGL(pose_adam_kernel, dim3(1), dim3(POSE_ADAM_BLOCK), 0, st, a);
+    return hipGetLastError();
+}

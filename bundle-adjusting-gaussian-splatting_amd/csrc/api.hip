@@ -660,6 +660,50 @@ int bags_camera_backward(const BagsCamera* c, const float* gV, const float* gM, 
     return BAGS_OK;
 }
 
+// the row list of a camera bank call (BagsPoseBank, BagsPoseAdamArgs): 1..BAGS_MAX_POSE_ROWS distinct rows, each in [0, N)
+static int check_pose_rows(const char* op, int N, int n_rows, const int32_t* rows)
+{
+    if (N < 1) return fail(BAGS_ERR_ARG, "%s: N %d < 1", op, N);
+    if (n_rows < 1 || n_rows > BAGS_MAX_POSE_ROWS) return fail(BAGS_ERR_ARG, "%s: n_rows %d not in 1..%d", op, n_rows, BAGS_MAX_POSE_ROWS);
+    for (int v = 0; v < n_rows; ++v) {
+        if (rows[v] < 0 || rows[v] >= N) return fail(BAGS_ERR_ARG, "%s: rows[%d] = %d is not in [0, %d)", op, v, rows[v], N);
+        for (int u = 0; u < v; ++u)
+            if (rows[u] == rows[v]) return fail(BAGS_ERR_ARG, "%s: row %d is listed twice (rows[%d] and rows[%d])", op, rows[v], u, v);
+    }
+    return BAGS_OK;
+}
+
+static int check_pose_bank(const char* op, const BagsPoseBank* b)
+{
+    if (!b) return fail(BAGS_ERR_ARG, "%s: null struct", op);
+    if (!b->init_quaternion || !b->init_translation || !b->near_far || !b->leaves)
+        return fail(BAGS_ERR_ARG, "%s: init_quaternion / init_translation / near_far / leaves tables must be given", op);
+    return check_pose_rows(op, b->N, b->n_rows, b->rows);
+}
+
+int bags_pose_bank_forward(const BagsPoseBank* b, float* V, float* M, float* K, float* C, void* stream)
+{
+    int rc = check_pose_bank("pose_bank_forward", b);
+    if (rc) return rc;
+    if (!V || !M || !K || !C) return fail(BAGS_ERR_ARG, "pose_bank_forward: null output");
+    HIP_TRY(launch_pose_bank_fwd(*b, V, M, K, C, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
+int bags_pose_bank_backward(const BagsPoseBank* b, const float* gV, const float* gM, const float* gK, const float* gC, float* grad_leaves,
+                            float* g_grot, float* g_gscale, void* stream)
+{
+    int rc = check_pose_bank("pose_bank_backward", b);
+    if (rc) return rc;
+    if (!grad_leaves) return fail(BAGS_ERR_ARG, "pose_bank_backward: null grad_leaves");
+    if (grad_leaves == b->leaves) return fail(BAGS_ERR_ARG, "pose_bank_backward: grad_leaves must not be the leaves table");
+    if (g_grot && !b->global_rotation) return fail(BAGS_ERR_ARG, "pose_bank_backward: g_global_rotation asked for without a global_rotation");
+    if (g_gscale && !b->global_translation_scale)
+        return fail(BAGS_ERR_ARG, "pose_bank_backward: g_global_translation_scale asked for without a global_translation_scale");
+    HIP_TRY(launch_pose_bank_bwd(*b, gV, gM, gK, gC, grad_leaves, g_grot, g_gscale, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- distortion resampling
 static int check_resample(int C, int H, int W, int h, int w, int Hf, int Wf, int Hc, int Wc)
 {
@@ -856,6 +900,16 @@ int bags_adam_step(const BagsAdamArgs* a, const BagsDensifyStats* stats, void* s
     }
     if (a->P == 0) return BAGS_OK;
     HIP_TRY(launch_adam(*a, stats, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
+int bags_pose_adam_step(const BagsPoseAdamArgs* a, void* stream)
+{
+    if (!a) return fail(BAGS_ERR_ARG, "pose_adam: null struct");
+    if (!a->leaves || !a->grad || !a->exp_avg || !a->exp_avg_sq) return fail(BAGS_ERR_ARG, "pose_adam: leaves / grad / exp_avg / exp_avg_sq tables must be given");
+    int rc = check_pose_rows("pose_adam", a->N, a->n_rows, a->rows);
+    if (rc) return rc;
+    HIP_TRY(launch_pose_adam(*a, (hipStream_t)stream));
     return BAGS_OK;
 }
 

@@ -247,6 +247,9 @@ hipError_t launch_camera_bwd(const float* q0, const float* dq, const float* t0, 
                              const float* grot, const float* gscale, float znear, float zfar,
                              const float* gV, const float* gM, const float* gK, const float* gC,
                              float* g_dq, float* g_dt, float* g_fovx, float* g_fovy, float* g_grot, float* g_gscale, hipStream_t st);
+hipError_t launch_pose_bank_fwd(const BagsPoseBank& bank, float* V, float* M, float* K, float* C, hipStream_t st);
+hipError_t launch_pose_bank_bwd(const BagsPoseBank& bank, const float* gV, const float* gM, const float* gK, const float* gC,
+                                float* grad_leaves, float* g_grot, float* g_gscale, hipStream_t st);
 // resample.hip: flow upsample + grid_sample + centre crop + mask in one pass, and the adjoint
 hipError_t launch_resample_fwd(const float* image, int C, int H, int W, const float* ctrl, int h, int w, int Hf, int Wf, int Hc, int Wc,
                                float* out, float* mask, float* flow_out, hipStream_t st);
@@ -272,6 +275,7 @@ hipError_t launch_sh_colors_views_bwd(const BagsShColorsViews& a, const float* c
                                       float* g_xyz, float* const* g_campos, hipStream_t st);
 // adam.hip: torch.optim.Adam step of up to BAGS_ADAM_MAX_GROUPS parameter groups (+ densification statistics) in one launch
 hipError_t launch_adam(const BagsAdamArgs& args, const BagsDensifyStats* stats, hipStream_t st);
+hipError_t launch_pose_adam(const BagsPoseAdamArgs& args, hipStream_t st);
 // densify.hip: densify-and-prune (decide + scan, then map + gather) and the opacity reset
 size_t densify_workspace_bytes(int P);
 hipError_t launch_densify_plan(const BagsDensifyRule& r, void* workspace, u32 host_totals[5], hipStream_t st);

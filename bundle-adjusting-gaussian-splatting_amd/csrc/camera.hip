@@ -10,6 +10,8 @@
 //             viewmatrix = W2C^T; intrinsic = P^T(fovx, fovy, znear, zfar); projmatrix = viewmatrix intrinsic;
 //             campos = -R^-1 t (= inverse(viewmatrix)[3,:3])
 //   backward: the adjoint of exactly those steps, to dq, dt, fovx, fovy (and G, s when given).
+// cam_forward / cam_adjoint state the two once; the single-camera kernels run them in one thread, the camera bank's kernels
+// (second half of this file) in one thread per camera of a step.
 #include "bags_common.h"
 
 struct CamIn {
@@ -60,9 +62,9 @@ __device__ static void cam_forward_mid(const CamIn& in, CamMid& m)
     for (int i = 0; i < 3; ++i) m.c[i] = -(m.Ri[3 * i] * m.t[0] + m.Ri[3 * i + 1] * m.t[1] + m.Ri[3 * i + 2] * m.t[2]);
 }
 
-__global__ void camera_fwd_kernel(CamIn in, float* __restrict__ V, float* __restrict__ M, float* __restrict__ K, float* __restrict__ C)
+// The forward of ONE camera, by one thread: the body of the single-camera kernel and of a bank row alike.
+__device__ __forceinline__ static void cam_forward(const CamIn& in, float* __restrict__ V, float* __restrict__ M, float* __restrict__ K, float* __restrict__ C)
 {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
     CamMid m; cam_forward_mid(in, m);
     float v[16], k[16];
 #pragma unroll
@@ -93,11 +95,11 @@ __global__ void camera_fwd_kernel(CamIn in, float* __restrict__ V, float* __rest
     for (int i = 0; i < 3; ++i) C[i] = m.c[i];
 }
 
-__global__ void camera_bwd_kernel(CamIn in, const float* __restrict__ gV_, const float* __restrict__ gM, const float* __restrict__ gK_,
-                                  const float* __restrict__ gC, float* __restrict__ g_dq, float* __restrict__ g_dt,
-                                  float* __restrict__ g_fovx, float* __restrict__ g_fovy, float* __restrict__ g_grot, float* __restrict__ g_gscale)
+// The adjoint of ONE camera, by one thread.  Upstream gradients may be NULL (= zero), outputs may be NULL (= not wanted).
+__device__ __forceinline__ static void cam_adjoint(const CamIn& in, const float* __restrict__ gV_, const float* __restrict__ gM, const float* __restrict__ gK_,
+                                                   const float* __restrict__ gC, float* __restrict__ g_dq, float* __restrict__ g_dt,
+                                                   float* __restrict__ g_fovx, float* __restrict__ g_fovy, float* __restrict__ g_grot, float* __restrict__ g_gscale)
 {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
     CamMid m; cam_forward_mid(in, m);
     float v[16], k[16], gV[16], gK[16];
 #pragma unroll
@@ -175,6 +177,99 @@ __global__ void camera_bwd_kernel(CamIn in, const float* __restrict__ gV_, const
     }
 }
 
+__global__ void camera_fwd_kernel(CamIn in, float* __restrict__ V, float* __restrict__ M, float* __restrict__ K, float* __restrict__ C)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    cam_forward(in, V, M, K, C);
+}
+
+__global__ void camera_bwd_kernel(CamIn in, const float* __restrict__ gV, const float* __restrict__ gM, const float* __restrict__ gK,
+                                  const float* __restrict__ gC, float* __restrict__ g_dq, float* __restrict__ g_dt,
+                                  float* __restrict__ g_fovx, float* __restrict__ g_fovy, float* __restrict__ g_grot, float* __restrict__ g_gscale)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    cam_adjoint(in, gV, gM, gK, gC, g_dq, g_dt, g_fovx, g_fovy, g_grot, g_gscale);
+}
+
+// ---------------------------------------------------------------------------------------------- the camera bank
+// The leaves of all N cameras sit in (N,9) tables; a call names n_rows <= BAGS_MAX_POSE_ROWS of them in a list that arrives by value
+// in the kernel arguments.  Thread v < n_rows of workgroup 0 builds camera rows[v]'s CamIn from the tables and runs the very
+// functions above, so a bank row gets the single-camera kernel's bits.
+struct PoseBankDev {
+    const float* q0; const float* t0; const float* near_far; const float* leaves;      // (N,4) (N,3) (N,2) (N,9)
+    const float* grot; const float* gscale;
+    int N, n_rows;
+    int rows[BAGS_MAX_POSE_ROWS];
+};
+
+#define POSE_LEAVES 9
+#define POSE_FILL_BLOCK 256
+
+__device__ __forceinline__ static CamIn pose_bank_row(const PoseBankDev& b, const int v)
+{
+    int r = b.rows[0];                                         // selects over the by-value list: no indexed read of the arguments
+#pragma unroll
+    for (int k = 1; k < BAGS_MAX_POSE_ROWS; ++k)
+        if (v == k) r = b.rows[k];
+    const float* leaf = b.leaves + (size_t)r * POSE_LEAVES;
+    return CamIn{b.q0 + (size_t)r * 4, leaf, b.t0 + (size_t)r * 3, leaf + 4, leaf + 7, leaf + 8, b.grot, b.gscale,
+                 b.near_far[(size_t)r * 2], b.near_far[(size_t)r * 2 + 1]};
+}
+
+// one workgroup of 64: thread v < n_rows is camera rows[v]
+__global__ void __launch_bounds__(64) pose_bank_fwd_kernel(const PoseBankDev b, float* __restrict__ V, float* __restrict__ M, float* __restrict__ K,
+                                                           float* __restrict__ C)
+{
+    const int v = threadIdx.x;
+    if (blockIdx.x != 0 || v >= b.n_rows) return;
+    const CamIn in = pose_bank_row(b, v);
+    cam_forward(in, V + 16 * v, M + 16 * v, K + 16 * v, C + 3 * v);
+}
+
+// ceil(N * 9 / 256) workgroups of 256.  Every thread owns one element of grad_leaves and writes a zero unless its row is listed;
+// thread v < n_rows of workgroup 0 also runs the adjoint of camera rows[v] and writes that row.  The two sets of addresses are
+// disjoint, so no order between them is needed.  The alignment gradients of the rows go to LDS, and thread 0 adds them up in
+// row-list order v = 0, 1, ...: an fp32 left fold, no atomics.
+__global__ void __launch_bounds__(POSE_FILL_BLOCK) pose_bank_bwd_kernel(const PoseBankDev b, const float* __restrict__ gV, const float* __restrict__ gM,
+                                                                        const float* __restrict__ gK, const float* __restrict__ gC,
+                                                                        float* __restrict__ grad_leaves, float* __restrict__ g_grot,
+                                                                        float* __restrict__ g_gscale)
+{
+    __shared__ float part[BAGS_MAX_POSE_ROWS][10];             // per listed row: g_grot 0..8 | g_gscale 9
+    if (blockIdx.x == 0) {
+        const int v = threadIdx.x;
+        if (v < b.n_rows) {
+            const CamIn in = pose_bank_row(b, v);
+            float* g = grad_leaves + (size_t)(in.dq - b.leaves);                // this camera's row of grad_leaves
+            cam_adjoint(in, gV ? gV + 16 * v : nullptr, gM ? gM + 16 * v : nullptr, gK ? gK + 16 * v : nullptr, gC ? gC + 3 * v : nullptr,
+                        g, g + 4, g + 7, g + 8, g_grot ? &part[v][0] : nullptr, g_gscale ? &part[v][9] : nullptr);
+        }
+        __syncthreads();
+        if (v == 0) {
+            if (g_grot) {
+#pragma unroll
+                for (int i = 0; i < 9; ++i) {
+                    float acc = part[0][i];
+                    for (int k = 1; k < b.n_rows; ++k) acc += part[k][i];
+                    g_grot[i] = acc;
+                }
+            }
+            if (g_gscale) {
+                float acc = part[0][9];
+                for (int k = 1; k < b.n_rows; ++k) acc += part[k][9];
+                g_gscale[0] = acc;
+            }
+        }
+    }
+    const size_t e = (size_t)blockIdx.x * POSE_FILL_BLOCK + threadIdx.x;
+    if (e >= (size_t)b.N * POSE_LEAVES) return;
+    const int r = (int)(e / POSE_LEAVES);
+    bool listed = false;
+#pragma unroll
+    for (int k = 0; k < BAGS_MAX_POSE_ROWS; ++k) listed |= (k < b.n_rows && b.rows[k] == r);
+    if (!listed) grad_leaves[e] = 0.f;
+}
+
 hipError_t launch_camera_fwd(const float* q0, const float* dq, const float* t0, const float* dt, const float* fovx, const float* fovy,
                              const float* grot, const float* gscale, float znear, float zfar,
                              float* V, float* M, float* K, float* C, hipStream_t st)
@@ -191,5 +286,28 @@ hipError_t launch_camera_bwd(const float* q0, const float* dq, const float* t0, 
 {
     CamIn in{q0, dq, t0, dt, fovx, fovy, grot, gscale, znear, zfar};
     hipLaunchKernelGGL(camera_bwd_kernel, dim3(1), dim3(64), 0, st, in, gV, gM, gK, gC, g_dq, g_dt, g_fovx, g_fovy, g_grot, g_gscale);
+    return hipGetLastError();
+}
+
+static PoseBankDev pose_bank_dev(const BagsPoseBank& a)
+{
+    PoseBankDev b{a.init_quaternion, a.init_translation, a.near_far, a.leaves, a.global_rotation, a.global_translation_scale, a.N, a.n_rows, {}};
+    for (int k = 0; k < BAGS_MAX_POSE_ROWS; ++k) b.rows[k] = k < a.n_rows ? a.rows[k] : -1;
+    return b;
+}
+
+// the bank struct is validated by the caller (api.hip): rows distinct and in range, tables given
+hipError_t launch_pose_bank_fwd(const BagsPoseBank& a, float* V, float* M, float* K, float* C, hipStream_t st)
+{
+    hipLaunchKernelGGL(pose_bank_fwd_kernel, dim3(1), dim3(64), 0, st, pose_bank_dev(a), V, M, K, C);
+    return hipGetLastError();
+}
+
+hipError_t launch_pose_bank_bwd(const BagsPoseBank& a, const float* gV, const float* gM, const float* gK, const float* gC,
+                                float* grad_leaves, float* g_grot, float* g_gscale, hipStream_t st)
+{
+    const size_t blocks = ((size_t)a.N * POSE_LEAVES + POSE_FILL_BLOCK - 1) / POSE_FILL_BLOCK;
+    hipLaunchKernelGGL(pose_bank_bwd_kernel, dim3((unsigned)blocks), dim3(POSE_FILL_BLOCK), 0, st, pose_bank_dev(a), gV, gM, gK, gC,
+                       grad_leaves, g_grot, g_gscale);
     return hipGetLastError();
 }

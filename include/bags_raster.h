@@ -320,6 +320,33 @@ int bags_camera_backward(const BagsCamera* cam, const float* g_viewmatrix, const
                          const float* g_campos, float* g_delta_quaternion, float* g_delta_translation, float* g_fovx,
                          float* g_fovy, float* g_global_rotation, float* g_global_translation_scale, void* stream);
 
+/* The camera bank: the pose leaves of all N training cameras in device tables, and the chain above for the n_rows <=
+ * BAGS_MAX_POSE_ROWS cameras of one step in ONE launch each way (csrc/camera.hip).  Row v of every output belongs to camera
+ * rows[v] and holds the bits bags_camera_forward / bags_camera_backward give for that camera's leaves.  The row list travels by
+ * value; nothing is uploaded, nothing allocated, no host synchronisation, no atomics.  rows are distinct and each in [0, N). */
+#define BAGS_MAX_POSE_ROWS 16
+typedef struct BagsPoseBank {
+    int32_t N;                       /* cameras in the bank, >= 1 */
+    const float* init_quaternion;    /* (N,4) w,x,y,z */
+    const float* init_translation;   /* (N,3) */
+    const float* near_far;           /* (N,2) znear, zfar per camera, 0 < znear < zfar */
+    const float* leaves;             /* (N,9): delta_quaternion 0..3 | delta_translation 4..6 | fovx 7 | fovy 8 */
+    const float* global_rotation;    /* (3,3) row-major or NULL, shared by the rows of a call */
+    const float* global_translation_scale;   /* scalar or NULL */
+    int32_t n_rows;                  /* 1..BAGS_MAX_POSE_ROWS */
+    int32_t rows[BAGS_MAX_POSE_ROWS];
+} BagsPoseBank;
+/* viewmatrix, projmatrix, intrinsic: (n_rows,4,4); campos: (n_rows,3) */
+int bags_pose_bank_forward(const BagsPoseBank* bank, float* viewmatrix, float* projmatrix, float* intrinsic, float* campos,
+                           void* stream);
+/* Upstream gradients (n_rows,...) may be NULL (= zero).  grad_leaves (N,9): EVERY element is written by this call, the rows not
+ * listed as exact zeros (no fill launch is needed before it).  g_global_rotation (3,3) and g_global_translation_scale (1) may be
+ * NULL (= not wanted); each needs its input in the bank struct.  They are the sum over the listed rows in row-list order
+ * v = 0, 1, ...: an fp32 left fold by one thread. */
+int bags_pose_bank_backward(const BagsPoseBank* bank, const float* g_viewmatrix, const float* g_projmatrix, const float* g_intrinsic,
+                            const float* g_campos, float* grad_leaves, float* g_global_rotation, float* g_global_translation_scale,
+                            void* stream);
+
 /* Image-space distortion resampling: the apply2gt == False branch of apply_distortion
  * (utils/util_distortion.py:271-311, call site train.py:255-263) in one pass each way:
  *   flow  = interpolate(control flow (h,w,2) -> (flow_H, flow_W), bilinear, align_corners=False)
@@ -448,6 +475,29 @@ typedef struct BagsDensifyStats {
 } BagsDensifyStats;
 /* stats may be NULL.  P == 0 is a successful no-op. */
 int bags_adam_step(const BagsAdamArgs* args, const BagsDensifyStats* stats, void* stream);
+
+/* The per-camera Adam of a camera bank (BagsPoseBank above) in ONE launch for the n_rows cameras of a step: every camera has its
+ * own torch.optim.Adam over three groups -- rotation (columns 0..3 of its row), translation (4..6), fov (7..8) -- as the reference
+ * keeps them per camera (train.py steps the first two under --opt_cam, the fov pair under --opt_intrinsic), stepped only when the
+ * camera is listed.  The update per element is the one of BagsAdamArgs, operation for operation.  groups[v][g] belongs to camera
+ * rows[v]: step_size and bias_correction2_sqrt come from that (camera, group)'s OWN step count, formed by the caller in double.
+ * A column whose group is not enabled, and every row not listed, is neither read nor written.  rows as for BagsPoseBank. */
+typedef struct BagsPoseAdamGroup {
+    int32_t enabled;                 /* 0: the group's columns of this row are left alone */
+    float step_size;                 /* lr / (1 - beta1^step) */
+    float bias_correction2_sqrt;     /* sqrt(1 - beta2^step) */
+} BagsPoseAdamGroup;
+typedef struct BagsPoseAdamArgs {
+    int32_t N, n_rows;               /* n_rows in 1..BAGS_MAX_POSE_ROWS */
+    float* leaves;                   /* (N,9), updated in place */
+    const float* grad;               /* (N,9) */
+    float* exp_avg;                  /* (N,9), updated in place */
+    float* exp_avg_sq;               /* (N,9), updated in place */
+    double beta1, beta2, eps;
+    int32_t rows[BAGS_MAX_POSE_ROWS];
+    BagsPoseAdamGroup groups[BAGS_MAX_POSE_ROWS][3];
+} BagsPoseAdamArgs;
+int bags_pose_adam_step(const BagsPoseAdamArgs* args, void* stream);
 
 /* Densify-and-prune of the Gaussian set and the opacity reset (csrc/densify.hip): GaussianModel.densify_and_prune
  * (scene/gaussian_model.py:393-447, called from train.py:381-386) with the optimizer surgery of cat_tensors_to_optimizer
