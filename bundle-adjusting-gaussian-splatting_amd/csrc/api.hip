@@ -472,8 +472,7 @@ int bags_backward_ex(const BagsSettings* s, const BagsInputs* in, const BagsStat
     }
     if (a->phase == BAGS_BWD_BLEND) return BAGS_OK;          // the per-Gaussian half comes with a second call (BAGS_BWD_PREPROCESS)
     int nblocks = 0;
-    { ProfScope ps(ST_PRE_BWD, st, true); HIP_TRY(launch_preprocess_bwd(*s, *in, v.g, nullptr, w.partials, w.pose_slab, &nblocks, *a, st, v.binned, dense ? w.live_map : nullptr,
-                                                                     extra)); }
+    { ProfScope ps(ST_PRE_BWD, st, true); HIP_TRY(launch_preprocess_bwd(*s, *in, v.g, w.partials, w.pose_slab, &nblocks, *a, st, v.binned, dense ? w.live_map : nullptr, extra)); }
     DEBUG_SYNC(s, st, "preprocess_bwd");
     { ProfScope ps(ST_POSE_REDUCE, st, true); HIP_TRY(launch_pose_reduce(w.pose_slab, nblocks, *a, st)); }
     DEBUG_SYNC(s, st, "pose_reduce");

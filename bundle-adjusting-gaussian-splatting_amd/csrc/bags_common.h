@@ -64,6 +64,31 @@ __device__ __forceinline__ float wave_total_f(float x)
     return x;
 }
 
+// Column t of a slab of nblocks rows (one per workgroup of the kernel that wrote it, `stride` floats apart) summed in fp64 by one
+// 256-thread workgroup: thread i adds rows i, i + 256, ... in row order, the 64 partial sums of a wave are added by a fixed shuffle
+// tree, the four wave sums in wave order, so the result is deterministic.  The sum is returned in thread 0 (the others' is the same
+// and not meant to be used).  Every thread has its 8 loads of a trip in flight at once; rows past the end INSIDE the batch are read
+// at a clamped index and dropped afterwards: a remainder loop of single loads -- 1954 rows are 7.6 per thread, so most threads took
+// it -- was seven dependent round trips, 6.5 us of a kernel that needs one.  No `in range ? load : 0`: the compiler makes that a
+// branch per load with a wait behind each.
+__device__ __forceinline__ double slab_column_sum(const float* __restrict__ slab, const int nblocks, const int stride, const int t)
+{
+    __shared__ double wsum[4];
+    double acc = 0.0;
+    for (int b = threadIdx.x; b < nblocks; b += 8 * 256) {
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = slab[(size_t)min(b + u * 256, nblocks - 1) * stride + t];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) acc += (b + u * 256 < nblocks) ? (double)v[u] : 0.0;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    return ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+}
+
 // ---- tile masks of small rectangles (GeomView::keep) ------------------------------------------------------
 // A rectangle of at most 8 x 8 tiles carries a 64-bit mask of the tiles it emits, bit ry * 8 + rx; a larger one emits all.
 __device__ __forceinline__ bool rect_small(int w, int h) { return w <= 8 && h <= 8; }
@@ -196,6 +221,8 @@ static inline void launch_k(void (*kernel)(KArgs...), dim3 grid, dim3 block, siz
     }
 }
 #define LAUNCH_K(kernel, grid, block, lds, st, ...) launch_k(kernel, grid, block, lds, st, __VA_ARGS__)
+// a run-time bool as a compile-time one: f(std::true_type{}) or f(std::false_type{}); nested, it picks a kernel's template instance
+template <typename F> static inline auto with_bool(bool b, F f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
 
 int radix_items_for(long long n);
 int radix_blocks_for(long long n);
@@ -227,9 +254,9 @@ hipError_t launch_blend_bwd(const BagsSettings& s, const GeomView& g, const BinV
                             const float* grad_depth = nullptr, const float* grad_weights = nullptr);   // BagsExtraGrads (ABI 11)
 bool bwd_dense_mode(long long n_records, int T, int dense_per_tile);      // does a backward of this size run in dense-scene mode?
 // extra: the records carry dL/dz in their twelfth float (blend_bwd ran with BagsExtraGrads): it is summed and added to dL/dtzs
-hipError_t launch_preprocess_bwd(const BagsSettings& s, const BagsInputs& in, const GeomView& g, const int32_t* radii_or_null,
-                                 const float* partials, float* pose_slab, int* nblocks_out, const BagsBackwardArgs& a, hipStream_t st,
-                                 bool binned, const unsigned char* live_map = nullptr, bool extra = false);
+hipError_t launch_preprocess_bwd(const BagsSettings& s, const BagsInputs& in, const GeomView& g, const float* partials, float* pose_slab,
+                                 int* nblocks_out, const BagsBackwardArgs& a, hipStream_t st, bool binned,
+                                 const unsigned char* live_map = nullptr, bool extra = false);
 hipError_t launch_pose_reduce(const float* pose_slab, int nblocks, const BagsBackwardArgs& a, hipStream_t st);
 hipError_t launch_sh_grad_from_views(int P, int M, int deg, const float* means3D, const BagsShViews& views, float* g_shs, float* g_shs_rest,
                                      int accumulate, hipStream_t st);

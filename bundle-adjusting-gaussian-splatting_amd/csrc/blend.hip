@@ -927,11 +927,6 @@ hipError_t launch_blend_bwd(const BagsSettings& s, const GeomView& g, const BinV
                   (const u32*)(binned ? nullptr : g.inst_off), (const u32*)g.block_base, (const float*)s.bg, (const float*)im.final_T,  \
                   (const u32*)im.n_contrib, grad_color, partials, (int)(compact ? 1 : 0), (const uint4*)im.tile_aux, live_map,                 \
                   grad_depth, grad_weights
-#define BWD_LAUNCH_X_(ABS_, CMP_, SPARSE_, EXTRA_)                                                                                   \
-    do { if (ev_start || ev_stop) hipExtLaunchKernelGGL((blend_bwd_scan_kernel<ABS_, CMP_, SPARSE_, EXTRA_>), dim3(grid), dim3(256), 0, \
-                                                        st, ev_start, ev_stop, 0, BWD_ARGS_);                                         \
-         else LAUNCH_K((blend_bwd_scan_kernel<ABS_, CMP_, SPARSE_, EXTRA_>), dim3(grid), dim3(256), 0, st, BWD_ARGS_); } while (0)
-#define BWD_LAUNCH_(ABS_, CMP_, SPARSE_) do { if (extra) BWD_LAUNCH_X_(ABS_, CMP_, SPARSE_, true); else BWD_LAUNCH_X_(ABS_, CMP_, SPARSE_, false); } while (0)
     // The chunk geometry follows the SCENE, not the dense-scene decision: forcing the dense-scene mode on or off leaves the arithmetic
     // untouched, so the two modes stay bit-identical (tests, tools/fuzz_paths.py --cross-dense)
     // (stock tile rule on the tile-binned path: the chunks are staged from the compacted list of record holders -- ~60 % of the list's
@@ -941,12 +936,11 @@ hipError_t launch_blend_bwd(const BagsSettings& s, const GeomView& g, const BinV
 #endif
     const long long per_tile_x5 = compact ? n_records * COMPACT_DENSITY_NUM : n_records * 5;
     const bool sparse = per_tile_x5 <= 5ll * BWD_SPARSE_PER_TILE * T;
-#define BWD_LAUNCH(ABS_, CMP_) do { if (sparse) BWD_LAUNCH_(ABS_, CMP_, true); else BWD_LAUNCH_(ABS_, CMP_, false); } while (0)
-    if (want_abs) { if (compact) BWD_LAUNCH(true, true); else BWD_LAUNCH(true, false); }
-    else          { if (compact) BWD_LAUNCH(false, true); else BWD_LAUNCH(false, false); }
-#undef BWD_LAUNCH
-#undef BWD_LAUNCH_
-#undef BWD_LAUNCH_X_
+    with_bool(want_abs, [&](auto ABS) { with_bool(compact, [&](auto CMP) { with_bool(sparse, [&](auto SPARSE) { with_bool(extra, [&](auto EXTRA) {
+        const auto kernel = blend_bwd_scan_kernel<decltype(ABS)::value, decltype(CMP)::value, decltype(SPARSE)::value, decltype(EXTRA)::value>;
+        if (ev_start || ev_stop) hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, st, ev_start, ev_stop, 0, BWD_ARGS_);
+        else LAUNCH_K(kernel, dim3(grid), dim3(256), 0, st, BWD_ARGS_);
+    }); }); }); });
 #undef BWD_ARGS_
     return hipGetLastError();
 }

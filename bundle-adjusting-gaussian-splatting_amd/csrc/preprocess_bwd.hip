@@ -13,6 +13,7 @@
 #include "bags_common.h"
 #include "sh_basis.h"
 #include "projection.h"
+#include "sh_rows.h"
 
 // K8a: each Gaussian's consecutive partial records (written by blend_bwd at its emission slots) summed in list order.
 // Light kernel (high occupancy, two records in flight per lane): the record stream is the only traffic.  Gaussians with
@@ -152,6 +153,17 @@ __device__ __forceinline__ void pose_write_out(const int t, const float val, flo
     }
 }
 
+// The SH colour path's view direction of a Gaussian: 1 / |p - campos| and the unit vector.  The ONE statement of it for K9 and for the
+// sh_grad_from_views kernels below, whose basis -- and so whose gradient rows -- must carry K9's bits: one function in one file
+// compiled with one set of flags.
+struct ShDir { float il, ux, uy, uz; };
+__device__ __forceinline__ ShDir sh_dir(const float x, const float y, const float z, const float cpx, const float cpy, const float cpz)
+{
+    const float ex = x - cpx, ey = y - cpy, ez = z - cpz;
+    const float il = 1.0f / sqrtf(ex * ex + ey * ey + ez * ez);
+    return {il, ex * il, ey * il, ez * il};
+}
+
 // ACCUM (BagsBackwardArgs.accumulate): the seven Gaussian-parameter gradients are ADDED to what their buffers hold (several
 // views of one step accumulate in place: no separate add pass per view); means2D / densify / pose outputs are overwritten.
 // EXTRA: the records' twelfth float (dL/dz from the depth cotangent, BagsExtraGrads) is summed and added to dL/dtzs.
@@ -194,7 +206,7 @@ preprocess_bwd_kernel(int P, int M, int deg, int W, int H, float tanfovx, float 
     // the SH rows themselves came IN through the same 48 KB -- since round 3 the forward leaves d(colour)/d(direction) behind,
     // 48 bytes per Gaussian, and the backward does not read the 192-byte row a second time).  With 108 VGPRs that makes four
     // workgroups per CU (three before, both by registers and by LDS).
-    __shared__ float srow[256][20];                     // basis[16] (zero beyond the active degree), dL/dcolour[3], pad
+    __shared__ float srow[256][SHR_W];                  // sh_rows.h: basis[16] (zero beyond the active degree), dL/dcolour[3], pad
     const bool stage = (M == 16) && (colors_precomp == nullptr) && (shs != nullptr) && (g_shs != nullptr);      // uniform
     const size_t base4 = (size_t)blockIdx.x * (256 * 12), lim4 = (size_t)P * 12;
 
@@ -425,9 +437,8 @@ preprocess_bwd_kernel(int P, int M, int deg, int W, int H, float tanfovx, float 
             if (cl & 4u) drgb[2] = 0.f;
             // factored SH gradient (BagsBackwardArgs.grad_dldc): the row basis x dL/dcolour is formed later, for all views of the step at once
             if (g_dldc) { g_dldc[3 * (size_t)i] = drgb[0]; g_dldc[3 * (size_t)i + 1] = drgb[1]; g_dldc[3 * (size_t)i + 2] = drgb[2]; }
-            const float ex = x - cpx, ey = y - cpy, ez = z - cpz;
-            const float il = 1.0f / sqrtf(ex * ex + ey * ey + ez * ez);
-            const float ux_ = ex * il, uy_ = ey * il, uz_ = ez * il;
+            const ShDir dir = sh_dir(x, y, z, cpx, cpy, cpz);
+            const float il = dir.il, ux_ = dir.ux, uy_ = dir.uy, uz_ = dir.uz;
             float bs[16];
             sh_basis(deg, ux_, uy_, uz_, bs);
             const int nb = (deg + 1) * (deg + 1);
@@ -440,14 +451,7 @@ preprocess_bwd_kernel(int P, int M, int deg, int W, int H, float tanfovx, float 
             const float ddz = mj[6] * drgb[0] + mj[7] * drgb[1] + mj[8] * drgb[2];
             // dL/dsh[t][c] = basis_t dL/dcolour_c: no input row needed
             if (M == 16) {
-                if (stage) {
-                    float4* d4 = reinterpret_cast<float4*>(&srow[threadIdx.x][0]);
-                    d4[0] = make_float4(bs[0], nb > 1 ? bs[1] : 0.f, nb > 1 ? bs[2] : 0.f, nb > 1 ? bs[3] : 0.f);
-                    d4[1] = make_float4(nb > 4 ? bs[4] : 0.f, nb > 4 ? bs[5] : 0.f, nb > 4 ? bs[6] : 0.f, nb > 4 ? bs[7] : 0.f);
-                    d4[2] = make_float4(nb > 4 ? bs[8] : 0.f, nb > 9 ? bs[9] : 0.f, nb > 9 ? bs[10] : 0.f, nb > 9 ? bs[11] : 0.f);
-                    d4[3] = make_float4(nb > 9 ? bs[12] : 0.f, nb > 9 ? bs[13] : 0.f, nb > 9 ? bs[14] : 0.f, nb > 9 ? bs[15] : 0.f);
-                    d4[4] = make_float4(drgb[0], drgb[1], drgb[2], 0.f);
-                }
+                if (stage) shr_stage(&srow[threadIdx.x][0], bs, nb, drgb[0], drgb[1], drgb[2]);
             } else if (gsh)
             for (int t = 0; t < M; ++t) {
                 const bool on = t < nb;
@@ -467,11 +471,7 @@ preprocess_bwd_kernel(int P, int M, int deg, int W, int H, float tanfovx, float 
         float* gsh = g_shs_rest ? g_shs + 3 * (size_t)i : g_shs + (size_t)i * M * 3;
         float* gsr = g_shs_rest ? g_shs_rest + (size_t)i * (M - 1) * 3 : gsh + 3;
         if (M == 16) {
-            if (stage) {
-                float4* d4 = reinterpret_cast<float4*>(&srow[threadIdx.x][0]);
-#pragma unroll
-                for (int t = 0; t < 5; ++t) d4[t] = make_float4(0.f, 0.f, 0.f, 0.f);
-            }
+            if (stage) shr_stage_zero(&srow[threadIdx.x][0]);
         } else if (!ACCUM) {
             gsh[0] = gsh[1] = gsh[2] = 0.f;
             for (int t = 0; t < 3 * (M - 1); ++t) gsr[t] = 0.f;
@@ -479,33 +479,11 @@ preprocess_bwd_kernel(int P, int M, int deg, int W, int H, float tanfovx, float 
     }
     if (stage && g_shs_rest) {                       // ... as two spans: 256 DC triples (3 KB) and 256 rows of 45 floats (45 KB)
         __syncthreads();
-        auto span = [&](float* __restrict__ out, const u32 R, const u32 t0, const u32 rounds) {      // R floats per row, first coefficient t0
-            const size_t first = (size_t)blockIdx.x * 256u * R, total = (size_t)P * R;
-            for (u32 k = 0; k < rounds; ++k) {
-                const u32 el = k * 256u + threadIdx.x;           // float4 number inside the workgroup's span
-                if (el * 4u >= 256u * R) break;
-                float o4[4]; size_t gi[4];
-#pragma unroll
-                for (u32 u = 0; u < 4; ++u) {
-                    const u32 f = el * 4u + u, row = f / R, r = f - row * R, t = t0 + r / 3u, c = r - 3u * (r / 3u);
-                    o4[u] = srow[row][t] * srow[row][16u + c];
-                    gi[u] = first + f;
-                }
-                if (gi[3] < total) {
-                    float4* d = reinterpret_cast<float4*>(out + gi[0]);
-                    float4 o = make_float4(o4[0], o4[1], o4[2], o4[3]);
-                    if (ACCUM) { const float4 old = *d; o.x += old.x; o.y += old.y; o.z += old.z; o.w += old.w; }
-                    *d = o;
-                } else {
-#pragma unroll
-                    for (u32 u = 0; u < 4; ++u)
-                        if (gi[u] < total) out[gi[u]] = ACCUM ? out[gi[u]] + o4[u] : o4[u];
-                }
-            }
-        };
-        span(g_shs, 3u, 0u, 1u);
-        span(g_shs_rest, 45u, 1u, 12u);
+        constexpr ShrMode MODE = ACCUM ? SHR_PRODUCT_ADD : SHR_PRODUCT;
+        shr_span<256u, 3u, 0u, MODE>(srow, g_shs, P);
+        shr_span<256u, 45u, 1u, MODE, true>(srow, g_shs_rest, P);
     } else if (stage) {                              // the workgroup's gradient rows leave as whole lines
+        // (its own spelling of shr_span<256, 48, 0, MODE>: through the header this pass costs the kernel registers, profiles/sh_rows/NOTES.md)
         __syncthreads();
         float4* g4g = reinterpret_cast<float4*>(g_shs);
 #pragma unroll
@@ -569,101 +547,62 @@ preprocess_bwd_kernel(int P, int M, int deg, int W, int H, float tanfovx, float 
     }
 }
 
-// rows -> the five pose tensors, summed in fp64.  One workgroup per slab column (35 used): thread t adds rows t, t + 256, ...
-// in row order, the 64 partial sums of a wave are added by a fixed shuffle tree, the four wave sums in wave order, so the
-// result is deterministic.  (One 1024-thread workgroup for all 40 columns took 10.5 us: 78 dependent-latency-bound loads
-// per thread; here every thread has its 8 loads in flight at once.)
+// rows -> the five pose tensors, summed in fp64 in a fixed order (bags_common.h: slab_column_sum).  One workgroup per slab column
+// (35 used).  (One 1024-thread workgroup for all 40 columns took 10.5 us: 78 dependent-latency-bound loads per thread; here every
+// thread has its 8 loads in flight at once.)
 __global__ void __launch_bounds__(256)
 pose_reduce_kernel(const float* __restrict__ slab, int nblocks, float* __restrict__ g_view, float* __restrict__ g_proj,
                    float* __restrict__ g_intr, float* __restrict__ g_campos, float* __restrict__ g_shift)
 {
-    __shared__ double wsum[4];
     const int t = blockIdx.x;                            // slab column
-    double acc = 0.0;
-    int b = threadIdx.x;
-    // (rows past the end INSIDE the batch, read at a clamped index and dropped afterwards: a remainder loop of single loads -- 1954 rows are
-    // 7.6 per thread, so most threads took it -- was seven dependent round trips, 6.5 us of a kernel that needs one.  No `in range ? load : 0`:
-    // the compiler makes that a branch per load with a wait behind each.  The order of the additions is unchanged.)
-    for (; b < nblocks; b += 8 * 256) {
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = slab[(size_t)min(b + u * 256, nblocks - 1) * POSE_VALS + t];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) acc += (b + u * 256 < nblocks) ? (double)v[u] : 0.0;
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-    __syncthreads();
+    const double sum = slab_column_sum(slab, nblocks, POSE_VALS, t);
     if (threadIdx.x != 0) return;
-    const float val = (float)(((wsum[0] + wsum[1]) + wsum[2]) + wsum[3]);
-    pose_write_out(t, val, g_view, g_proj, g_intr, g_campos, g_shift);
+    pose_write_out(t, (float)sum, g_view, g_proj, g_intr, g_campos, g_shift);
 }
 
-hipError_t launch_preprocess_bwd(const BagsSettings& s, const BagsInputs& in, const GeomView& g, const int32_t*,
-                                 const float* partials_records, float* pose_slab, int* nblocks_out, const BagsBackwardArgs& a,
-                                 hipStream_t st, bool binned, const unsigned char* live_map, bool extra)
+template <bool COV, bool ACC, bool LIVE, bool EXTRA>
+static hipError_t pre_bwd_launch(const BagsSettings& s, const BagsInputs& in, const GeomView& g, const float* partials, float* pose_slab,
+                                 const BagsBackwardArgs& a, hipStream_t st, bool binned, const unsigned char* live_map)
 {
     const int P = in.P;
-    const int nb = cdiv(P, 256);
-    *nblocks_out = nb;
-    if (P == 0) return hipSuccess;
-    const float* partials = partials_records;
-#define PRE_BWD_LAUNCH_X(COV, EXTRA_) LAUNCH_K((preprocess_bwd_kernel<COV, ACC_, LIVE_, EXTRA_>), dim3(nb), dim3(256), 0, st, P, s.sh_coeffs, s.sh_degree, s.image_width, \
-                       s.image_height, s.tanfovx, s.tanfovy, s.scale_modifier, (s.clamp_grad == BAGS_CLAMP_GRAD_EXACT) ? 0 : 1, \
-                       (s.conic_grad == BAGS_CONIC_GRAD_EXACT) ? 0 : 1, in.means3D, in.shift_factors, in.shs, \
-                       in.colors_precomp, in.scales, in.rotations, in.cov3D_precomp, s.viewmatrix, s.projmatrix, \
-                       s.intrinsic, s.campos, in.opacities, g.rec_count, binned ? nullptr : g.inst_off, g.local_off, g.block_base, \
-                       binned_per_block(P), g.shjac, partials, live_map, \
-                       pose_slab, a.grad_means3D, a.grad_means2D, a.grad_means2D_densify, a.grad_shs, in.shs_rest ? a.grad_shs_rest : nullptr, \
-                       (in.shs && !in.colors_precomp) ? a.grad_dldc : nullptr, \
-                       a.grad_colors_precomp, a.grad_opacities, a.grad_scales, a.grad_rotations, a.grad_cov3D_precomp);
-#define PRE_BWD_LAUNCH(COV) if (extra) { PRE_BWD_LAUNCH_X(COV, true) } else { PRE_BWD_LAUNCH_X(COV, false) }
-#define PRE_BWD_PICK if (in.cov3D_precomp) { PRE_BWD_LAUNCH(true) } else { PRE_BWD_LAUNCH(false) }
-    if (live_map) {
-#define LIVE_ true
-        if (a.accumulate) {
-#define ACC_ true
-            PRE_BWD_PICK
-#undef ACC_
-        } else {
-#define ACC_ false
-            PRE_BWD_PICK
-#undef ACC_
-        }
-#undef LIVE_
-    } else {
-#define LIVE_ false
-        if (a.accumulate) {
-#define ACC_ true
-            PRE_BWD_PICK
-#undef ACC_
-        } else {
-#define ACC_ false
-            PRE_BWD_PICK
-#undef ACC_
-        }
-#undef LIVE_
-    }
-#undef PRE_BWD_PICK
-#undef PRE_BWD_LAUNCH
-#undef PRE_BWD_LAUNCH_X
+    LAUNCH_K((preprocess_bwd_kernel<COV, ACC, LIVE, EXTRA>), dim3(cdiv(P, 256)), dim3(256), 0, st, P, s.sh_coeffs, s.sh_degree, s.image_width,
+             s.image_height, s.tanfovx, s.tanfovy, s.scale_modifier, (s.clamp_grad == BAGS_CLAMP_GRAD_EXACT) ? 0 : 1,
+             (s.conic_grad == BAGS_CONIC_GRAD_EXACT) ? 0 : 1, in.means3D, in.shift_factors, in.shs,
+             in.colors_precomp, in.scales, in.rotations, in.cov3D_precomp, s.viewmatrix, s.projmatrix,
+             s.intrinsic, s.campos, in.opacities, g.rec_count, binned ? nullptr : g.inst_off, g.local_off, g.block_base,
+             binned_per_block(P), g.shjac, partials, live_map,
+             pose_slab, a.grad_means3D, a.grad_means2D, a.grad_means2D_densify, a.grad_shs, in.shs_rest ? a.grad_shs_rest : nullptr,
+             (in.shs && !in.colors_precomp) ? a.grad_dldc : nullptr,
+             a.grad_colors_precomp, a.grad_opacities, a.grad_scales, a.grad_rotations, a.grad_cov3D_precomp);
     return hipGetLastError();
 }
 
+hipError_t launch_preprocess_bwd(const BagsSettings& s, const BagsInputs& in, const GeomView& g, const float* partials, float* pose_slab,
+                                 int* nblocks_out, const BagsBackwardArgs& a, hipStream_t st, bool binned, const unsigned char* live_map,
+                                 bool extra)
+{
+    *nblocks_out = cdiv(in.P, 256);
+    if (in.P == 0) return hipSuccess;
+    return with_bool(in.cov3D_precomp != nullptr, [&](auto COV) { return with_bool(a.accumulate != 0, [&](auto ACC) {
+        return with_bool(live_map != nullptr, [&](auto LIVE) { return with_bool(extra, [&](auto EXTRA) {
+            return pre_bwd_launch<decltype(COV)::value, decltype(ACC)::value, decltype(LIVE)::value, decltype(EXTRA)::value>(
+                s, in, g, partials, pose_slab, a, st, binned, live_map); }); }); }); });
+}
+
 // ---- (ABI 10) SH-gradient rows of several views from their factored form.  One 256-thread workgroup per SHV_G = 128 Gaussians, view
-// after view: threads 0..127 form their Gaussian's basis at the view's direction (the very expressions preprocess_bwd_kernel uses: same
-// file, same flags, same bits) and stage 16 + 3 floats; then the workgroup's 128 rows leave as whole lines, thread t owning float4
-// number k * 256 + t of the span for ALL views -- the running sums of a step live in registers (six or seven float4s per thread: with
-// 256 Gaussians per workgroup the thirteen float4s and their index arithmetic did not fit 128 registers), the rows are written once.
+// after view: threads 0..127 form their Gaussian's basis at the view's direction (sh_dir: K9's statement, hence K9's bits) and stage
+// 16 + 3 floats; then the workgroup's 128 rows leave as whole lines (sh_rows.h), thread t owning float4 number k * 256 + t of the span
+// for ALL views -- the running sums of a step live in registers (six or seven float4s per thread: with 256 Gaussians per workgroup the
+// thirteen float4s and their index arithmetic did not fit 128 registers), the rows are written once.
 #define SHV_G 128
 struct ShViewPtrs { const float* campos[BAGS_MAX_SH_VIEWS]; const float* dldc[BAGS_MAX_SH_VIEWS]; };
+template <u32 N> using U = std::integral_constant<u32, N>;      // a span's R and T0 as arguments of the kernel's lambda
 template <bool SPLIT>
 __global__ void __launch_bounds__(256, SPLIT ? 3 : 4)      // (split: 45-float rows, dearer index arithmetic: 19 spilled registers at four per CU)
 sh_grad_from_views_kernel(int P, int deg, const float* __restrict__ means3D, const ShViewPtrs V, int n_views,
                           float* __restrict__ g_shs, float* __restrict__ g_shs_rest, int accumulate)
 {
-    __shared__ float srow[SHV_G][20];
+    __shared__ float srow[SHV_G][SHR_W];
     const int i = blockIdx.x * SHV_G + (threadIdx.x & (SHV_G - 1));
     const size_t ic = (size_t)(i < P ? i : P - 1);
     const float x = means3D[3 * ic], y = means3D[3 * ic + 1], z = means3D[3 * ic + 2];
@@ -676,74 +615,50 @@ sh_grad_from_views_kernel(int P, int deg, const float* __restrict__ means3D, con
     for (int v = 0; v < n_views; ++v) {
         __syncthreads();                                  // the previous view's rows have been consumed
         if (threadIdx.x < SHV_G) {
-            const float cpx = V.campos[v][0], cpy = V.campos[v][1], cpz = V.campos[v][2];
             const float* dl = V.dldc[v] + 3 * ic;
             const float d0 = dl[0], d1 = dl[1], d2 = dl[2];
-            const float ex = x - cpx, ey = y - cpy, ez = z - cpz;
-            const float il = 1.0f / sqrtf(ex * ex + ey * ey + ez * ez);
-            const float ux_ = ex * il, uy_ = ey * il, uz_ = ez * il;
+            const ShDir dir = sh_dir(x, y, z, V.campos[v][0], V.campos[v][1], V.campos[v][2]);
             float bs[16];
-            sh_basis(deg, ux_, uy_, uz_, bs);
-            float4* d4 = reinterpret_cast<float4*>(&srow[threadIdx.x][0]);
+            sh_basis(deg, dir.ux, dir.uy, dir.uz, bs);
             const bool on = i < P;
-            d4[0] = make_float4(bs[0], nb > 1 ? bs[1] : 0.f, nb > 1 ? bs[2] : 0.f, nb > 1 ? bs[3] : 0.f);
-            d4[1] = make_float4(nb > 4 ? bs[4] : 0.f, nb > 4 ? bs[5] : 0.f, nb > 4 ? bs[6] : 0.f, nb > 4 ? bs[7] : 0.f);
-            d4[2] = make_float4(nb > 4 ? bs[8] : 0.f, nb > 9 ? bs[9] : 0.f, nb > 9 ? bs[10] : 0.f, nb > 9 ? bs[11] : 0.f);
-            d4[3] = make_float4(nb > 9 ? bs[12] : 0.f, nb > 9 ? bs[13] : 0.f, nb > 9 ? bs[14] : 0.f, nb > 9 ? bs[15] : 0.f);
-            d4[4] = make_float4(on ? d0 : 0.f, on ? d1 : 0.f, on ? d2 : 0.f, 0.f);
+            shr_stage(&srow[threadIdx.x][0], bs, nb, on ? d0 : 0.f, on ? d1 : 0.f, on ? d2 : 0.f);
         }
         __syncthreads();
-        // products of this view for the float4s the thread owns; the first view starts the sums (or adds to the buffers' content)
-        auto add = [&](const int k, const u32 R, const u32 t0, const u32 el, float* __restrict__ out, const size_t first_f, const size_t total) {
-            float o4[4];
-#pragma unroll
-            for (u32 u = 0; u < 4; ++u) {
-                const u32 f = el * 4u + u, row = f / R, r = f - row * R, t = t0 + r / 3u, c = r - 3u * (r / 3u);
-                o4[u] = srow[row][t] * srow[row][16u + c];
-            }
-            if (first) acc[k] = make_float4(o4[0], o4[1], o4[2], o4[3]);
+        // this view's products for float4 el of a span (rows of R floats, first coefficient T0) into running sum k: the first view starts
+        // the sum, or, in an accumulating call, adds to the buffer's content.  (A lambda on acc[k]: as a function taking the sum by
+        // reference the split instance recomputes its index arithmetic per view, 1591 -> 1836 instructions, profiles/sh_rows/NOTES.md)
+        auto add = [&](const int k, auto R, auto T0, const u32 el, const float* out) {
+            const float4 o = shr_product<decltype(R)::value, decltype(T0)::value>(srow, el);
+            if (first) acc[k] = o;
             else {
-                if (v == 0) {                                // accumulate: the running sums start from what the buffers hold
-                    const size_t g0 = first_f + (size_t)el * 4u;
-                    if (g0 + 3 < total) acc[k] = *reinterpret_cast<const float4*>(out + g0);
-                    else acc[k] = make_float4(g0 < total ? out[g0] : 0.f, g0 + 1 < total ? out[g0 + 1] : 0.f, g0 + 2 < total ? out[g0 + 2] : 0.f, 0.f);
-                }
-                acc[k].x = o4[0] + acc[k].x; acc[k].y = o4[1] + acc[k].y; acc[k].z = o4[2] + acc[k].z; acc[k].w = o4[3] + acc[k].w;
+                if (v == 0) acc[k] = shr_load(out, shr_first<SHV_G, decltype(R)::value>(el), (size_t)P * decltype(R)::value);
+                acc[k] = shr_sum(o, acc[k]);
             }
         };
         if (SPLIT) {
-            if (threadIdx.x < (u32)(SHV_G * 3 / 4)) add(0, 3u, 0u, threadIdx.x, g_shs, (size_t)blockIdx.x * SHV_G * 3u, (size_t)P * 3u);
+            if (threadIdx.x < (u32)(SHV_G * 3 / 4)) add(0, U<3u>{}, U<0u>{}, threadIdx.x, g_shs);
 #pragma unroll
             for (int k = 0; k < 6; ++k) {
                 const u32 el = (u32)k * 256u + threadIdx.x;
-                if (el * 4u < (u32)SHV_G * 45u) add(1 + k, 45u, 1u, el, g_shs_rest, (size_t)blockIdx.x * SHV_G * 45u, (size_t)P * 45u);
+                if (el * 4u < (u32)SHV_G * 45u) add(1 + k, U<45u>{}, U<1u>{}, el, g_shs_rest);
             }
         } else {
 #pragma unroll
-            for (int k = 0; k < 6; ++k) add(k, 48u, 0u, (u32)k * 256u + threadIdx.x, g_shs, (size_t)blockIdx.x * SHV_G * 48u, (size_t)P * 48u);
+            for (int k = 0; k < 6; ++k) add(k, U<48u>{}, U<0u>{}, (u32)k * 256u + threadIdx.x, g_shs);
         }
         first = false;
     }
-    auto put = [&](const int k, const u32 el, float* __restrict__ out, const size_t first_f, const size_t total) {
-        const size_t g0 = first_f + (size_t)el * 4u;
-        if (g0 + 3 < total) *reinterpret_cast<float4*>(out + g0) = acc[k];
-        else {
-            if (g0 < total) out[g0] = acc[k].x;
-            if (g0 + 1 < total) out[g0 + 1] = acc[k].y;
-            if (g0 + 2 < total) out[g0 + 2] = acc[k].z;
-        }
-    };
     if (n_views <= 0) return;
     if (SPLIT) {
-        if (threadIdx.x < (u32)(SHV_G * 3 / 4)) put(0, threadIdx.x, g_shs, (size_t)blockIdx.x * SHV_G * 3u, (size_t)P * 3u);
+        if (threadIdx.x < (u32)(SHV_G * 3 / 4)) shr_store(g_shs, shr_first<SHV_G, 3u>(threadIdx.x), (size_t)P * 3u, acc[0]);
 #pragma unroll
         for (int k = 0; k < 6; ++k) {
             const u32 el = (u32)k * 256u + threadIdx.x;
-            if (el * 4u < (u32)SHV_G * 45u) put(1 + k, el, g_shs_rest, (size_t)blockIdx.x * SHV_G * 45u, (size_t)P * 45u);
+            if (el * 4u < (u32)SHV_G * 45u) shr_store(g_shs_rest, shr_first<SHV_G, 45u>(el), (size_t)P * 45u, acc[1 + k]);
         }
     } else {
 #pragma unroll
-        for (int k = 0; k < 6; ++k) put(k, (u32)k * 256u + threadIdx.x, g_shs, (size_t)blockIdx.x * SHV_G * 48u, (size_t)P * 48u);
+        for (int k = 0; k < 6; ++k) shr_store(g_shs, shr_first<SHV_G, 48u>((u32)k * 256u + threadIdx.x), (size_t)P * 48u, acc[k]);
     }
 }
 // any other M (fewer stored coefficients): a thread per Gaussian writes its own row; the same products in the same order
@@ -758,13 +673,11 @@ sh_grad_from_views_generic_kernel(int P, int M, int deg, const float* __restrict
     float* gsh = g_shs_rest ? g_shs + 3 * (size_t)i : g_shs + (size_t)i * M * 3;
     float* gsr = g_shs_rest ? g_shs_rest + (size_t)i * (M - 1) * 3 : gsh + 3;
     for (int v = 0; v < n_views; ++v) {
-        const float cpx = V.campos[v][0], cpy = V.campos[v][1], cpz = V.campos[v][2];
         const float* dl = V.dldc[v] + 3 * (size_t)i;
         const float d[3] = {dl[0], dl[1], dl[2]};
-        const float ex = x - cpx, ey = y - cpy, ez = z - cpz;
-        const float il = 1.0f / sqrtf(ex * ex + ey * ey + ez * ez);
+        const ShDir dir = sh_dir(x, y, z, V.campos[v][0], V.campos[v][1], V.campos[v][2]);
         float bs[16];
-        sh_basis(deg, ex * il, ey * il, ez * il, bs);
+        sh_basis(deg, dir.ux, dir.uy, dir.uz, bs);
         const bool add = accumulate != 0 || v > 0;
         for (int t = 0; t < M; ++t) {
             float* gr = (t == 0) ? gsh : gsr + 3 * (t - 1);

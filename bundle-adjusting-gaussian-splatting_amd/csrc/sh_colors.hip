@@ -15,8 +15,8 @@
 //   dL/dsh[t][c] = basis_t * m_c  (t < (deg+1)^2; exactly zero for the stored rows beyond)
 //   dL/du        = sum_t grad basis_t * (sum_c sh[t][c] m_c),   dL/dxyz = (dL/du - u (u . dL/du)) / |d|,   dL/dcampos = -sum_P dL/dxyz
 // A Gaussian whose three cotangents are zero (everything the rasterizer culled) reads neither its position nor its row and writes
-// zeros.  The SH gradient rows leave as whole lines through LDS (K9's store pass); the campos sums go wave (DPP) -> workgroup ->
-// one slab row, and sh_campos_reduce_kernel adds the rows in fp64 in a fixed order (a last-workgroup tail inside the kernel is the
+// zeros.  The SH gradient rows leave as whole lines through LDS (sh_rows.h: the write-out K9 uses); the campos sums go wave (DPP) ->
+// workgroup -> one slab row, and sh_campos_reduce_kernel adds the rows in fp64 in a fixed order (a last-workgroup tail inside the kernel is the
 // fold that lost twice for pose_reduce).  No atomics: every gradient is bitwise reproducible.
 //
 // Multi-view form (sh_colors_views_*_kernel): the V <= BAGS_MAX_SH_VIEWS views of one step over the same Gaussians.
@@ -26,12 +26,13 @@
 // value in the kernel arguments (adam.hip's group table): nothing is uploaded.
 //
 // The four colour kernels are built from the same statements, spelled once where that leaves the generated code as it is:
-// shc_load_row (the coefficient row), shc_eval (a view's direction, basis and raw colour) and shc_store_span (the SH gradient rows
-// as whole lines).  The direction gradient is spelled in each backward kernel: as a function of its own it compiles to other code
+// shc_load_row (the coefficient row) and shc_eval (a view's direction, basis and raw colour); the SH gradient rows leave through
+// sh_rows.h (shr_stage, shr_span), which preprocess_bwd.hip shares.  The direction gradient is spelled in each backward kernel: as a function of its own it compiles to other code
 // (profiles/sh_colors/NOTES.md), so a change to it is made in both.  They share statements, not kernels: the views backward stages
 // 51200 bytes of LDS and needs twice the registers of the single-view one, which is render()'s default path.
 #include "bags_common.h"
 #include "sh_basis.h"
+#include "sh_rows.h"
 
 struct ShcIn { int P, deg; const float *shs, *shs_rest, *xyz, *campos; };
 
@@ -104,49 +105,13 @@ sh_colors_fwd_kernel(const ShcIn A, float* __restrict__ rgb)
 
 #define SHC_ROW 49       // floats per Gaussian in the views backward's LDS stage: 48 + 1, so that the 64 lanes' own rows fall on distinct banks
 
-// The workgroup's 256 gradient rows of one tensor, R floats each, as whole lines: thread t owns float4 number t, t + 256, ... of the
-// workgroup's span (256 R floats: a multiple of 16 bytes from a 16-byte aligned base).  The floats come from the kernel's LDS stage,
-// W floats per Gaussian, the tensor's row starting at coefficient T0:
-//   PRODUCT (single view, W = 20): stage[g] = basis[16] (zero beyond the active degree and for a Gaussian that writes zeros), masked
-//                                  cotangent[3], pad; a gradient is their product
-//   otherwise (views, W = SHC_ROW): stage[g] = the summed gradient row, packed
-template <u32 R, u32 T0, bool PRODUCT, u32 W>
-__device__ __forceinline__ void shc_store_span(const float (*stage)[W], float* __restrict__ out, const int P)
-{
-    const size_t first_f = (size_t)blockIdx.x * 256u * R, total = (size_t)P * R;
-#pragma unroll
-    for (u32 k = 0; k < (64u * R + 255u) / 256u; ++k) {
-        const u32 el = k * 256u + threadIdx.x;
-        const size_t g0 = first_f + (size_t)el * 4u;
-        if (el < 64u * R && g0 < total) {
-            float o4[4];
-#pragma unroll
-            for (u32 u = 0; u < 4; ++u) {
-                if constexpr (PRODUCT) {
-                    const u32 f = el * 4u + u, row = f / R, r = f - row * R, t = T0 + r / 3u, ch = r - 3u * (r / 3u);
-                    o4[u] = stage[row][t] * stage[row][16u + ch];
-                } else {
-                    const u32 f = el * 4u + u, row = f / R, r = f - row * R;
-                    o4[u] = stage[row][3u * T0 + r];
-                }
-            }
-            if (g0 + 3 < total) *reinterpret_cast<float4*>(out + g0) = make_float4(o4[0], o4[1], o4[2], o4[3]);
-            else {                                    // the tensor's last float4 may be partial (P R not a multiple of 4)
-                out[g0] = o4[0];
-                if (g0 + 1 < total) out[g0 + 1] = o4[1];
-                if (g0 + 2 < total) out[g0 + 2] = o4[2];
-            }
-        }
-    }
-}
-
 // need_dir: the direction gradient is wanted (deg > 0 and g_xyz or slab given); without it g_xyz, if given, receives zeros
 template <int K, bool SPLIT>
 __global__ void __launch_bounds__(256)
 sh_colors_bwd_kernel(const ShcIn A, const float* __restrict__ g_rgb, float* __restrict__ g_shs, float* __restrict__ g_shs_rest,
                      float* __restrict__ g_xyz, float* __restrict__ slab, const int need_dir)
 {
-    __shared__ float srow[256][20];
+    __shared__ float srow[256][SHR_W];
     __shared__ float wsum[4][4];
     const int i = blockIdx.x * 256 + threadIdx.x;
     const bool on = i < A.P;
@@ -166,7 +131,7 @@ sh_colors_bwd_kernel(const ShcIn A, const float* __restrict__ g_rgb, float* __re
         shc_eval<K>(x, y, z, A.campos, A.deg, nb, c, dl, ux, uy, uz, b, r, g, bl);   // the forward's bits, hence its clamp decision
         m0 = r < 0.f ? 0.f : g0; m1 = g < 0.f ? 0.f : g1; m2 = bl < 0.f ? 0.f : g2;
 #pragma unroll
-        for (int t = 0; t < K; ++t) bs[t] = (t < nb) ? b[t] : 0.f;
+        for (int t = 0; t < K; ++t) bs[t] = b[t];
         if (need_dir && (m0 != 0.f || m1 != 0.f || m2 != 0.f)) {
             float bx[16], by[16], bz[16];
             sh_basis_grad(A.deg, ux, uy, uz, bx, by, bz);
@@ -184,18 +149,13 @@ sh_colors_bwd_kernel(const ShcIn A, const float* __restrict__ g_rgb, float* __re
     if (g_xyz && on) { g_xyz[3 * ic] = gx; g_xyz[3 * ic + 1] = gy; g_xyz[3 * ic + 2] = gz; }
 
     if (g_shs || g_shs_rest) {                           // (kernel arguments: the whole workgroup takes the same side)
-        float4* d4 = reinterpret_cast<float4*>(&srow[threadIdx.x][0]);
-        d4[0] = make_float4(bs[0], bs[1], bs[2], bs[3]);
-        d4[1] = make_float4(bs[4], bs[5], bs[6], bs[7]);
-        d4[2] = make_float4(bs[8], bs[9], bs[10], bs[11]);
-        d4[3] = make_float4(bs[12], bs[13], bs[14], bs[15]);
-        d4[4] = make_float4(m0, m1, m2, 0.f);
+        shr_stage(&srow[threadIdx.x][0], bs, nb, m0, m1, m2);      // (bs is zero beyond the active degree already, and for a Gaussian that writes zeros)
         __syncthreads();
         if constexpr (SPLIT) {
-            if (g_shs) shc_store_span<3u, 0u, true>(srow, g_shs, A.P);
-            if (g_shs_rest) shc_store_span<3u * (K - 1), 1u, true>(srow, g_shs_rest, A.P);
+            if (g_shs) shr_span<256u, 3u, 0u, SHR_PRODUCT>(srow, g_shs, A.P);
+            if (g_shs_rest) shr_span<256u, 3u * (K - 1), 1u, SHR_PRODUCT>(srow, g_shs_rest, A.P);
         } else if (g_shs) {
-            shc_store_span<3u * K, 0u, true>(srow, g_shs, A.P);
+            shr_span<256u, 3u * K, 0u, SHR_PRODUCT>(srow, g_shs, A.P);
         }
     }
 
@@ -211,24 +171,11 @@ sh_colors_bwd_kernel(const ShcIn A, const float* __restrict__ g_rgb, float* __re
     }
 }
 
-// slab rows -> dL/dcampos in fp64: one workgroup per component, thread t adds rows t, t + 256, ... in row order, the lanes of a
-// wave by a fixed shuffle tree, the four waves in wave order (pose_reduce_kernel's scheme, clamped batched loads included)
+// slab rows -> dL/dcampos in fp64, one workgroup per component (bags_common.h: slab_column_sum, pose_reduce_kernel's sum)
 __device__ __forceinline__ void shc_campos_reduce(const float* __restrict__ slab, const int nblocks, const int t, float* __restrict__ g_campos)
 {
-    __shared__ double wsum[4];
-    double acc = 0.0;
-    for (int b = threadIdx.x; b < nblocks; b += 8 * 256) {
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = slab[(size_t)min(b + u * 256, nblocks - 1) * 4 + t];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) acc += (b + u * 256 < nblocks) ? (double)v[u] : 0.0;
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) g_campos[t] = (float)(((wsum[0] + wsum[1]) + wsum[2]) + wsum[3]);
+    const double sum = slab_column_sum(slab, nblocks, SH_SLAB, t);
+    if (threadIdx.x == 0) g_campos[t] = (float)sum;
 }
 
 __global__ void __launch_bounds__(256)
@@ -350,10 +297,10 @@ sh_colors_views_bwd_kernel(const ShcViewsIn A, const ShcViewsCot G, float* __res
     }
     __syncthreads();
     if constexpr (SPLIT) {
-        if (g_shs) shc_store_span<3u, 0u, false>(sacc, g_shs, A.P);
-        if (g_shs_rest) shc_store_span<3u * (K - 1), 1u, false>(sacc, g_shs_rest, A.P);
+        if (g_shs) shr_span<256u, 3u, 0u, SHR_PACKED>(sacc, g_shs, A.P);
+        if (g_shs_rest) shr_span<256u, 3u * (K - 1), 1u, SHR_PACKED>(sacc, g_shs_rest, A.P);
     } else if (g_shs) {
-        shc_store_span<3u * K, 0u, false>(sacc, g_shs, A.P);
+        shr_span<256u, 3u * K, 0u, SHR_PACKED>(sacc, g_shs, A.P);
     }
     if (slab && threadIdx.x < 4 * A.V) {                 // one slab row per (view, workgroup), the single-view kernel's sum of the waves
         const int v = threadIdx.x >> 2, t = threadIdx.x & 3;

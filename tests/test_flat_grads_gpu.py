@@ -277,14 +277,17 @@ def test_backward_twice_on_one_forward_and_forward_without_backward():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("M,deg,split,P", [(16, 3, False, 3001), (16, 3, True, 3001), (16, 1, True, 700), (9, 2, False, 515), (4, 1, True, 130)])
+@pytest.mark.parametrize("M,deg,split,P", [(16, 3, False, 3001), (16, 3, True, 3001), (16, 1, True, 700), (9, 2, False, 515), (4, 1, True, 130),
+                                           (16, 2, True, 127), (16, 3, False, 129), (16, 3, True, 257)])
 def test_factored_sh_gradient_equals_the_accumulated_one(M, deg, split, P):
     """ABI 10: rasterizer.FactoredSH.  Every view's backward writes only dL/dcolour (P,3); finish() forms the SH-gradient rows of the
     whole step in one kernel.  Same products (basis at the view's direction x dL/dcolour), added in view order: the result must be
     bit for bit what the same backwards leave with ACCUMULATE_IN_PLACE (and with autograd's own accumulation) -- for the concatenated
     (P,M,3) tensor and for the features_dc / features_rest pair, M = 16 (whole-line kernel) and smaller M (row kernel), an active
     degree below the stored one, P not a multiple of the workgroup's 128 Gaussians, a second step accumulating on top of the first;
-    every other gradient untouched by the switch."""
+    every other gradient untouched by the switch.  The last three shapes sit at the workgroup edges of the shared write-out
+    (csrc/sh_rows.h): one partial 128-Gaussian workgroup, one Gaussian into the second, K9's 256 rows plus one (3 P and 45 P no
+    multiples of 4: the tensors' last float4 is partial)."""
     import math
     from bags_raster import GaussianRasterizationSettings, GaussianRasterizer, rasterizer as R
     from bags_raster.synth import sphere_views, synth_scene

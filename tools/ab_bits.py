@@ -18,7 +18,13 @@ partial second workgroup, several blocks -- the kernels are one thread per Gauss
 crossed so that each of the 4 K1 kernels (SPLIT x with / without the tile count) and the 16 instances of preprocess_bwd_kernel
 (COV3D x ACCUM x LIVE x EXTRA) runs in at least one stable case; one camera is narrow enough that visible Gaussians sit beyond the
 1.3 x field-of-view clamp on each axis (checked on the CPU with the oracle before any child starts).  Exit status 0: every
-counted tensor equal and every instance covered."""
+counted tensor equal and every instance covered.
+
+Since csrc/sh_rows.h (the SH gradient row write-out shared by K9, sh_grad_from_views_kernel and the sh_colors backwards) the list
+also holds, at the same image size: steps of V = 3 views through rasterizer.FactoredSH, the second step accumulating (M = 16 packed
+and split: sh_grad_from_views_kernel<0> / <1>; M = 9 packed and M = 4 split: the generic kernel; P in {129, 257, 3000}), and the
+backwards of sh_colors and sh_colors_views with V = 3 and every gradient asked for (K in {16, 9, 4} packed and split, K = 1 packed,
+P in {1, 257, 3000}: the store pass and the campos reduction both run).  They count as the others do."""
 import argparse
 import itertools
 import os
@@ -61,7 +67,100 @@ def case_list():
     add("narrow_packed", 3000, 60, "packed", cam="narrow")
     add("narrow_split_radix", 3000, 61, "split", binning="radix", tile_bounds="aabb", accum=True, dense=1, extra=True, cam="narrow")
     add("narrow_cov3d", 3000, 62, "precomp", "cov3d", dense=1, cam="narrow")
+    # csrc/sh_rows.h: the factored SH gradient of a step of views, and the colour operators' backwards
+    for P in (129, 257, 3000):
+        for M, colour in ((16, "packed"), (16, "split"), (9, "packed"), (4, "split")):
+            add(f"fsh_m{M}_{colour}_p{P}", P, 70 + M, colour)
+            cases[-1].update(kind="factored", M=M)
+    for P in (1, 257, 3000):
+        for K, colour in ((16, "packed"), (16, "split"), (9, "packed"), (9, "split"), (4, "packed"), (4, "split"), (1, "packed")):
+            add(f"shc_k{K}_{colour}_p{P}", P, 90 + K, colour)
+            cases[-1].update(kind="shc", M=K)
     return cases
+
+
+VIEWS = 3
+
+
+def run_factored(c, dev):
+    """GPU (child): two steps of VIEWS views with rasterizer.FactoredSH installed, the second accumulating on the first's gradients."""
+    import math
+    from bags_raster import GaussianRasterizationSettings, GaussianRasterizer
+    from bags_raster import rasterizer as R
+    from bags_raster.synth import sphere_views
+    from scenes import camera_tensors
+    x, _ = build_case(c)
+    P, M = c["P"], c["M"]
+    deg = {16: 3, 9: 2, 4: 1}[M]
+    cams = sphere_views(VIEWS, W, H, noise=0.05)
+    cots = [torch.randn(3, H, W, generator=torch.Generator().manual_seed(300 + v)).to(dev) for v in range(VIEWS)]
+    leaf = lambda t: t.to(dev).clone().contiguous().requires_grad_(True)     # noqa: E731
+    p = {k: leaf(x[k]) for k in ("means3D", "opacities", "scales", "rotations")}
+    shs = x["shs"][:, :M]
+    dc, rest = (leaf(shs[:, :1]), leaf(shs[:, 1:])) if c["colour"] == "split" else (leaf(shs), None)
+    saved = (R.ACCUMULATE_IN_PLACE, R.FACTORED_SH, R.DENSE_PER_TILE)
+    R.ACCUMULATE_IN_PLACE, R.DENSE_PER_TILE = True, -1
+    try:
+        for _ in range(2):
+            fs = R.FactoredSH()
+            R.FACTORED_SH = fs
+            for cam, cot in zip(cams, cots):
+                ct = camera_tensors(cam, dev)
+                st = GaussianRasterizationSettings(image_height=H, image_width=W, tanfovx=math.tan(cam.FoVx * 0.5), tanfovy=math.tan(cam.FoVy * 0.5),
+                                                   bg=torch.zeros(3, device=dev), scale_modifier=SM, viewmatrix=ct["viewmatrix"],
+                                                   projmatrix=ct["projmatrix"], intrinsic=ct["intrinsic"], sh_degree=deg, campos=ct["campos"])
+                img = GaussianRasterizer(st)(means3D=p["means3D"], means2D=torch.zeros(P, 3, device=dev, requires_grad=True), shs=dc, shs_rest=rest,
+                                             opacities=p["opacities"], scales=p["scales"], rotations=p["rotations"])[0]
+                img.backward(cot)
+            R.FACTORED_SH = None
+            fs.finish(p["means3D"], dc, rest)
+    finally:
+        R.ACCUMULATE_IN_PLACE, R.FACTORED_SH, R.DENSE_PER_TILE = saved
+    res = {"grad_" + k: t.grad.detach() for k, t in p.items()}
+    res["grad_shs"] = dc.grad.detach()
+    if rest is not None:
+        res["grad_shs_rest"] = rest.grad.detach()
+    res["image"] = img.detach()
+    res["num_rendered"] = torch.tensor([R.LAST_NUM_RENDERED])
+    torch.cuda.synchronize(dev)
+    return {k: t.cpu().numpy() for k, t in res.items()}
+
+
+def run_shc(c, dev):
+    """GPU (child): sh_colors (view 0) and sh_colors_views (VIEWS views) forward + backward, every gradient asked for."""
+    from bags_raster import sh_colors, sh_colors_views
+    x, _ = build_case(c)
+    P, K = c["P"], c["M"]
+    deg = {16: 3, 9: 2, 4: 1, 1: 0}[K]
+    g = torch.Generator().manual_seed(2000 + c["seed"])
+    centres = [torch.tensor([0.3 * v, -0.2, -4.0 + 0.5 * v]) + 0.1 * torch.randn(3, generator=g) for v in range(VIEWS)]
+    cots = []
+    for v in range(VIEWS):
+        cot = torch.randn(P, 3, generator=g)
+        cot[(2 + v)::5] = 0.0                            # rows without a cotangent, as for culled Gaussians
+        cots.append(cot.to(dev))
+    shs = x["shs"][:, :K]
+    res = {}
+    for tag in ("one", "views"):
+        leaf = lambda t: t.to(dev).clone().contiguous().requires_grad_(True)     # noqa: E731
+        xyz = leaf(x["means3D"])
+        dc, rest = (leaf(shs[:, :1]), leaf(shs[:, 1:])) if c["colour"] == "split" else (leaf(shs), None)
+        cps = [leaf(t) for t in centres]
+        if tag == "one":
+            outs = [sh_colors(deg, dc, xyz, cps[0], shs_rest=rest)]
+        else:
+            outs = list(sh_colors_views(deg, dc, xyz, cps, shs_rest=rest))
+        torch.autograd.backward(outs, cots[:len(outs)])
+        for v, o in enumerate(outs):
+            res[f"{tag}_rgb{v}"] = o.detach()
+            if cps[v].grad is not None:
+                res[f"{tag}_grad_campos{v}"] = cps[v].grad.detach()
+        res[f"{tag}_grad_shs"], res[f"{tag}_grad_xyz"] = dc.grad.detach(), xyz.grad.detach()
+        if rest is not None:
+            res[f"{tag}_grad_shs_rest"] = rest.grad.detach()
+    res["num_rendered"] = torch.tensor([0])
+    torch.cuda.synchronize(dev)
+    return {k: t.cpu().numpy() for k, t in res.items()}
 
 
 def build_case(c):
@@ -111,6 +210,10 @@ def check_clamp(cases):
 
 def run_case(c, dev):
     """GPU (child): one case through the op; returns {tensor name: numpy array}."""
+    if c.get("kind") == "factored":
+        return run_factored(c, dev)
+    if c.get("kind") == "shc":
+        return run_shc(c, dev)
     from bags_raster import GaussianRasterizer, debug_views
     from bags_raster import rasterizer as R
     from scenes import camera_tensors, hip_settings
@@ -180,7 +283,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("alternative", nargs="?")
     ap.add_argument("--out", help="where the children's .npz files go (default: a fresh temporary directory)")
-    ap.add_argument("--timeout", type=int, default=150, help="seconds per child")
+    ap.add_argument("--timeout", type=int, default=240, help="seconds per child")
     ap.add_argument("--child", metavar="NPZ", help=argparse.SUPPRESS)
     ap.add_argument("--check-clamp", action="store_true", help="only the CPU check of the narrow camera's cases")
     a = ap.parse_args()
@@ -214,7 +317,7 @@ def main():
             return 1
         runs[tag] = np.load(path)
     same = lambda u, v: u.dtype == v.dtype and u.shape == v.shape and u.tobytes() == v.tobytes()     # noqa: E731
-    bad, covered_k9, covered_k1 = 0, set(), set()
+    bad, covered_k9, covered_k1, covered_rows = 0, set(), set(), set()
     for c in cases:
         keys = sorted(k for k in runs["alt_1"].files if k.startswith(c["name"] + "/"))
         if sorted(k for k in runs["product"].files if k.startswith(c["name"] + "/")) != keys:
@@ -225,10 +328,20 @@ def main():
         k9 = (c["cov"] == "cov3d", c["accum"], c["dense"] > 0 and n_inst > c["dense"] * TILES, c["extra"])
         k1 = (c["colour"] == "split", c["binning"] == "auto")
         tag = "K9<COV3D,ACCUM,LIVE,EXTRA>=" + "".join("01"[b] for b in k9) + " K1<SPLIT>=%d%s" % (k1[0], ",count" if k1[1] else "")
+        rows = None
+        if c.get("kind") == "factored":                  # K9 runs too (ACCUM, no LIVE / EXTRA / COV3D): the raster cases cover it
+            rows = ("sh_grad_from_views", c["M"] if c["M"] != 16 else (16, c["colour"]))
+            k9, tag = None, "K9<..>=0100 + %s %s" % rows
+        elif c.get("kind") == "shc":
+            rows = ("sh_colors(_views)_bwd", c["M"], c["colour"])
+            k9, tag = None, "%s K=%d %s" % rows
         if unstable:
             print(f"{c['name']:22s} NOT BIT-STABLE on the alternative itself, not counted ({tag}): " + " ".join(k.split("/")[1] for k in unstable))
             continue
-        covered_k9.add(k9); covered_k1.add(k1)
+        if rows:
+            covered_rows.add(rows)
+        else:
+            covered_k9.add(k9); covered_k1.add(k1)
         for k in keys:
             eq = same(runs["alt_1"][k], runs["product"][k])
             bad += not eq
@@ -237,9 +350,14 @@ def main():
         print(f"{c['name']:22s} instances {n_inst}  {tag}")
     miss9 = [t for t in itertools.product((False, True), repeat=4) if t not in covered_k9]
     miss1 = [t for t in itertools.product((False, True), repeat=2) if t not in covered_k1]
-    print(f"instances covered by stable cases: preprocess_bwd_kernel {len(covered_k9)} of 16, K1 {len(covered_k1)} of 4")
-    if miss9 or miss1:
-        print("FAIL: not covered:", miss9, miss1)
+    want_rows = {("sh_grad_from_views", (16, "packed")), ("sh_grad_from_views", (16, "split")), ("sh_grad_from_views", 9), ("sh_grad_from_views", 4)}
+    want_rows |= {("sh_colors(_views)_bwd", K, col) for K in (16, 9, 4) for col in ("packed", "split")} | {("sh_colors(_views)_bwd", 1, "packed")}
+    miss_rows = sorted(map(str, want_rows - covered_rows))
+    print(f"instances covered by stable cases: preprocess_bwd_kernel {len(covered_k9)} of 16, K1 {len(covered_k1)} of 4, "
+          f"sh_grad_from_views {sum(r[0] == 'sh_grad_from_views' for r in covered_rows)} of 4, "
+          f"colour backwards {sum(r[0] != 'sh_grad_from_views' for r in covered_rows)} of 7")
+    if miss9 or miss1 or miss_rows:
+        print("FAIL: not covered:", miss9, miss1, miss_rows)
         return 1
     print("FAIL: %d tensors differ" % bad if bad else "OK: every tensor of every counted case is byte-equal")
     return 1 if bad else 0
