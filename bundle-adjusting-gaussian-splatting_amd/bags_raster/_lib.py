@@ -156,6 +156,13 @@ class BagsDensifyGroup(C.Structure):
                 ("exp_avg_sq_out", c_fp), ("width", C.c_int32), ("role", C.c_int32)]
 
 
+LENS_MAX_HIDDEN, LENS_MAX_INTERNAL_LAYERS, LENS_MAX_BLOCKS = 64, 4, 32
+
+
+class BagsLensField(C.Structure):           # the lens network: params is ONE flat vector, per block W_0 b_0 (W_i b_i) x n W_out b_out
+    _fields_ = [("blocks", C.c_int32), ("hidden", C.c_int32), ("internal_layers", C.c_int32), ("reserved", C.c_int32), ("params", c_fp)]
+
+
 SYMBOLS = {    "bags_abi_version": (C.c_int, []),
     "bags_build_info": (C.c_char_p, []),
     "bags_last_error": (C.c_char_p, []),
@@ -215,6 +222,10 @@ SYMBOLS = {    "bags_abi_version": (C.c_int, []),
     "bags_densify_apply": (C.c_int, [C.POINTER(BagsDensifyRule), C.POINTER(BagsDensifyGroup), C.c_int32, C.c_void_p, C.c_size_t, C.c_int64,
                                      c_fp, c_fp, c_fp, c_fp, C.c_void_p]),
     "bags_reset_opacity": (C.c_int, [c_fp, c_fp, c_fp, C.c_int32, C.c_void_p]),
+    "bags_lens_field_workspace_size": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int64]),
+    "bags_lens_field_forward": (C.c_int, [C.POINTER(BagsLensField), c_fp, C.c_int64, c_fp, C.c_void_p]),
+    "bags_lens_field_backward": (C.c_int, [C.POINTER(BagsLensField), c_fp, C.c_int64, c_fp, C.c_void_p, C.c_size_t, c_fp, c_fp, C.c_void_p]),
+    "bags_lens_field_inverse": (C.c_int, [C.POINTER(BagsLensField), c_fp, C.c_int64, C.c_int32, c_fp, C.c_void_p]),
     "bags_knn_workspace_size": (C.c_size_t, [C.c_int32]),
     "bags_knn_mean_dist2": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "bags_compute_relocation": (C.c_int, [c_fp, c_fp, c_fp, c_fp, C.c_int32, C.c_int32, c_fp, c_fp, C.c_void_p]),

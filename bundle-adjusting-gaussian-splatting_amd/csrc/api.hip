@@ -1008,6 +1008,70 @@ int bags_reset_opacity(float* opacity, float* exp_avg, float* exp_avg_sq, int32_
     return BAGS_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- lens network
+#define LENS_TORCH_PATH "a larger net is a GEMM problem, not a launch-count one: use the PyTorch path, lens_field_torch"
+static const int64_t LENS_MAX_POINTS = (int64_t)1 << 36;       // tiles of 64 points fit the grid's 31 bits
+
+static bool lens_shape_ok(int B, int H, int n)
+{
+    return B >= 1 && B <= BAGS_LENS_MAX_BLOCKS && H >= 1 && H <= BAGS_LENS_MAX_HIDDEN && n >= 0 && n <= BAGS_LENS_MAX_INTERNAL_LAYERS;
+}
+
+static int check_lens_field(const char* op, const BagsLensField* a, int64_t M)
+{
+    if (!a) return fail(BAGS_ERR_ARG, "%s: null struct", op);
+    if (!lens_shape_ok(a->blocks, a->hidden, a->internal_layers))
+        return fail(BAGS_ERR_ARG, "%s: blocks %d, hidden %d, internal_layers %d not in 1..%d, 1..%d, 0..%d (" LENS_TORCH_PATH ")", op, a->blocks, a->hidden,
+                    a->internal_layers, BAGS_LENS_MAX_BLOCKS, BAGS_LENS_MAX_HIDDEN, BAGS_LENS_MAX_INTERNAL_LAYERS);
+    if (M < 0 || M > LENS_MAX_POINTS) return fail(BAGS_ERR_ARG, "%s: M %lld not in 0..2^36", op, (long long)M);
+    if (!a->params) return fail(BAGS_ERR_ARG, "%s: null params", op);
+    return BAGS_OK;
+}
+
+// 0 for a shape outside the limits (the entry points refuse it) or M < 0
+size_t bags_lens_field_workspace_size(int32_t blocks, int32_t hidden, int32_t internal_layers, int64_t M)
+{
+    if (!lens_shape_ok(blocks, hidden, internal_layers) || M < 0 || M > LENS_MAX_POINTS) return 0;
+    return lens_field_workspace_bytes(blocks, hidden, internal_layers, M);
+}
+
+int bags_lens_field_forward(const BagsLensField* a, const float* x, int64_t M, float* y, void* stream)
+{
+    if (const int rc = check_lens_field("lens_field_forward", a, M)) return rc;
+    if (M == 0) return BAGS_OK;
+    if (!x || !y) return fail(BAGS_ERR_ARG, "lens_field_forward: null x / y");
+    HIP_TRY(launch_lens_field_fwd(*a, x, M, y, false, 0, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
+int bags_lens_field_inverse(const BagsLensField* a, const float* y, int64_t M, int32_t iterations, float* x, void* stream)
+{
+    if (const int rc = check_lens_field("lens_field_inverse", a, M)) return rc;
+    if (iterations < 0) return fail(BAGS_ERR_ARG, "lens_field_inverse: iterations %d < 0", iterations);
+    if (M == 0) return BAGS_OK;
+    if (!x || !y) return fail(BAGS_ERR_ARG, "lens_field_inverse: null y / x");
+    HIP_TRY(launch_lens_field_fwd(*a, y, M, x, true, iterations, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
+int bags_lens_field_backward(const BagsLensField* a, const float* x, int64_t M, const float* grad_y, void* workspace, size_t workspace_bytes,
+                             float* grad_x, float* grad_params, void* stream)
+{
+    if (const int rc = check_lens_field("lens_field_backward", a, M)) return rc;
+    if (!grad_x && !grad_params) return BAGS_OK;
+    if (M == 0) {
+        if (grad_params)
+            HIP_TRY(hipMemsetAsync(grad_params, 0, (size_t)a->blocks * lens_block_floats(a->hidden, a->internal_layers) * sizeof(float), (hipStream_t)stream));
+        return BAGS_OK;
+    }
+    if (!x || !grad_y) return fail(BAGS_ERR_ARG, "lens_field_backward: null x / grad_y");
+    if (grad_params == a->params) return fail(BAGS_ERR_ARG, "lens_field_backward: grad_params must not be the params vector");
+    const size_t need = lens_field_workspace_bytes(a->blocks, a->hidden, a->internal_layers, M);
+    if (!workspace || workspace_bytes < need) return fail(BAGS_ERR_SIZE, "lens_field_backward: needs a workspace of %zu bytes", need);
+    HIP_TRY(launch_lens_field_bwd(*a, x, M, grad_y, workspace, grad_x, grad_params, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- kNN scale initialiser
 size_t bags_knn_workspace_size(int32_t P) { return knn_workspace_bytes(P > 0 ? P : 1); }
 

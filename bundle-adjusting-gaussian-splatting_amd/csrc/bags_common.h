@@ -309,6 +309,12 @@ hipError_t launch_densify_plan(const BagsDensifyRule& r, void* workspace, u32 ho
 hipError_t launch_densify_apply(const BagsDensifyRule& r, const BagsDensifyGroup* groups, int n_groups, void* workspace, long long P_new,
                                 float* accum_out, float* denom_out, float* radii_out, int32_t* provenance, hipStream_t st);
 hipError_t launch_reset_opacity(float* opacity, float* exp_avg, float* exp_avg_sq, int P, float cap, hipStream_t st);
+// lens_field.hip: the invertible-ResNet lens network on M points of R^2 (forward / fixed-point inverse in one launch, backward in two)
+__host__ __device__ static inline int lens_block_floats(int H, int n) { return 3 * H + n * (H * H + H) + 2 * H + 2; }   // of the flat vector, per block
+size_t lens_field_workspace_bytes(int B, int H, int n, long long M);
+hipError_t launch_lens_field_fwd(const BagsLensField& a, const float* src, long long M, float* dst, bool inverse, int iterations, hipStream_t st);
+hipError_t launch_lens_field_bwd(const BagsLensField& a, const float* x, long long M, const float* grad_y, void* workspace, float* grad_x,
+                                 float* grad_params, hipStream_t st);
 // knn.hip: mean squared distance to the three nearest neighbours (distCUDA2)
 size_t knn_workspace_bytes(int P);
 hipError_t launch_knn(const float* pts, int P, void* ws, float* out, hipStream_t st);

@@ -564,6 +564,36 @@ int bags_densify_apply(const BagsDensifyRule* rule, const BagsDensifyGroup* grou
 /* GaussianModel.reset_opacity: opacity = logit(min(sigmoid(opacity), 0.01)) in place, its two moments (either may be NULL) zeroed. */
 int bags_reset_opacity(float* opacity, float* exp_avg, float* exp_avg_sq, int32_t P, void* stream);
 
+/* The lens network that produces the control flow of bags_resample_* (csrc/lens_field.hip): the reference's invertible ResNet
+ * (scene/iresnet.py, FrEIA's IResNetLayer shape) evaluated on M points of R^2.  A point goes through `blocks` residual blocks
+ * x <- x + g_b(x); g_b is Linear(2, H), ELU, then `internal_layers` times (Linear(H, H), ELU), then Linear(H, 2), with ELU's
+ * alpha = 1 and every weight in nn.Linear's (out, in) row-major layout.  params is ONE flat fp32 vector; per block, in order:
+ * W_0 (H,2), b_0 (H), then W_i (H,H), b_i (H) for i = 1..internal_layers, then W_out (2,H), b_out (2), that is
+ * 3H + n(H^2 + H) + 2H + 2 floats per block.  A wider net is a GEMM problem, not a launch-count one: it stays with PyTorch.
+ * forward:  y (M,2) in one launch; a block's weights are staged once per workgroup in LDS and nothing per point leaves the chip but y.
+ * backward: nothing is saved by the forward; every block's input and activations are recomputed from x.  grad_x (M,2) and
+ *           grad_params (the length of params) may each be NULL; with grad_x NULL the first layer's input gradient is not formed.
+ *           grad_params is written, not accumulated: per-workgroup partial sums in the workspace, added in workgroup order by a
+ *           second launch.  No atomics: two runs give the same bits on any stream.  The workspace
+ *           (bags_lens_field_workspace_size bytes) needs no initialisation; beside the partial sums it holds 8 bytes per point
+ *           and block boundary.
+ * inverse:  the blocks in reverse order, each by `iterations` steps of the fixed-point iteration x <- y - g_b(x) from x = y,
+ *           which converges when every g_b is a contraction (LensField.lipschitz_correction keeps them so).  No gradient.
+ * x, y and grad_y must not alias an output of the same call (forward and inverse may run in place: y == x).  M == 0 is a
+ * successful no-op that still zero-fills grad_params. */
+#define BAGS_LENS_MAX_HIDDEN 64
+#define BAGS_LENS_MAX_INTERNAL_LAYERS 4
+#define BAGS_LENS_MAX_BLOCKS 32
+typedef struct BagsLensField {
+    int32_t blocks, hidden, internal_layers, reserved;
+    const float* params;             /* blocks * (3H + n(H^2 + H) + 2H + 2) floats */
+} BagsLensField;
+size_t bags_lens_field_workspace_size(int32_t blocks, int32_t hidden, int32_t internal_layers, int64_t M);
+int bags_lens_field_forward(const BagsLensField* net, const float* x, int64_t M, float* y, void* stream);
+int bags_lens_field_backward(const BagsLensField* net, const float* x, int64_t M, const float* grad_y, void* workspace,
+                             size_t workspace_bytes, float* grad_x, float* grad_params, void* stream);
+int bags_lens_field_inverse(const BagsLensField* net, const float* y, int64_t M, int32_t iterations, float* x, void* stream);
+
 /* distCUDA2 of the reference's second native dependency (simple_knn._C, imported at scene/gaussian_model.py:20, called at
  * scene/gaussian_model.py:177 to initialise the scales): out[i] = mean of the squared distances from point i to its three
  * nearest neighbours (self excluded by index; coincident points count with distance 0; with fewer than four points the
