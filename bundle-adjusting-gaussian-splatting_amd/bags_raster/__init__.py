@@ -12,8 +12,10 @@ from .io import save_ply, load_ply, save_checkpoint, load_checkpoint
 from .optim import GaussianAdam
 from .pose_bank import PoseBank, PoseAdam
 from .lens_field import LensField, lens_field, lens_field_torch
+from .distortion import resample_faces, resample_faces_torch, cube_face_matrices
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "debug_views",
            "compute_relocation", "render", "render_views", "PipelineParams", "GaussianBag", "eval_sh", "sh_colors", "sh_colors_views",
            "save_ply", "load_ply", "save_checkpoint", "load_checkpoint", "GaussianAdam",
-           "PoseBank", "PoseAdam", "LensField", "lens_field", "lens_field_torch"]
+           "PoseBank", "PoseAdam", "LensField", "lens_field", "lens_field_torch",
+           "resample_faces", "resample_faces_torch", "cube_face_matrices"]

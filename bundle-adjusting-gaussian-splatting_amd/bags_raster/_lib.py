@@ -163,6 +163,14 @@ class BagsLensField(C.Structure):           # the lens network: params is ONE fl
     _fields_ = [("blocks", C.c_int32), ("hidden", C.c_int32), ("internal_layers", C.c_int32), ("reserved", C.c_int32), ("params", c_fp)]
 
 
+MAX_FACES = 8
+
+
+class BagsFaces(C.Structure):               # the faces of a cubemap: image pointers and the 3x3 matrices (row-major) by value
+    _fields_ = [("n_faces", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("image", c_fp * MAX_FACES),
+                ("mats", (C.c_float * 9) * MAX_FACES)]
+
+
 SYMBOLS = {    "bags_abi_version": (C.c_int, []),
     "bags_build_info": (C.c_char_p, []),
     "bags_last_error": (C.c_char_p, []),
@@ -207,6 +215,10 @@ SYMBOLS = {    "bags_abi_version": (C.c_int, []),
     "bags_resample_workspace_size": (C.c_size_t, [C.c_int32] * 4),
     "bags_resample_backward": (C.c_int, [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p] + [C.c_int32] * 6 +
                                [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bags_resample_faces_workspace_size": (C.c_size_t, [C.c_int32] * 5),
+    "bags_resample_faces_forward": (C.c_int, [C.POINTER(BagsFaces), c_fp] + [C.c_int32] * 6 + [c_fp, c_fp, C.c_void_p]),
+    "bags_resample_faces_backward": (C.c_int, [C.POINTER(BagsFaces), c_fp] + [C.c_int32] * 6 + [c_fp, c_fp, C.c_void_p, C.c_size_t,
+                                               C.POINTER(c_fp), c_fp, C.c_void_p]),
     "bags_activations_forward": (C.c_int, [C.POINTER(BagsRawGaussians)] + [C.c_void_p] * 5),
     "bags_activations_backward": (C.c_int, [C.POINTER(BagsRawGaussians)] + [C.c_void_p] * 10),
     "bags_sh_colors_workspace_size": (C.c_size_t, [C.c_int32]),

@@ -744,6 +744,54 @@ int bags_resample_backward(const float* image, int32_t C, int32_t H, int32_t W, 
     return BAGS_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- cubemap stitch
+static int check_faces(const char* who, const BagsFaces* f, int h, int w, int Hf, int Wf, int Hc, int Wc)
+{
+    if (!f) return fail(BAGS_ERR_ARG, "%s: null BagsFaces", who);
+    if (f->n_faces < 1 || f->n_faces > BAGS_MAX_FACES)
+        return fail(BAGS_ERR_ARG, "%s: n_faces %d outside 1..%d", who, f->n_faces, BAGS_MAX_FACES);
+    if (f->C <= 0 || f->H <= 0 || f->W <= 0 || h <= 0 || w <= 0 || Hf <= 0 || Wf <= 0 || Hc <= 0 || Wc <= 0)
+        return fail(BAGS_ERR_ARG, "%s: every extent must be positive", who);
+    if (f->C > 4) return fail(BAGS_ERR_ARG, "%s: at most 4 channels per face (got %d)", who, f->C);
+    if (Hc > Hf || Wc > Wf) return fail(BAGS_ERR_ARG, "%s: crop %dx%d exceeds the flow size %dx%d", who, Wc, Hc, Wf, Hf);
+    if (f->H > 32000 || f->W > 32000) return fail(BAGS_ERR_ARG, "%s: face %dx%d too large (tap coordinates are kept as int16)", who, f->W, f->H);
+    for (int i = 0; i < f->n_faces; ++i)
+        if (!f->image[i]) return fail(BAGS_ERR_ARG, "%s: null image of face %d", who, i);
+    return BAGS_OK;
+}
+
+size_t bags_resample_faces_workspace_size(int32_t n_faces, int32_t H, int32_t W, int32_t Hc, int32_t Wc)
+{
+    if (n_faces < 1 || n_faces > BAGS_MAX_FACES || H <= 0 || W <= 0 || Hc <= 0 || Wc <= 0) return 0;
+    return resample_faces_workspace_bytes(n_faces, H, W, Hc, Wc);
+}
+
+int bags_resample_faces_forward(const BagsFaces* f, const float* ctrl, int32_t h, int32_t w, int32_t Hf, int32_t Wf, int32_t Hc, int32_t Wc,
+                                float* out, int8_t* face_index, void* stream)
+{
+    int rc = check_faces("resample_faces_forward", f, h, w, Hf, Wf, Hc, Wc);
+    if (rc) return rc;
+    if (!ctrl || !out || !face_index) return fail(BAGS_ERR_ARG, "resample_faces_forward: null pointer");
+    HIP_TRY(launch_resample_faces_fwd(*f, ctrl, h, w, Hf, Wf, Hc, Wc, out, face_index, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
+int bags_resample_faces_backward(const BagsFaces* f, const float* ctrl, int32_t h, int32_t w, int32_t Hf, int32_t Wf, int32_t Hc, int32_t Wc,
+                                 const int8_t* face_index, const float* grad_out, void* workspace, size_t workspace_bytes,
+                                 float* const grad_faces[BAGS_MAX_FACES], float* grad_ctrl, void* stream)
+{
+    int rc = check_faces("resample_faces_backward", f, h, w, Hf, Wf, Hc, Wc);
+    if (rc) return rc;
+    if (!ctrl || !face_index || !grad_out) return fail(BAGS_ERR_ARG, "resample_faces_backward: null pointer");
+    bool any = grad_ctrl != nullptr;
+    for (int i = 0; grad_faces && i < f->n_faces; ++i) any |= grad_faces[i] != nullptr;
+    if (!any) return BAGS_OK;
+    const size_t need = resample_faces_workspace_bytes(f->n_faces, f->H, f->W, Hc, Wc);
+    if (!workspace || workspace_bytes < need) return fail(BAGS_ERR_SIZE, "resample_faces_backward: needs a workspace of %zu bytes", need);
+    HIP_TRY(launch_resample_faces_bwd(*f, ctrl, h, w, Hf, Wf, Hc, Wc, face_index, grad_out, workspace, grad_faces, grad_ctrl, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- activations
 static int check_raw(const BagsRawGaussians* r, bool features)      // features: the SH concatenation (or its gradient) is asked for
 {

@@ -283,6 +283,14 @@ hipError_t launch_resample_fwd(const float* image, int C, int H, int W, const fl
 hipError_t launch_resample_bwd(const float* image, int C, int H, int W, const float* ctrl, int h, int w, int Hf, int Wf, int Hc, int Wc,
                                const float* grad_out, void* workspace, float* grad_image, float* grad_ctrl, hipStream_t st);
 size_t resample_workspace_bytes(int H, int W, int Hc, int Wc);
+hipError_t launch_resample_ctrl_gather(int h, int w, int Hf, int Wf, int Hc, int Wc, const float2* gflow, float* grad_ctrl, hipStream_t st);
+// resample_faces.hip: the same warp from the F faces of a cubemap, stitched (first valid face per pixel), and the adjoint
+hipError_t launch_resample_faces_fwd(const BagsFaces& f, const float* ctrl, int h, int w, int Hf, int Wf, int Hc, int Wc, float* out,
+                                     int8_t* face_index, hipStream_t st);
+hipError_t launch_resample_faces_bwd(const BagsFaces& f, const float* ctrl, int h, int w, int Hf, int Wf, int Hc, int Wc,
+                                     const int8_t* face_index, const float* grad_out, void* workspace, float* const* grad_faces,
+                                     float* grad_ctrl, hipStream_t st);
+size_t resample_faces_workspace_bytes(int F, int H, int W, int Hc, int Wc);
 // activations.hip: cat / sigmoid / exp / normalize of the raw Gaussian parameters, and the adjoint
 hipError_t launch_activations_fwd(int P, int K, const float* dc, const float* rest, const float* opacity, const float* scaling,
                                   const float* rotation, float* shs, float* o_opacity, float* o_scales, float* o_rot, hipStream_t st);

@@ -12,50 +12,7 @@
 // dL/d(control flow) per control node.
 // The crop is taken as exact integer indexing (the reference's second grid_sample reproduces integer positions only to
 // ~1e-4 px after normalising and un-normalising the grid; the difference is below 2e-4 of the image range).
-#include "bags_common.h"
-
-struct ResampleGeom {
-    int C, H, W;          // image
-    int h, w;             // control grid of the flow
-    int Hf, Wf;           // size the flow is upsampled to (= size of the warped image before the crop)
-    int Hc, Wc;           // centre crop
-    int y0, x0;           // crop origin inside (Hf, Wf)
-};
-
-struct FlowTap { int i00, i01, i10, i11; float w00, w01, w10, w11; };
-
-// bilinear upsampling source taps of F.interpolate(align_corners=False) at destination (Y, X)
-__device__ __forceinline__ FlowTap flow_taps(const ResampleGeom& g, int Y, int X)
-{
-    const float sy = fmaxf(((float)Y + 0.5f) * ((float)g.h / (float)g.Hf) - 0.5f, 0.f);
-    const float sx = fmaxf(((float)X + 0.5f) * ((float)g.w / (float)g.Wf) - 0.5f, 0.f);
-    const int y0 = min((int)sy, g.h - 1), x0 = min((int)sx, g.w - 1);
-    const int y1 = y0 + (y0 < g.h - 1), x1 = x0 + (x0 < g.w - 1);
-    const float ly = sy - (float)y0, lx = sx - (float)x0;
-    FlowTap t;
-    t.i00 = y0 * g.w + x0; t.i01 = y0 * g.w + x1; t.i10 = y1 * g.w + x0; t.i11 = y1 * g.w + x1;
-    t.w00 = (1.f - ly) * (1.f - lx); t.w01 = (1.f - ly) * lx; t.w10 = ly * (1.f - lx); t.w11 = ly * lx;
-    return t;
-}
-
-struct ImgTap { int x0, y0; float fx, fy; bool in00, in01, in10, in11; };
-
-// grid_sample(align_corners=True, zeros padding) taps for the normalised coordinate (gx, gy)
-__device__ __forceinline__ ImgTap img_taps(const ResampleGeom& g, float gx, float gy)
-{
-    const float ix = (gx + 1.f) * 0.5f * (float)(g.W - 1), iy = (gy + 1.f) * 0.5f * (float)(g.H - 1);
-    const float fx0 = floorf(ix), fy0 = floorf(iy);
-    ImgTap t;
-    // far-away coordinates (|ix| beyond int range) are simply out of bounds
-    t.x0 = (fx0 > -2.f && fx0 < (float)g.W + 1.f) ? (int)fx0 : -2;
-    t.y0 = (fy0 > -2.f && fy0 < (float)g.H + 1.f) ? (int)fy0 : -2;
-    t.fx = ix - fx0; t.fy = iy - fy0;
-    const bool xa = t.x0 >= 0 && t.x0 < g.W, xb = t.x0 + 1 >= 0 && t.x0 + 1 < g.W;
-    const bool ya = t.y0 >= 0 && t.y0 < g.H, yb = t.y0 + 1 >= 0 && t.y0 + 1 < g.H;
-    t.in00 = xa && ya; t.in01 = xb && ya; t.in10 = xa && yb; t.in11 = xb && yb;
-    if (!isfinite(ix) || !isfinite(iy)) { t.in00 = t.in01 = t.in10 = t.in11 = false; t.fx = t.fy = 0.f; }
-    return t;
-}
+#include "resample_taps.h"
 
 __global__ void __launch_bounds__(256)
 resample_fwd_kernel(ResampleGeom g, const float* __restrict__ image, const float* __restrict__ ctrl,
@@ -106,8 +63,6 @@ resample_fwd_kernel(ResampleGeom g, const float* __restrict__ image, const float
 //      tiles, i.e. far below fp32 resolution of the result.  Every source tile is written (zeros where nothing lands): no
 //      memset of dL/dimage.  A source tile whose list overflows RS_CAP (extreme minification: dozens of output tiles
 //      sampling one source tile) ignores the list and tests the boxes of all output tiles instead: slow, exact.
-#define RS_TILE 16
-#define RS_CAP 32
 struct RsWork { float2* gflow; int4* bbox; float* tmax; u32* count; u32* list; float4* taps; };
 // What the pixels kernel leaves for the gather per OUTPUT pixel: the four bilinear taps of its sample, (x0 | y0 << 16 as int16s,
 // fx, fy, 0).  The gather used to re-derive them per listed tile (upsampling taps of the control flow -> four control-node loads
@@ -235,13 +190,8 @@ resample_gather_kernel(ResampleGeom g, const float* __restrict__ ctrl, const flo
                 // in this source tile (and hence inside the image: every source tile is clipped by the write-out below)?
                 if (lx < 0 || lx >= RS_TILE || ly < 0 || ly >= RS_TILE || sx >= g.W || sy >= g.H) continue;
                 for (int ch = 0; ch < g.C; ++ch) {
-                    const float v = w[q] * go[ch];                                                  // the term, as the scatter form had it
-                    const float x = v * up;                                                         // exact (power of two), |x| < 2^24
-                    const int hi = (int)x;                                                          // integer part
-                    const int lo = (int)((x - (float)hi) * 16777216.0f);                            // 24 more fractional bits, exact
-                    const long long fx = shift >= 24 ? (((long long)hi << 24) + (long long)lo) << (shift - 24)
-                                                     : (((long long)hi << 24) + (long long)lo) >> (24 - shift);
-                    atomicAdd(&acc[ch * 256 + ly * RS_TILE + lx], (unsigned long long)fx);
+                    // the term, as the scatter form had it, in fixed point (resample_taps.h)
+                    atomicAdd(&acc[ch * 256 + ly * RS_TILE + lx], rs_fixed(w[q] * go[ch], up, shift));
                 }
             }
         };
@@ -293,13 +243,7 @@ resample_gather_kernel(ResampleGeom g, const float* __restrict__ ctrl, const flo
                     const int lx = sx - X0, ly = sy - Y0;
                     if (lx < 0 || lx >= RS_TILE || ly < 0 || ly >= RS_TILE || sx >= g.W || sy >= g.H) continue;
                     for (int ch = 0; ch < g.C; ++ch) {
-                        const float v = w[q] * go[ch];
-                        const float x = v * up;
-                        const int hi = (int)x;
-                        const int lo = (int)((x - (float)hi) * 16777216.0f);
-                        const long long fx = shift >= 24 ? (((long long)hi << 24) + (long long)lo) << (shift - 24)
-                                                         : (((long long)hi << 24) + (long long)lo) >> (24 - shift);
-                        atomicAdd(&acc[ch * 256 + ly * RS_TILE + lx], (unsigned long long)fx);
+                        atomicAdd(&acc[ch * 256 + ly * RS_TILE + lx], rs_fixed(w[q] * go[ch], up, shift));
                     }
                 }
             }
@@ -348,10 +292,12 @@ resample_ctrl_gather_kernel(ResampleGeom g, const float2* __restrict__ gflow, fl
     if (lane == 0) { grad_ctrl[2 * node] = ax; grad_ctrl[2 * node + 1] = ay; }
 }
 
-static ResampleGeom make_geom(int C, int H, int W, int h, int w, int Hf, int Wf, int Hc, int Wc)
+// the control-node gather on its own, for resample_faces.hip: gflow is (Hc, Wc), zero where a pixel has no sample
+hipError_t launch_resample_ctrl_gather(int h, int w, int Hf, int Wf, int Hc, int Wc, const float2* gflow, float* grad_ctrl, hipStream_t st)
 {
-    ResampleGeom g{C, H, W, h, w, Hf, Wf, Hc, Wc, (Hf - Hc) / 2, (Wf - Wc) / 2};
-    return g;
+    const ResampleGeom g = make_geom(0, 0, 0, h, w, Hf, Wf, Hc, Wc);
+    hipLaunchKernelGGL(resample_ctrl_gather_kernel, dim3(h * w), dim3(64), 0, st, g, gflow, grad_ctrl);
+    return hipGetLastError();
 }
 
 hipError_t launch_resample_fwd(const float* image, int C, int H, int W, const float* ctrl, int h, int w, int Hf, int Wf, int Hc, int Wc,

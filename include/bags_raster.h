@@ -368,6 +368,34 @@ int bags_resample_backward(const float* image, int32_t C, int32_t H, int32_t W, 
                            int32_t flow_H, int32_t flow_W, int32_t crop_H, int32_t crop_W, const float* grad_out,
                            void* workspace, size_t workspace_bytes, float* grad_image, float* grad_ctrl, void* stream);
 
+/* The cubemap stitch (utils/cubemap_utils.py:181-186,219-288; csrc/resample_faces.hip): the F <= BAGS_MAX_FACES
+ * perspective faces of one step, each (C,H,W) with C <= 4, warped into the distorted output image and stitched in one pass.
+ * Per cropped output pixel, with (gx, gy) the upsampled control flow there exactly as bags_resample_* compute it (grid_sample
+ * coordinates of the FRONT image):
+ *   (a, b, c) = mats[f] (gx, gy, 1)^T,  u = a / c,  v = b / c;  face f is valid iff c > 0 && |u| <= 1 && |v| <= 1  (a NaN: not valid)
+ *   the pixel belongs to the FIRST valid face in list order: image = bilinear sample of that face at (u, v) (grid_sample,
+ *   align_corners=True, zeros padding), face_index = f;  no valid face: image = 0 in every channel, face_index = -1.
+ * mats[f] = diag(1/tx_f, 1/ty_f, 1) R_f diag(tx_0, ty_0, 1), row-major: R_f rotates a ray of the front camera into face f's camera
+ * frame, tx / ty are the tangents of the half fields of view (index 0: the front camera, which ctrl_flow is meant for).  The
+ * matrices travel by value and are not differentiated.
+ * Backward: the choice is REPLAYED from face_index (the forward's output), never decided again.  grad_faces[f] (C,H,W), any of
+ * them NULL, is gathered per 16x16 tile of face f into a 64-bit fixed-point accumulator in LDS, every element written (zeros
+ * where nothing lands, a face no pixel chose all zeros: no memset needed); grad_ctrl (h,w,2), may be NULL, is gathered per
+ * control node through u = a/c, v = b/c.  No global float atomics: both are bitwise reproducible, and each is the same whichever
+ * others are asked for.  Workspace: bags_resample_faces_workspace_size bytes, caller-owned (0 for invalid arguments). */
+#define BAGS_MAX_FACES 8
+typedef struct BagsFaces {
+    int32_t n_faces, C, H, W;            /* 1..BAGS_MAX_FACES faces of (C,H,W), C <= 4 */
+    const float* image[BAGS_MAX_FACES];  /* the first n_faces given */
+    float mats[BAGS_MAX_FACES][9];
+} BagsFaces;
+size_t bags_resample_faces_workspace_size(int32_t n_faces, int32_t H, int32_t W, int32_t crop_H, int32_t crop_W);
+int bags_resample_faces_forward(const BagsFaces* faces, const float* ctrl_flow, int32_t h, int32_t w, int32_t flow_H, int32_t flow_W,
+                                int32_t crop_H, int32_t crop_W, float* out, int8_t* face_index, void* stream);
+int bags_resample_faces_backward(const BagsFaces* faces, const float* ctrl_flow, int32_t h, int32_t w, int32_t flow_H, int32_t flow_W,
+                                 int32_t crop_H, int32_t crop_W, const int8_t* face_index, const float* grad_out, void* workspace,
+                                 size_t workspace_bytes, float* const grad_faces[BAGS_MAX_FACES], float* grad_ctrl, void* stream);
+
 /* The parameter activations that feed the op, one launch each way: GaussianModel.get_features
  * (cat of features_dc and features_rest), get_opacity (sigmoid), get_scaling (exp), get_rotation (normalize) --
  * scene/gaussian_model.py:118-141.  K = SH coefficients per Gaussian (1 + rest).  Outputs / gradients may be NULL; with
