@@ -3,11 +3,11 @@
 Mirrors the operator API of the reference's ``diff_gaussian_rasterization`` package
 (gaussian_renderer/__init__.py:14,50-65,110-121): ``GaussianRasterizationSettings``, ``GaussianRasterizer``.
 """
-from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, rasterize_gaussians, debug_views,
-                         compute_relocation)
+from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, rasterize_gaussians, debug_views
 
 from .render import render, render_views, PipelineParams
 from .gaussians import GaussianBag, eval_sh, sh_colors, sh_colors_views
+from .mcmc import compute_relocation, compute_relocation_torch, relocation_binoms
 from .io import save_ply, load_ply, save_checkpoint, load_checkpoint
 from .optim import GaussianAdam
 from .pose_bank import PoseBank, PoseAdam
@@ -15,7 +15,8 @@ from .lens_field import LensField, lens_field, lens_field_torch
 from .distortion import resample_faces, resample_faces_torch, cube_face_matrices
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "debug_views",
-           "compute_relocation", "render", "render_views", "PipelineParams", "GaussianBag", "eval_sh", "sh_colors", "sh_colors_views",
+           "compute_relocation", "compute_relocation_torch", "relocation_binoms", "render", "render_views", "PipelineParams",
+           "GaussianBag", "eval_sh", "sh_colors", "sh_colors_views",
            "save_ply", "load_ply", "save_checkpoint", "load_checkpoint", "GaussianAdam",
            "PoseBank", "PoseAdam", "LensField", "lens_field", "lens_field_torch",
            "resample_faces", "resample_faces_torch", "cube_face_matrices"]

@@ -156,6 +156,14 @@ class BagsDensifyGroup(C.Structure):
                 ("exp_avg_sq_out", c_fp), ("width", C.c_int32), ("role", C.c_int32)]
 
 
+MCMC_MAX_BINOMS = 51
+
+
+class BagsMcmcGroup(C.Structure):           # relocate: in place (the outputs unused); add_new: the (P + n_sampled)-row outputs
+    _fields_ = [("param", c_fp), ("exp_avg", c_fp), ("exp_avg_sq", c_fp), ("param_out", c_fp), ("exp_avg_out", c_fp),
+                ("exp_avg_sq_out", c_fp), ("width", C.c_int32), ("role", C.c_int32)]
+
+
 LENS_MAX_HIDDEN, LENS_MAX_INTERNAL_LAYERS, LENS_MAX_BLOCKS = 64, 4, 32
 
 
@@ -241,6 +249,12 @@ SYMBOLS = {    "bags_abi_version": (C.c_int, []),
     "bags_knn_workspace_size": (C.c_size_t, [C.c_int32]),
     "bags_knn_mean_dist2": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "bags_compute_relocation": (C.c_int, [c_fp, c_fp, c_fp, c_fp, C.c_int32, C.c_int32, c_fp, c_fp, C.c_void_p]),
+    "bags_mcmc_workspace_size": (C.c_size_t, [C.c_int32]),
+    "bags_mcmc_relocate": (C.c_int, [C.POINTER(BagsMcmcGroup), C.c_int32, C.c_int32, c_fp, c_fp, C.c_int32, c_fp, C.c_int32, C.c_double,
+                                     C.c_void_p, C.c_size_t, C.c_void_p]),
+    "bags_mcmc_add_new": (C.c_int, [C.POINTER(BagsMcmcGroup), C.c_int32, C.c_int32, c_fp, C.c_int32, c_fp, C.c_int32, C.c_double,
+                                    C.c_void_p, C.c_size_t, c_fp, c_fp, c_fp, C.c_void_p]),
+    "bags_mcmc_noise": (C.c_int, [c_fp, c_fp, c_fp, c_fp, C.c_int32, c_fp, C.c_uint64] + [C.c_double] * 4 + [C.c_void_p]),
 }
 
 _lib = None

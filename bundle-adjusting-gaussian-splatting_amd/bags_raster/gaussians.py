@@ -13,7 +13,8 @@ Host-side mirror of the pieces of the reference's ``GaussianModel`` that sit on 
 Everything here is device-agnostic torch (the reference hard-codes ``device="cuda"``); values are pinned by
 tests/golden/{sh_basis,gaussian_activations}.npz, generated from the reference's own functions.
 ``GaussianBag.densify_and_prune`` and ``GaussianBag.reset_opacity`` (scene/gaussian_model.py:393-447 and ``reset_opacity``) are
-fused HIP calls (csrc/densify.hip) and, unlike the rest of this module, run only on a GPU; the optimizer step is
+fused HIP calls (csrc/densify.hip), as are the three call sites of the 3DGS-MCMC strategy, ``GaussianBag.relocate`` / ``add_new`` /
+``mcmc_noise`` (csrc/mcmc.hip); unlike the rest of this module they run only on a GPU.  The optimizer step is
 ``bags_raster.optim.GaussianAdam``, PLY / checkpoint I/O ``bags_raster.io``.
 """
 from __future__ import annotations
@@ -24,6 +25,7 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import _lib as L
+from .mcmc import N_MAX, relocation_binoms
 
 SH_C0 = 0.28209479177387814
 _SH_C1 = 0.4886025119029199
@@ -315,6 +317,154 @@ class GaussianBag:
                     raise RuntimeError(f"{what}: {key} has shape {tuple(t.shape)} on {t.device}, _opacity {tuple(p.shape)} on {p.device}")
         L.call("bags_reset_opacity", p.device, p.data_ptr(), L.ptr(m), L.ptr(v), p.numel())
         p.grad = None
+
+    # ---- the 3DGS-MCMC strategy (train.py:366-367 under --mcmc, and its noise block): csrc/mcmc.hip
+    def _mcmc_groups(self, what: str, found):
+        """The six groups' parameters and moments as the MCMC kernels take them: ``_ARG``, on one device, the set's row count."""
+        P, dev = self._xyz.shape[0], self._xyz.device
+        for n, (_, p, st) in found.items():
+            for key, t in (("parameter", p),) + ((("exp_avg", st["exp_avg"]), ("exp_avg_sq", st["exp_avg_sq"])) if st is not None else ()):
+                L.require(what, f"{key} of group {n!r}", t, **self._ARG)
+                if t.shape != p.shape or t.shape[0] != P or t.device != dev:
+                    raise RuntimeError(f"{what}: {key} of group {n!r} has shape {tuple(t.shape)} on {t.device}, expected {(P,) + tuple(p.shape[1:])} on {dev}")
+
+    def _mcmc_struct(self, found, outs=None):
+        gs = []
+        for n, (_, p, st) in found.items():
+            m, v = (st["exp_avg"], st["exp_avg_sq"]) if st is not None else (None, None)
+            o = outs[n] if outs is not None else (None, None, None)
+            width = int(math.prod(p.shape[1:]))
+            if width:                                                             # (SH degree 0: _features_rest is (P,0,3), nothing to move)
+                gs.append(L.BagsMcmcGroup(p.data_ptr(), L.ptr(m), L.ptr(v), L.ptr(o[0]), L.ptr(o[1]), L.ptr(o[2]), width, self._GROUPS[n][1]))
+        return (L.BagsMcmcGroup * len(gs))(*gs), len(gs)
+
+    @staticmethod
+    def _mcmc_rows(what: str, name: str, rows, P: int, like, count=None):
+        """``rows``: an int32 / int64 vector of row numbers in 0..P-1 on the device of ``like``; checked where it lives."""
+        L.require(what, name, rows, on=like)
+        if rows.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"{what}: {name} must be int32 or int64, got {rows.dtype}")
+        if rows.dim() != 1 or (count is not None and rows.numel() != count):
+            raise RuntimeError(f"{what}: {name} must be a vector" + (f" of {count} rows" if count is not None else "") + f", got shape {tuple(rows.shape)}")
+        if rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= P):
+            raise IndexError(f"{what}: {name} holds rows outside 0..{P - 1}")
+
+    @staticmethod
+    def _mcmc_sample(p, n: int, generator):
+        """``n`` draws from the rows of ``p`` (opacities, any positive weights) in proportion to them, with replacement: the
+        published ``_sample_alives``."""
+        return torch.multinomial(p / p.sum(), n, replacement=True, generator=generator)
+
+    @torch.no_grad()
+    def relocate(self, optimizer, dead_mask, sampled=None, generator=None, min_opacity: float = 0.005):
+        """The published ``relocate_gs``, in place, in three HIP launches: every dead row (``dead_mask (P,)`` bool) is moved onto an
+        alive row drawn in proportion to its opacity, and the opacity and scale of the rows drawn are corrected so that the
+        rendering is kept (``compute_relocation`` with the count of draws + 1; the opacity clamped to
+        ``[min_opacity, 1 - eps]``).  Dead row j takes every parameter of ``sampled[j]``; the sources get the same new ``_opacity`` and
+        ``_scaling``, and their ``exp_avg`` / ``exp_avg_sq`` are zeroed in all six groups; dead rows keep their moments and ``step``
+        stays, as published.  No other row is touched.
+
+        ``sampled`` ``(D,)``, D the number of dead rows: the source of each dead row, in the order of the dead rows; it must list
+        alive rows.  None: drawn here with ``torch.multinomial`` under ``generator``; on a GPU that draw does not repeat bit for bit at
+        large P (its prefix sum does not), so view-sharded ranks draw once and pass one tensor.
+        No dead rows, or no alive ones: nothing happens.  Returns ``{"dead": D, "sources": distinct rows drawn}``."""
+        what = "GaussianBag.relocate"
+        found = self._named_groups(optimizer, what)
+        P = self._xyz.shape[0]
+        L.require(what, "dead_mask", dead_mask, on=self._xyz)
+        if dead_mask.dtype != torch.bool:
+            raise TypeError(f"{what}: dead_mask must be bool, got {dead_mask.dtype}")
+        if tuple(dead_mask.shape) != (P,):
+            raise RuntimeError(f"{what}: dead_mask must be ({P},), got {tuple(dead_mask.shape)}")
+        D = int(dead_mask.sum())
+        if sampled is not None:
+            self._mcmc_rows(what, "sampled", sampled, P, dead_mask, count=D)
+            if D and bool(dead_mask[sampled.long()].any()):
+                raise ValueError(f"{what}: sampled lists a dead row; the sources must be alive")
+        self._mcmc_groups(what, found)
+        if D == 0 or D == P:
+            return {"dead": D, "sources": 0}
+        dev = self._xyz.device
+        dead = dead_mask.nonzero().reshape(-1)
+        if sampled is None:
+            alive = (~dead_mask).nonzero().reshape(-1)
+            sampled = alive[self._mcmc_sample(torch.sigmoid(self._opacity.detach()[alive, 0]), D, generator)]
+        groups, n = self._mcmc_struct(found)
+        dead32, sampled32 = dead.to(torch.int32), sampled.to(torch.int32).contiguous()
+        ws = L.workspace(L.load().bags_mcmc_workspace_size(P), dev)
+        L.call("bags_mcmc_relocate", dev, groups, n, P, dead32.data_ptr(), sampled32.data_ptr(), D, relocation_binoms(N_MAX, dev).data_ptr(), N_MAX,
+               float(min_opacity), ws.data_ptr(), ws.numel())
+        return {"dead": D, "sources": int(torch.unique(sampled32).numel())}
+
+    @torch.no_grad()
+    def add_new(self, optimizer, cap_max: int, sampled=None, generator=None, min_opacity: float = 0.005):
+        """The published ``add_new_gs`` with its optimizer surgery, in three HIP launches: the set grows by 5 % up to ``cap_max`` rows,
+        ``A = max(0, min(cap_max, int(1.05 * P)) - P)`` new rows, each a copy of a row drawn in proportion to its opacity; the rows
+        drawn and their copies get the corrected opacity and scale of ``relocate``.  New ``nn.Parameter`` s are installed in the bag
+        and in ``group["params"][0]`` as ``densify_and_prune`` installs them: old rows bit for bit (but the sources' opacity, scaling
+        and zeroed moments), new rows' moments zero, ``step`` unchanged, the three statistics zeros of the new size.
+
+        ``sampled`` ``(A,)``: the source of each new row (any rows of the set); None: drawn here.  ``A == 0``: nothing happens.
+        Returns ``{"added": A, "P_new": P + A}``."""
+        what = "GaussianBag.add_new"
+        found = self._named_groups(optimizer, what)
+        P = self._xyz.shape[0]
+        A = max(0, min(int(cap_max), int(1.05 * P)) - P)
+        if sampled is not None:
+            self._mcmc_rows(what, "sampled", sampled, P, self._xyz, count=A)
+        self._mcmc_groups(what, found)
+        if A == 0:
+            return {"added": 0, "P_new": P}
+        dev = self._xyz.device
+        if sampled is None:
+            sampled = self._mcmc_sample(torch.sigmoid(self._opacity.detach()[:, 0]), A, generator)
+        P_new = P + A
+        new = {}
+        for n, (_, p, st) in found.items():
+            shape = (P_new,) + tuple(p.shape[1:])
+            new[n] = [torch.empty(shape, dtype=torch.float32, device=dev) for _ in range(3 if st is not None else 1)] + [None, None]
+        groups, n_groups = self._mcmc_struct(found, new)
+        accum = torch.empty(P_new, 1, dtype=torch.float32, device=dev)
+        denom = torch.empty(P_new, 1, dtype=torch.float32, device=dev)
+        radii = torch.empty(P_new, dtype=torch.float32, device=dev)
+        sampled32 = sampled.to(torch.int32).contiguous()
+        ws = L.workspace(L.load().bags_mcmc_workspace_size(P), dev)
+        L.call("bags_mcmc_add_new", dev, groups, n_groups, P, sampled32.data_ptr(), A, relocation_binoms(N_MAX, dev).data_ptr(), N_MAX, float(min_opacity),
+               ws.data_ptr(), ws.numel(), accum.data_ptr(), denom.data_ptr(), radii.data_ptr())
+        for n, (group, p, st) in found.items():
+            param = torch.nn.Parameter(new[n][0].requires_grad_(True))
+            if p in optimizer.state:
+                stored = optimizer.state.pop(p)
+                if st is not None:
+                    stored["exp_avg"], stored["exp_avg_sq"] = new[n][1], new[n][2]
+                optimizer.state[param] = stored
+            group["params"][0] = param
+            setattr(self, self._GROUPS[n][0], param)
+        self.xyz_gradient_accum, self.denom, self.max_radii2D = accum, denom, radii
+        return {"added": A, "P_new": P_new}
+
+    @torch.no_grad()
+    def mcmc_noise(self, scale: float, noise: Optional[torch.Tensor] = None, seed: Optional[int] = None, k: float = 100.0, x0: float = 0.995,
+                   scaling_modifier: float = 1.0) -> None:
+        """The per-iteration SGLD step of the MCMC strategy (train.py's ``noise_lr * xyz_lr`` block) in one HIP launch, in place on
+        ``_xyz``: ``_xyz += Sigma (z * g * scale)`` with ``g = 1 / (1 + exp(-k ((1 - sigmoid(_opacity)) - x0)))`` and
+        ``Sigma = R diag(s^2) R^T``, ``s = scaling_modifier * exp(_scaling)``.  Only the new ``_xyz`` is written; no covariance is
+        built in memory.  ``z``: ``noise (P,3)``, or three standard normals per row from the generator of ``densify_and_prune`` keyed
+        by ``(seed, row)`` -- the same bits from the same seed on every rank; ``seed`` None: drawn from torch's CPU generator."""
+        what = "GaussianBag.mcmc_noise"
+        P, dev = self._xyz.shape[0], self._xyz.device
+        for name, t, w in (("_xyz", self._xyz, 3), ("_opacity", self._opacity, 1), ("_scaling", self._scaling, 3), ("_rotation", self._rotation, 4)):
+            L.require(what, name, t, **self._ARG)
+            if tuple(t.shape) != (P, w) or t.device != dev:
+                raise RuntimeError(f"{what}: {name} must be ({P}, {w}) on {dev}, got {tuple(t.shape)} on {t.device}")
+        if noise is not None:
+            L.require(what, "noise", noise, **self._ARG)
+            if tuple(noise.shape) != (P, 3) or noise.device != dev:
+                raise RuntimeError(f"{what}: noise must be ({P}, 3) on {dev}, got {tuple(noise.shape)} on {noise.device}")
+        elif seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+        L.call("bags_mcmc_noise", dev, self._xyz.data_ptr(), self._opacity.data_ptr(), self._scaling.data_ptr(), self._rotation.data_ptr(), P, L.ptr(noise),
+               (0 if seed is None else int(seed)) & (2 ** 64 - 1), float(scale), float(k), float(x0), float(scaling_modifier))
 
     # ---- consumers of the op's screen-space gradients (scene/gaussian_model.py:449-455)
     def add_densification_stats(self, viewspace_point_tensor, viewspace_point_tensor_densify, update_filter, abs_grad: bool):

@@ -803,8 +803,3 @@ def debug_views(settings: GaussianRasterizationSettings, means3D, means2D, shift
         v["num_rendered"] = I
         v["outputs"] = outs
     return v
-
-
-def compute_relocation(opacity_old, scale_old, N, binoms, n_max):
-    """utils/reloc_utils.py:11-13.  The reference's only caller is commented out (scene/gaussian_model.py:23,494-504)."""
-    raise NotImplementedError("compute_relocation is not part of the accelerated path (MCMC relocation is disabled in the reference)")

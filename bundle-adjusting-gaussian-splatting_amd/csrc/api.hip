@@ -1134,9 +1134,101 @@ int bags_knn_mean_dist2(const float* points, int32_t P, void* workspace, size_t 
     return BAGS_OK;
 }
 
-int bags_compute_relocation(const float*, const float*, const int32_t*, const float*, int32_t, int32_t, float*, float*, void*)
+// ---------------------------------------------------------------------------------------------- MCMC relocation, growth and noise
+static int check_binoms(const char* op, const float* binoms, int32_t n_max)
 {
-    return fail(BAGS_ERR_ARG, "compute_relocation: the reference's only caller is commented out (scene/gaussian_model.py:23,494-504); not implemented");
+    if (!binoms) return fail(BAGS_ERR_ARG, "%s: NULL binoms", op);
+    if (n_max < 2 || n_max > BAGS_MCMC_MAX_BINOMS) return fail(BAGS_ERR_ARG, "%s: n_max %d not in 2..%d", op, n_max, BAGS_MCMC_MAX_BINOMS);
+    return BAGS_OK;
+}
+
+int bags_compute_relocation(const float* opacity_old, const float* scale_old, const int32_t* N, const float* binoms, int32_t n_max, int32_t P,
+                            float* opacity_new, float* scale_new, void* stream)
+{
+    if (const int rc = check_binoms("compute_relocation", binoms, n_max)) return rc;
+    if (P < 0) return fail(BAGS_ERR_ARG, "compute_relocation: P < 0 (got %d)", P);
+    if (P == 0) return BAGS_OK;
+    if (!opacity_old || !scale_old || !N) return fail(BAGS_ERR_ARG, "compute_relocation: NULL opacity_old / scale_old / N");
+    if (!opacity_new || !scale_new) return fail(BAGS_ERR_ARG, "compute_relocation: NULL opacity_new / scale_new");
+    HIP_TRY(launch_compute_relocation(opacity_old, scale_old, N, binoms, n_max, P, opacity_new, scale_new, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
+size_t bags_mcmc_workspace_size(int32_t P) { return mcmc_workspace_bytes(P); }
+
+// what relocate and add_new share; outputs: add_new's (P + n_sampled)-row arrays are checked too
+static int check_mcmc(const char* op, const BagsMcmcGroup* groups, int32_t n_groups, int32_t P, const int32_t* sampled, int32_t n_sampled,
+                      const float* binoms, int32_t n_max, double min_opacity, const void* workspace, size_t workspace_bytes, bool outputs)
+{
+    if (const int rc = check_binoms(op, binoms, n_max)) return rc;
+    if (P < 0) return fail(BAGS_ERR_ARG, "%s: P < 0 (got %d)", op, P);
+    if (n_sampled < 0) return fail(BAGS_ERR_ARG, "%s: n_sampled < 0 (got %d)", op, n_sampled);
+    if (!(min_opacity > 0.0 && min_opacity < 1.0)) return fail(BAGS_ERR_ARG, "%s: min_opacity %g not in (0, 1)", op, min_opacity);
+    if (n_groups < 1 || n_groups > BAGS_DENSIFY_MAX_GROUPS) return fail(BAGS_ERR_ARG, "%s: n_groups %d not in 1..%d", op, n_groups, BAGS_DENSIFY_MAX_GROUPS);
+    if (!groups) return fail(BAGS_ERR_ARG, "%s: NULL groups", op);
+    if (outputs && (int64_t)P + n_sampled > 0x7FFFFFFFll) return fail(BAGS_ERR_SIZE, "%s: the new set would hold %lld rows (> 2^31 - 1)", op, (long long)P + n_sampled);
+    const bool work = P > 0 && n_sampled > 0;
+    int n_opacity = 0, n_scaling = 0;
+    for (int k = 0; k < n_groups; ++k) {
+        const BagsMcmcGroup& g = groups[k];
+        if (g.width <= 0) return fail(BAGS_ERR_ARG, "%s: group %d: width %d <= 0", op, k, g.width);
+        if (g.role < BAGS_ROLE_OTHER || g.role > BAGS_ROLE_OPACITY) return fail(BAGS_ERR_ARG, "%s: group %d: unknown role %d", op, k, g.role);
+        const int want = g.role == BAGS_ROLE_XYZ || g.role == BAGS_ROLE_SCALING ? 3 : g.role == BAGS_ROLE_ROTATION ? 4 : g.role == BAGS_ROLE_OPACITY ? 1 : g.width;
+        if (g.width != want) return fail(BAGS_ERR_ARG, "%s: group %d: width %d, but its role %d has width %d", op, k, g.width, g.role, want);
+        n_opacity += g.role == BAGS_ROLE_OPACITY; n_scaling += g.role == BAGS_ROLE_SCALING;
+        if (!work) continue;
+        if (!g.param) return fail(BAGS_ERR_ARG, "%s: group %d: NULL param", op, k);
+        if ((g.exp_avg != nullptr) != (g.exp_avg_sq != nullptr)) return fail(BAGS_ERR_ARG, "%s: group %d: exp_avg and exp_avg_sq are given together or not at all", op, k);
+        if (outputs) {
+            if (!g.param_out) return fail(BAGS_ERR_ARG, "%s: group %d: NULL param_out", op, k);
+            if ((g.exp_avg != nullptr) != (g.exp_avg_out != nullptr) || (g.exp_avg != nullptr) != (g.exp_avg_sq_out != nullptr))
+                return fail(BAGS_ERR_ARG, "%s: group %d: exp_avg_out and exp_avg_sq_out are given exactly when the moments are", op, k);
+            if (misaligned16(g.param_out) || misaligned16(g.exp_avg_out) || misaligned16(g.exp_avg_sq_out))
+                return fail(BAGS_ERR_ARG, "%s: group %d: param_out / exp_avg_out / exp_avg_sq_out is not 16-byte aligned", op, k);
+        }
+    }
+    if (n_opacity != 1 || n_scaling != 1) return fail(BAGS_ERR_ARG, "%s: role opacity and scaling must each be given once (got %d, %d)", op, n_opacity, n_scaling);
+    if (!work) return BAGS_OK;
+    if (!sampled) return fail(BAGS_ERR_ARG, "%s: NULL sampled", op);
+    if (!workspace) return fail(BAGS_ERR_ARG, "%s: NULL workspace", op);
+    if (workspace_bytes < mcmc_workspace_bytes(P)) return fail(BAGS_ERR_SIZE, "%s: workspace %zu bytes < %zu", op, workspace_bytes, mcmc_workspace_bytes(P));
+    return BAGS_OK;
+}
+
+int bags_mcmc_relocate(const BagsMcmcGroup* groups, int32_t n_groups, int32_t P, const int32_t* dead, const int32_t* sampled, int32_t n_sampled,
+                       const float* binoms, int32_t n_max, double min_opacity, void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (const int rc = check_mcmc("mcmc_relocate", groups, n_groups, P, sampled, n_sampled, binoms, n_max, min_opacity, workspace, workspace_bytes, false)) return rc;
+    if (P == 0 || n_sampled == 0) return BAGS_OK;
+    if (!dead) return fail(BAGS_ERR_ARG, "mcmc_relocate: NULL dead");
+    HIP_TRY(launch_mcmc_relocate(groups, n_groups, P, dead, sampled, n_sampled, binoms, n_max, min_opacity, workspace, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
+int bags_mcmc_add_new(const BagsMcmcGroup* groups, int32_t n_groups, int32_t P, const int32_t* sampled, int32_t n_sampled, const float* binoms,
+                      int32_t n_max, double min_opacity, void* workspace, size_t workspace_bytes, float* accum_out, float* denom_out,
+                      float* radii_out, void* stream)
+{
+    if (const int rc = check_mcmc("mcmc_add_new", groups, n_groups, P, sampled, n_sampled, binoms, n_max, min_opacity, workspace, workspace_bytes, true)) return rc;
+    if (P == 0 || n_sampled == 0) return BAGS_OK;
+    if (!accum_out || !denom_out || !radii_out) return fail(BAGS_ERR_ARG, "mcmc_add_new: NULL xyz_gradient_accum_out / denom_out / max_radii2D_out");
+    if (misaligned16(accum_out) || misaligned16(denom_out) || misaligned16(radii_out))
+        return fail(BAGS_ERR_ARG, "mcmc_add_new: xyz_gradient_accum_out / denom_out / max_radii2D_out is not 16-byte aligned");
+    HIP_TRY(launch_mcmc_add_new(groups, n_groups, P, sampled, n_sampled, binoms, n_max, min_opacity, workspace, accum_out, denom_out, radii_out,
+                                (hipStream_t)stream));
+    return BAGS_OK;
+}
+
+int bags_mcmc_noise(float* xyz, const float* opacity, const float* scaling, const float* rotation, int32_t P, const float* noise, uint64_t seed,
+                    double scale, double k, double x0, double scaling_modifier, void* stream)
+{
+    if (P < 0) return fail(BAGS_ERR_ARG, "mcmc_noise: P < 0 (got %d)", P);
+    if (!(scale == scale) || !(k == k) || !(x0 == x0) || !(scaling_modifier == scaling_modifier))
+        return fail(BAGS_ERR_ARG, "mcmc_noise: scale / k / x0 / scaling_modifier is NaN");
+    if (P == 0) return BAGS_OK;
+    if (!xyz || !opacity || !scaling || !rotation) return fail(BAGS_ERR_ARG, "mcmc_noise: NULL xyz / opacity / scaling / rotation");
+    HIP_TRY(launch_mcmc_noise(xyz, opacity, scaling, rotation, P, noise, seed, scale, k, x0, scaling_modifier, (hipStream_t)stream));
+    return BAGS_OK;
 }
 
 }  // extern "C"

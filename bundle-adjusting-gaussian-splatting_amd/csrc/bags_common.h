@@ -317,6 +317,16 @@ hipError_t launch_densify_plan(const BagsDensifyRule& r, void* workspace, u32 ho
 hipError_t launch_densify_apply(const BagsDensifyRule& r, const BagsDensifyGroup* groups, int n_groups, void* workspace, long long P_new,
                                 float* accum_out, float* denom_out, float* radii_out, int32_t* provenance, hipStream_t st);
 hipError_t launch_reset_opacity(float* opacity, float* exp_avg, float* exp_avg_sq, int P, float cap, hipStream_t st);
+// mcmc.hip: compute_relocation, relocate / add_new of the MCMC strategy (count + stage, then one copy pass) and the SGLD noise step
+size_t mcmc_workspace_bytes(int P);
+hipError_t launch_compute_relocation(const float* opacity_old, const float* scale_old, const int32_t* N, const float* binoms, int n_max, int P,
+                                     float* opacity_new, float* scale_new, hipStream_t st);
+hipError_t launch_mcmc_relocate(const BagsMcmcGroup* groups, int n_groups, int P, const int32_t* dead, const int32_t* sampled, int n_sampled,
+                                const float* binoms, int n_max, double min_opacity, void* workspace, hipStream_t st);
+hipError_t launch_mcmc_add_new(const BagsMcmcGroup* groups, int n_groups, int P, const int32_t* sampled, int n_sampled, const float* binoms,
+                               int n_max, double min_opacity, void* workspace, float* accum_out, float* denom_out, float* radii_out, hipStream_t st);
+hipError_t launch_mcmc_noise(float* xyz, const float* opacity, const float* scaling, const float* rotation, int P, const float* noise, uint64_t seed,
+                             double scale, double k, double x0, double scaling_modifier, hipStream_t st);
 // lens_field.hip: the invertible-ResNet lens network on M points of R^2 (forward / fixed-point inverse in one launch, backward in two)
 __host__ __device__ static inline int lens_block_floats(int H, int n) { return 3 * H + n * (H * H + H) + 2 * H + 2; }   // of the flat vector, per block
 size_t lens_field_workspace_bytes(int B, int H, int n, long long M);

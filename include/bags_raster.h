@@ -630,10 +630,59 @@ int bags_lens_field_inverse(const BagsLensField* net, const float* y, int64_t M,
 size_t bags_knn_workspace_size(int32_t P);
 int bags_knn_mean_dist2(const float* points, int32_t P, void* workspace, size_t workspace_bytes, float* out, void* stream);
 
-/* compute_relocation of the fork's MCMC path (utils/reloc_utils.py:11-13): its only caller is commented out in
- * the reference (scene/gaussian_model.py:23,494-504); exported so the symbol exists, returns BAGS_ERR_ARG. */
+/* The 3DGS-MCMC densification strategy (csrc/mcmc.hip): compute_relocation of utils/reloc_utils.py, relocate_gs / add_new_gs of
+ * the reference's --mcmc path (train.py:366-367) and the per-iteration SGLD noise on xyz (train.py's noise_lr * xyz_lr block).
+ *
+ * compute_relocation, per row, with n = clamp(N, 1, n_max - 1) (clamped on read: N is not written):
+ *     opacity_new = 1 - (1 - opacity_old)^(1/n)
+ *     denom       = sum_{i=1..n} sum_{k=0..i-1} binoms[i-1][k] * (-1)^k / sqrt(k+1) * opacity_new^(k+1)
+ *     scale_new   = (opacity_old / denom) * scale_old
+ * binoms: (n_max, n_max) row-major, binoms[n][k] = C(n, k); n_max in 2..BAGS_MCMC_MAX_BINOMS.  The sums are formed in double, by
+ * column (sum_i binoms[i-1][k] is exact there), and every output is rounded to fp32 once.  A NULL binoms, an n_max outside its
+ * range and, with P > 0, a NULL input or output are argument errors, reported before any launch and also when P == 0; after that
+ * check P == 0 is a successful no-op. */
+#define BAGS_MCMC_MAX_BINOMS 51
 int bags_compute_relocation(const float* opacity_old, const float* scale_old, const int32_t* N, const float* binoms,
                             int32_t n_max, int32_t P, float* opacity_new, float* scale_new, void* stream);
+
+/* relocate_gs and add_new_gs.  `sampled` (n_sampled) lists source rows (repeats allowed); c[s] = how often s is listed.  Every
+ * listed row s gets (o', sc') = compute_relocation(sigmoid(opacity[s]), exp(scaling[s]), c[s] + 1), o' clamped to
+ * [min_opacity, 1 - FLT_EPSILON]; its opacity becomes logit(o'), its scaling log(sc'), and its exp_avg / exp_avg_sq are zeroed in
+ * every group that has them.  The new values are staged in the workspace from the old rows before any row is written.
+ *   relocate: in place.  Row dead[j] takes every parameter of row sampled[j] (opacity and scaling: the new ones), j = 0..n_sampled-1;
+ *             its moments stay.  dead and sampled must be disjoint and dead must not repeat (the caller's check: the rows are on
+ *             the device).  param_out / exp_avg_out / exp_avg_sq_out are not used.  Rows neither dead nor sampled are not touched.
+ *   add_new:  writes (P + n_sampled)-row outputs in one pass over the output elements: rows 0..P-1 are the old rows (sources
+ *             updated as above), row P + j is a copy of the updated row sampled[j] with zero moments; the three statistics arrays
+ *             of the new size are zero-filled.  Outputs must not alias inputs and are 16-byte aligned.
+ * roles: opacity and scaling must each be given exactly once (xyz and rotation are plain copies here).  workspace:
+ * bags_mcmc_workspace_size(P) bytes, no initialisation needed.  n_sampled == 0 (and P == 0) is a successful no-op. */
+typedef struct BagsMcmcGroup {
+    float* param;                    /* (P, width) */
+    float* exp_avg;                  /* (P, width), or NULL with exp_avg_sq (and both outputs): a group without optimizer state */
+    float* exp_avg_sq;
+    float* param_out;                /* add_new: (P + n_sampled, width) */
+    float* exp_avg_out;
+    float* exp_avg_sq_out;
+    int32_t width;                   /* floats per Gaussian, >= 1 */
+    int32_t role;                    /* BAGS_ROLE_* */
+} BagsMcmcGroup;
+size_t bags_mcmc_workspace_size(int32_t P);
+int bags_mcmc_relocate(const BagsMcmcGroup* groups, int32_t n_groups, int32_t P, const int32_t* dead, const int32_t* sampled,
+                       int32_t n_sampled, const float* binoms, int32_t n_max, double min_opacity, void* workspace,
+                       size_t workspace_bytes, void* stream);
+int bags_mcmc_add_new(const BagsMcmcGroup* groups, int32_t n_groups, int32_t P, const int32_t* sampled, int32_t n_sampled,
+                      const float* binoms, int32_t n_max, double min_opacity, void* workspace, size_t workspace_bytes,
+                      float* xyz_gradient_accum_out, float* denom_out, float* max_radii2D_out, void* stream);
+
+/* The SGLD step on xyz, in place, one launch, nothing per row but the new xyz written:
+ *     g = 1 / (1 + exp(-k * ((1 - sigmoid(opacity)) - x0)))
+ *     Sigma = R diag(s^2) R^T,  s = scaling_modifier * exp(scaling),  R from the normalised quaternion (w, x, y, z)
+ *     xyz += Sigma (z * g * scale)
+ * z: noise (P,3), or, with noise NULL, three standard normals from the generator of bags_densify_apply keyed by (seed, row, 0).
+ * Evaluated in double from the fp32 inputs and rounded once.  P == 0 is a successful no-op. */
+int bags_mcmc_noise(float* xyz, const float* opacity, const float* scaling, const float* rotation, int32_t P, const float* noise,
+                    uint64_t seed, double scale, double k, double x0, double scaling_modifier, void* stream);
 
 #ifdef __cplusplus
 }
