@@ -8,6 +8,7 @@ from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, raste
 from .render import render, render_views, PipelineParams
 from .gaussians import GaussianBag, eval_sh, sh_colors, sh_colors_views
 from .mcmc import compute_relocation, compute_relocation_torch, relocation_binoms
+from .antialias import antialias_opacity, antialias_opacity_torch
 from .io import save_ply, load_ply, save_checkpoint, load_checkpoint
 from .optim import GaussianAdam
 from .pose_bank import PoseBank, PoseAdam
@@ -15,7 +16,7 @@ from .lens_field import LensField, lens_field, lens_field_torch
 from .distortion import resample_faces, resample_faces_torch, cube_face_matrices
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "debug_views",
-           "compute_relocation", "compute_relocation_torch", "relocation_binoms", "render", "render_views", "PipelineParams",
+           "compute_relocation", "compute_relocation_torch", "relocation_binoms", "antialias_opacity", "antialias_opacity_torch", "render", "render_views", "PipelineParams",
            "GaussianBag", "eval_sh", "sh_colors", "sh_colors_views",
            "save_ply", "load_ply", "save_checkpoint", "load_checkpoint", "GaussianAdam",
            "PoseBank", "PoseAdam", "LensField", "lens_field", "lens_field_torch",

@@ -179,6 +179,13 @@ class BagsFaces(C.Structure):               # the faces of a cubemap: image poin
                 ("mats", (C.c_float * 9) * MAX_FACES)]
 
 
+class BagsAntialias(C.Structure):           # one view's inputs of the antialiasing factor (csrc/antialias.hip); None = NULL
+    _fields_ = [("P", C.c_int32), ("image_width", C.c_int32), ("image_height", C.c_int32), ("clamp_grad", C.c_int32),
+                ("tanfovx", C.c_float), ("tanfovy", C.c_float), ("scale_modifier", C.c_float), ("reserved", C.c_int32),
+                ("means3D", c_fp), ("scales", c_fp), ("rotations", c_fp), ("cov3D_precomp", c_fp), ("opacities", c_fp),
+                ("shift_factors", c_fp), ("viewmatrix", c_fp), ("intrinsic", c_fp)]
+
+
 SYMBOLS = {    "bags_abi_version": (C.c_int, []),
     "bags_build_info": (C.c_char_p, []),
     "bags_last_error": (C.c_char_p, []),
@@ -255,6 +262,9 @@ SYMBOLS = {    "bags_abi_version": (C.c_int, []),
     "bags_mcmc_add_new": (C.c_int, [C.POINTER(BagsMcmcGroup), C.c_int32, C.c_int32, c_fp, C.c_int32, c_fp, C.c_int32, C.c_double,
                                     C.c_void_p, C.c_size_t, c_fp, c_fp, c_fp, C.c_void_p]),
     "bags_mcmc_noise": (C.c_int, [c_fp, c_fp, c_fp, c_fp, C.c_int32, c_fp, C.c_uint64] + [C.c_double] * 4 + [C.c_void_p]),
+    "bags_antialias_forward": (C.c_int, [C.POINTER(BagsAntialias), c_fp, C.c_void_p]),
+    "bags_antialias_workspace_size": (C.c_size_t, [C.c_int32]),
+    "bags_antialias_backward": (C.c_int, [C.POINTER(BagsAntialias), c_fp, C.c_void_p, C.c_size_t] + [c_fp] * 8 + [C.c_void_p]),
 }
 
 _lib = None

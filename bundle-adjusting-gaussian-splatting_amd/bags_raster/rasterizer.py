@@ -56,6 +56,13 @@ class GaussianRasterizationSettings(NamedTuple):
     # backward of conic = cov2D^-1: "stock" = upstream's computeCov2DCUDA, which divides by det^2 + 1e-7 (the fork inherits it;
     # default since round 5); "exact" = det^2.  At most 1.2e-5 relative on one Gaussian's dL/dcov2D (det >= 0.09)
     conic_grad: str = "stock"
+    # upstream's `antialiasing` (Mip-Splatting's 2D filter): True multiplies every opacity by sqrt(det(cov2D) / det(cov2D + 0.3 I)),
+    # so that the 0.3 px^2 dilation does not add energy to splats smaller than a pixel (decision D10 of DESIGN.md).  It never reaches
+    # BagsSettings: GaussianRasterizer.forward replaces `opacities` by bags_raster.antialias_opacity(...) of the call's own inputs, one
+    # HIP launch each way in front of the operator.  The opacity input is then a non-leaf, so with ACCUMULATE_IN_PLACE the operator
+    # falls back to returning its gradients for autograd to chain; that is correct.  (Passed by keyword, as upstream's callers do; it
+    # stands in front of depth_weights_grad, which stays the last field.)
+    antialiasing: bool = False
     # True: the depth (1,H,W) = sum w z and weights (1,H,W) = 1 - T_final outputs are differentiable too (decision D5 of DESIGN.md:
     # depth-prior and alpha / mask losses; the depth term reaches the pose).  False (default): only the image is, as in the reference
     depth_weights_grad: bool = False
@@ -146,6 +153,7 @@ class _Packed:
             raise ValueError("conic_grad must be 'stock' or 'exact'")
         if not isinstance(settings.depth_weights_grad, bool):
             raise ValueError("depth_weights_grad must be True or False")
+        _check_antialiasing(settings)           # (validated here like the others; it is applied in front of the operator, not in BagsSettings)
         self.depth_weights_grad = settings.depth_weights_grad
         self.settings = L.BagsSettings(
             int(settings.image_height), int(settings.image_width), float(settings.tanfovx), float(settings.tanfovy),
@@ -164,6 +172,21 @@ class _Packed:
 
 def _require_gpu(t: torch.Tensor) -> None:
     L.require("bags_raster", "means3D", t, gpu=True, type_error=RuntimeError)
+
+
+def _check_antialiasing(settings: GaussianRasterizationSettings) -> None:
+    if not isinstance(settings.antialiasing, bool):
+        raise ValueError("antialiasing must be True or False")
+
+
+def _antialiased(rs: GaussianRasterizationSettings, means3D, opacities, shift_factors, scales, rotations, cov3D_precomp):
+    """``opacities`` of an ``antialiasing=True`` call: bags_raster.antialias_opacity of the call's own inputs and settings."""
+    from .antialias import antialias_opacity
+    # (the fork's wrapper passes torch.Tensor([]) for an absent covariance source)
+    absent = lambda t: None if (t is None or (torch.is_tensor(t) and t.numel() == 0 and means3D.shape[0] > 0)) else t       # noqa: E731
+    return antialias_opacity(means3D, opacities, rs.viewmatrix, rs.intrinsic, (rs.image_height, rs.image_width), (rs.tanfovx, rs.tanfovy),
+                             scales=absent(scales), rotations=absent(rotations), cov3D_precomp=absent(cov3D_precomp),
+                             shift_factors=shift_factors, scale_modifier=rs.scale_modifier, clamp_grad=rs.clamp_grad)
 
 
 _bytes = L.workspace
@@ -773,6 +796,9 @@ class GaussianRasterizer(torch.nn.Module):
             raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
         if shs_rest is not None and shs is None:
             raise Exception('shs_rest (features_rest) goes with shs = features_dc')
+        _check_antialiasing(rs)
+        if rs.antialiasing:
+            opacities = _antialiased(rs, means3D, opacities, shift_factors, scales, rotations, cov3D_precomp)
         return rasterize_gaussians(means3D, means2D, means2D_densify, shift_factors, shs, colors_precomp, opacities,
                                    scales, rotations, cov3D_precomp, rs, shs_rest)
 
@@ -782,9 +808,12 @@ def debug_views(settings: GaussianRasterizationSettings, means3D, means2D, shift
     """Forward pass that also returns the integer artefacts (tiles_touched, rect, depth bits, sorted instance list,
     64-bit keys, tile ranges, n_contrib, final_T) for the bit-exact parity tests."""
     lib = L.load()
+    _check_antialiasing(settings)
     _require_gpu(means3D)
     dev = means3D.device
     with torch.cuda.device(dev), torch.no_grad():
+        if settings.antialiasing:
+            opacities = _antialiased(settings, means3D, opacities, shift_factors, scales, rotations, cov3D_precomp)
         pk = _Packed(settings, means3D, means2D, shift_factors, shs, colors_precomp, opacities, scales, rotations,
                      cov3D_precomp, settings.viewmatrix, settings.projmatrix, settings.intrinsic, settings.campos)
         H, W = int(settings.image_height), int(settings.image_width)

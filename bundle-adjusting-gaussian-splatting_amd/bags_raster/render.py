@@ -32,10 +32,13 @@ from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer
 
 
 class PipelineParams(SimpleNamespace):
-    """The three switches of arguments/__init__.py:67-72."""
+    """The three switches of arguments/__init__.py:67-72, and upstream's fourth, ``antialiasing`` (``pipe.antialiasing`` of the
+    current 3DGS training scripts): the rasterizer settings' field of that name."""
 
-    def __init__(self, convert_SHs_python: bool = False, compute_cov3D_python: bool = False, debug: bool = False):
-        super().__init__(convert_SHs_python=convert_SHs_python, compute_cov3D_python=compute_cov3D_python, debug=debug)
+    def __init__(self, convert_SHs_python: bool = False, compute_cov3D_python: bool = False, debug: bool = False,
+                 antialiasing: bool = False):
+        super().__init__(convert_SHs_python=convert_SHs_python, compute_cov3D_python=compute_cov3D_python, debug=debug,
+                         antialiasing=antialiasing)
 
 
 _ZERO3 = {}        # device -> zeros(3): the `shift_factors=None` stand-in (read-only: one fill launch per device, not per call)
@@ -120,6 +123,7 @@ def _rasterize_view(viewpoint_camera, pc, pipe, bg_color, mlp_color, shift_facto
         debug=pipe.debug,
         debug_iter=iteration,
         depth_key=depth_key,
+        antialiasing=getattr(pipe, "antialiasing", False),   # (a reference `pipe` may not have the attribute)
         depth_weights_grad=depth_weights_grad,
     )
     rasterizer = GaussianRasterizer(raster_settings=raster_settings)

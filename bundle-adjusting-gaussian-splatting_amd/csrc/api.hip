@@ -1231,4 +1231,62 @@ int bags_mcmc_noise(float* xyz, const float* opacity, const float* scaling, cons
     return BAGS_OK;
 }
 
+// ---- antialias.hip: one row of pose sums per workgroup
+static size_t carve_antialias(void* base, int P, float** slab)
+{
+    Carver c(base);
+    float* s = c.take<float>((size_t)antialias_blocks(P) * AA_SLAB);
+    if (slab) *slab = s;
+    return c.used();
+}
+
+size_t bags_antialias_workspace_size(int32_t P) { return carve_antialias(nullptr, P, nullptr) + BASE_SLACK; }
+
+static int check_antialias(const char* op, const BagsAntialias* a)
+{
+    if (!a) return fail(BAGS_ERR_ARG, "%s: null struct", op);
+    if (a->P < 0) return fail(BAGS_ERR_ARG, "%s: P < 0 (got %d)", op, a->P);
+    if (a->image_width <= 0 || a->image_height <= 0) return fail(BAGS_ERR_ARG, "%s: empty image %dx%d", op, a->image_width, a->image_height);
+    if (a->clamp_grad != BAGS_CLAMP_GRAD_STOCK && a->clamp_grad != BAGS_CLAMP_GRAD_EXACT)
+        return fail(BAGS_ERR_ARG, "%s: clamp_grad %d is neither stock (0) nor exact (1)", op, a->clamp_grad);
+    if (a->P == 0) return BAGS_OK;                 // an empty set has no rows to point to: the pointers are not looked at
+    const bool pair = a->scales || a->rotations;
+    if ((pair && a->cov3D_precomp) || (!(a->scales && a->rotations) && !a->cov3D_precomp))
+        return fail(BAGS_ERR_ARG, "%s: provide exactly one of either scale/rotation pair or precomputed 3D covariance", op);
+    if (!a->viewmatrix || !a->intrinsic) return fail(BAGS_ERR_ARG, "%s: NULL viewmatrix / intrinsic", op);
+    if (!a->means3D || !a->opacities) return fail(BAGS_ERR_ARG, "%s: NULL means3D / opacities", op);
+    return BAGS_OK;
+}
+
+int bags_antialias_forward(const BagsAntialias* a, float* out, void* stream)
+{
+    if (const int rc = check_antialias("antialias_forward", a)) return rc;
+    if (a->P == 0) return BAGS_OK;
+    if (!out) return fail(BAGS_ERR_ARG, "antialias_forward: NULL out");
+    HIP_TRY(launch_antialias_fwd(*a, out, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
+int bags_antialias_backward(const BagsAntialias* a, const float* grad_out, void* workspace, size_t workspace_bytes, float* g_opacities,
+                            float* g_means3D, float* g_scales, float* g_rotations, float* g_cov3D, float* g_viewmatrix, float* g_intrinsic,
+                            float* g_shift_factors, void* stream)
+{
+    if (const int rc = check_antialias("antialias_backward", a)) return rc;
+    if (a->P == 0) return BAGS_OK;
+    if (!grad_out) return fail(BAGS_ERR_ARG, "antialias_backward: NULL grad_out");
+    if (a->cov3D_precomp ? (g_scales || g_rotations) : g_cov3D != nullptr)
+        return fail(BAGS_ERR_ARG, "antialias_backward: a gradient is asked for the covariance source that was not given");
+    float* slab = nullptr;
+    if (g_viewmatrix || g_intrinsic || g_shift_factors) {
+        const size_t need = bags_antialias_workspace_size(a->P);
+        if (!workspace || workspace_bytes < need)
+            return fail(BAGS_ERR_SIZE, "antialias_backward: the pose gradients need a workspace of %zu bytes (got %zu)", need, workspace ? workspace_bytes : (size_t)0);
+        carve_antialias(workspace, a->P, &slab);
+    }
+    if (!g_opacities && !g_means3D && !g_scales && !g_rotations && !g_cov3D && !slab) return BAGS_OK;
+    HIP_TRY(launch_antialias_bwd(*a, grad_out, slab, g_opacities, g_means3D, g_scales, g_rotations, g_cov3D, g_viewmatrix, g_intrinsic,
+                                 g_shift_factors, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
 }  // extern "C"

@@ -327,6 +327,13 @@ hipError_t launch_mcmc_add_new(const BagsMcmcGroup* groups, int n_groups, int P,
                                int n_max, double min_opacity, void* workspace, float* accum_out, float* denom_out, float* radii_out, hipStream_t st);
 hipError_t launch_mcmc_noise(float* xyz, const float* opacity, const float* scaling, const float* rotation, int P, const float* noise, uint64_t seed,
                              double scale, double k, double x0, double scaling_modifier, hipStream_t st);
+// antialias.hip: the mip filter's opacity scale in front of the operator, and its adjoint; slab: antialias_blocks(P) rows of AA_SLAB
+// floats (17 used), or nullptr when no pose gradient is wanted (carve_antialias in api.hip)
+#define AA_SLAB 20
+int antialias_blocks(int P);
+hipError_t launch_antialias_fwd(const BagsAntialias& a, float* out, hipStream_t st);
+hipError_t launch_antialias_bwd(const BagsAntialias& a, const float* grad_out, float* slab, float* g_opac, float* g_means3D, float* g_scales,
+                                float* g_rot, float* g_cov3D, float* g_view, float* g_intr, float* g_shift, hipStream_t st);
 // lens_field.hip: the invertible-ResNet lens network on M points of R^2 (forward / fixed-point inverse in one launch, backward in two)
 __host__ __device__ static inline int lens_block_floats(int H, int n) { return 3 * H + n * (H * H + H) + 2 * H + 2; }   // of the flat vector, per block
 size_t lens_field_workspace_bytes(int B, int H, int n, long long M);

@@ -684,6 +684,36 @@ int bags_mcmc_add_new(const BagsMcmcGroup* groups, int32_t n_groups, int32_t P, 
 int bags_mcmc_noise(float* xyz, const float* opacity, const float* scaling, const float* rotation, int32_t P, const float* noise,
                     uint64_t seed, double scale, double k, double x0, double scaling_modifier, void* stream);
 
+/* Antialiased rendering (csrc/antialias.hip): upstream diff_gaussian_rasterization's `antialiasing` setting, the opacity scale
+ * of Mip-Splatting's 2D filter.  The rasterizer adds 0.3 px^2 to the diagonal of every projected covariance; per Gaussian
+ *     out = opacity * h,   h = sqrt(max(0.000025, det(cov2D) / det(cov2D + 0.3 I)))
+ * makes the dilated Gaussian carry the energy of the original one.  h = 1 for a Gaussian the forward culls (view depth <= 0.2,
+ * det(cov2D + 0.3 I) == 0).  cov2D is the operator's own: the same view-space point, entrance-pupil shift, Sigma, 1.3 x
+ * field-of-view clamp and Jacobian as its forward, rounded the same way.  The operator is not involved: `out` goes in as its
+ * `opacities`, and its dL/dopacities comes back as grad_out, which is upstream's antialiased forward and backward by the chain rule.
+ * forward:  one launch, 4 bytes written per Gaussian.
+ * backward: recomputes the forward from the inputs.  Every gradient pointer may be NULL (not wanted); a wanted one is written, not
+ *           accumulated, and its bits do not depend on which others are wanted.  g_scales is the gradient of the scales as given
+ *           (scale_modifier applied), g_rotations of the quaternion as given; g_viewmatrix and g_intrinsic are full (16) outputs
+ *           (the entries nothing depends on are written as zeros: viewmatrix's fourth column, all of intrinsic but [0] and [5]).
+ *           A culled Gaussian, or one on the floor, contributes grad_out * h to g_opacities and nothing else.  The three pose
+ *           outputs are per-workgroup sums in the workspace added in double in workgroup order by a second launch: no atomics,
+ *           two runs give the same bits.  The workspace (bags_antialias_workspace_size bytes, no initialisation) is needed only
+ *           when a pose output is wanted.
+ * P == 0 is a successful no-op (nothing is written). */
+typedef struct BagsAntialias {
+    int32_t P, image_width, image_height, clamp_grad;      /* clamp_grad: 0 stock, 1 exact, as BagsSettings */
+    float tanfovx, tanfovy, scale_modifier; int32_t reserved;
+    const float *means3D, *scales, *rotations, *cov3D_precomp;   /* scales + rotations, or cov3D_precomp */
+    const float *opacities, *shift_factors;                     /* shift_factors (3) or NULL = zeros */
+    const float *viewmatrix, *intrinsic;                        /* (16) each, device */
+} BagsAntialias;
+int    bags_antialias_forward(const BagsAntialias* args, float* out /* (P) */, void* stream);
+size_t bags_antialias_workspace_size(int32_t P);
+int    bags_antialias_backward(const BagsAntialias* args, const float* grad_out, void* workspace, size_t workspace_bytes,
+                               float* g_opacities, float* g_means3D, float* g_scales, float* g_rotations, float* g_cov3D,
+                               float* g_viewmatrix, float* g_intrinsic, float* g_shift_factors, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
