@@ -186,6 +186,15 @@ class BagsAntialias(C.Structure):           # one view's inputs of the antialias
                 ("shift_factors", c_fp), ("viewmatrix", c_fp), ("intrinsic", c_fp)]
 
 
+APPEARANCE_BLOCK, APPEARANCE_MIN_SLOTS, APPEARANCE_TILES_PER_SLOT = 256, 64, 4      # include/bags_raster.h: BAGS_APPEARANCE_*
+
+
+class BagsAppearance(C.Structure):          # the images of one step and their rows of the (N,16) appearance table (csrc/appearance.hip)
+    _fields_ = [("N", C.c_int32), ("table", c_fp), ("n_rows", C.c_int32), ("rows", C.c_int32 * MAX_POSE_ROWS), ("C", C.c_int32),
+                ("H", C.c_int32), ("W", C.c_int32), ("cx", C.c_float), ("cy", C.c_float), ("image", c_fp * MAX_POSE_ROWS),
+                ("out", c_fp * MAX_POSE_ROWS)]
+
+
 SYMBOLS = {    "bags_abi_version": (C.c_int, []),
     "bags_build_info": (C.c_char_p, []),
     "bags_last_error": (C.c_char_p, []),
@@ -265,6 +274,9 @@ SYMBOLS = {    "bags_abi_version": (C.c_int, []),
     "bags_antialias_forward": (C.c_int, [C.POINTER(BagsAntialias), c_fp, C.c_void_p]),
     "bags_antialias_workspace_size": (C.c_size_t, [C.c_int32]),
     "bags_antialias_backward": (C.c_int, [C.POINTER(BagsAntialias), c_fp, C.c_void_p, C.c_size_t] + [c_fp] * 8 + [C.c_void_p]),
+    "bags_appearance_forward": (C.c_int, [C.POINTER(BagsAppearance), C.c_void_p]),
+    "bags_appearance_workspace_size": (C.c_size_t, [C.c_int32] * 3),
+    "bags_appearance_backward": (C.c_int, [C.POINTER(BagsAppearance), C.POINTER(c_fp), C.c_void_p, C.c_size_t, C.POINTER(c_fp), c_fp, C.c_void_p]),
 }
 
 _lib = None

@@ -10,10 +10,16 @@
 * ``chkpnt<iter>.pth`` -- ``torch.save((gaussians.capture(), iteration), ...)`` (train.py:487-489): ``capture()`` is the
   12-tuple of scene/gaussian_model.py:62-76; ``restore`` also accepts the 15-tuple of older checkpoints (:78-113).
 
+* ``exposure.json`` -- upstream 3DGS's per-image exposure file, ``{image_name: 3x4 nested list}`` (its train.py writes
+  ``{name: scene.gaussians.get_exposure_from_name(name).detach().cpu().numpy().tolist()}``): ``save_exposure_json`` /
+  ``load_exposure_json`` for an ``AppearanceBank``.  The format has no field for the bank's vignetting coefficients: they ride in
+  the module's ``state_dict``.
+
 Everything here is host-side bookkeeping around the hot path: plain numpy / PyTorch, device-agnostic.
 """
 from __future__ import annotations
 
+import json
 import os
 from typing import Dict, List, Optional, Tuple
 
@@ -218,3 +224,37 @@ def load_checkpoint(path: str, sh_degree: int, device=None, trust_pickle: bool =
         model_args, iteration = torch.load(path, map_location=device, weights_only=False)
     pc, opt, lr_scale = restore(model_args, sh_degree, device)
     return pc, opt, lr_scale, int(iteration)
+
+
+def save_exposure_json(path: str, bank, image_names) -> None:
+    """Upstream's ``exposure.json``: ``{image_names[i]: bank.exposure(i) as a 3x4 nested list}``, readable as the plain dict upstream
+    reads.  A float32 survives the decimal text bit for bit.  The vignetting coefficients (columns 12..14 of ``bank.table``) are
+    NOT in the file -- the format has no field for them; save ``bank.state_dict()`` to keep them."""
+    names = list(image_names)
+    if len(names) != len(bank) or len(set(names)) != len(names):
+        raise ValueError(f"save_exposure_json: {len(names)} image names ({len(set(names))} distinct) for {len(bank)} cameras")
+    E = bank.table.detach()[:, :12].reshape(len(names), 3, 4).cpu().tolist()
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    with open(path, "w") as f:
+        json.dump({n: e for n, e in zip(names, E)}, f, indent=2)
+
+
+def load_exposure_json(path: str, image_names, device="cpu"):
+    """An ``AppearanceBank`` on ``device`` whose row i holds the exposure matrix stored under ``image_names[i]``; the vignetting
+    coefficients are zero (load the bank's ``state_dict`` for them).  A name the file lacks is a ``KeyError``."""
+    from .appearance import AppearanceBank
+    names = list(image_names)
+    with open(path) as f:
+        stored = json.load(f)
+    bank = AppearanceBank(len(names), "cpu")
+    with torch.no_grad():
+        for i, n in enumerate(names):
+            if n not in stored:
+                raise KeyError(f"{path}: no exposure for image {n!r}")
+            E = torch.tensor(stored[n], dtype=torch.float64)
+            if tuple(E.shape) != (3, 4):
+                raise ValueError(f"{path}: exposure of {n!r} has shape {tuple(E.shape)}, expected (3, 4)")
+            bank.table[i, :12] = E.reshape(12).to(torch.float32)
+    return bank.to(device)

@@ -1289,4 +1289,67 @@ int bags_antialias_backward(const BagsAntialias* a, const float* grad_out, void*
     return BAGS_OK;
 }
 
+// ---- appearance.hip: one row of 16 doubles per workgroup of the pixels kernel, view-major
+static size_t carve_appearance(void* base, int n_rows, int H, int W, double** partials)
+{
+    Carver c(base, false);                       // the base as given: a misaligned one is refused, not rounded
+    double* p = c.take<double>((size_t)n_rows * appearance_slots(H, W) * 16);
+    if (partials) *partials = p;
+    return c.used();
+}
+
+static bool appearance_image_ok(int H, int W) { return H >= 1 && W >= 1 && (long long)H * W < (1ll << 31); }
+
+size_t bags_appearance_workspace_size(int32_t n_rows, int32_t H, int32_t W)
+{
+    if (n_rows < 1 || n_rows > BAGS_MAX_POSE_ROWS || !appearance_image_ok(H, W)) return 0;
+    return carve_appearance(nullptr, n_rows, H, W, nullptr);
+}
+
+static int check_appearance(const char* op, const BagsAppearance* a)
+{
+    if (!a) return fail(BAGS_ERR_ARG, "%s: null struct", op);
+    if (!a->table) return fail(BAGS_ERR_ARG, "%s: null table", op);
+    if (const int rc = check_pose_rows(op, a->N, a->n_rows, a->rows)) return rc;
+    if (a->C != 3) return fail(BAGS_ERR_ARG, "%s: C must be 3 (got %d)", op, a->C);
+    if (a->H < 1 || a->W < 1) return fail(BAGS_ERR_ARG, "%s: empty image %dx%d", op, a->W, a->H);
+    if (!appearance_image_ok(a->H, a->W)) return fail(BAGS_ERR_ARG, "%s: image %dx%d has 2^31 pixels or more", op, a->W, a->H);
+    if (!(a->cx == a->cx) || !(a->cy == a->cy)) return fail(BAGS_ERR_ARG, "%s: the centre is NaN", op);
+    for (int v = 0; v < a->n_rows; ++v)
+        if (!a->image[v]) return fail(BAGS_ERR_ARG, "%s: null image[%d]", op, v);
+    return BAGS_OK;
+}
+
+int bags_appearance_forward(const BagsAppearance* a, void* stream)
+{
+    if (const int rc = check_appearance("appearance_forward", a)) return rc;
+    for (int v = 0; v < a->n_rows; ++v)
+        if (!a->out[v]) return fail(BAGS_ERR_ARG, "appearance_forward: null out[%d]", v);
+    HIP_TRY(launch_appearance_fwd(*a, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
+int bags_appearance_backward(const BagsAppearance* a, const float* const g_out[BAGS_MAX_POSE_ROWS], void* workspace, size_t workspace_bytes,
+                             float* const g_image[BAGS_MAX_POSE_ROWS], float* g_table, void* stream)
+{
+    if (const int rc = check_appearance("appearance_backward", a)) return rc;
+    if (!g_out) return fail(BAGS_ERR_ARG, "appearance_backward: null g_out");
+    for (int v = 0; v < a->n_rows; ++v)
+        if (!g_out[v]) return fail(BAGS_ERR_ARG, "appearance_backward: null g_out[%d]", v);
+    if (g_table == a->table) return fail(BAGS_ERR_ARG, "appearance_backward: g_table must not be the table");
+    double* partials = nullptr;
+    if (g_table) {
+        const size_t need = bags_appearance_workspace_size(a->n_rows, a->H, a->W);
+        if (!workspace || workspace_bytes < need)
+            return fail(BAGS_ERR_ARG, "appearance_backward: g_table needs a workspace of %zu bytes (got %zu)", need, workspace ? workspace_bytes : (size_t)0);
+        if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return fail(BAGS_ERR_ARG, "appearance_backward: the workspace is not 16-byte aligned");
+        carve_appearance(workspace, a->n_rows, a->H, a->W, &partials);
+    }
+    bool any_image = false;
+    for (int v = 0; g_image && v < a->n_rows; ++v) any_image |= g_image[v] != nullptr;
+    if (!any_image && !g_table) return BAGS_OK;
+    HIP_TRY(launch_appearance_bwd(*a, g_out, partials, any_image ? g_image : nullptr, g_table, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
 }  // extern "C"

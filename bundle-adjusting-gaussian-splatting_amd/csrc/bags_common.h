@@ -334,6 +334,12 @@ int antialias_blocks(int P);
 hipError_t launch_antialias_fwd(const BagsAntialias& a, float* out, hipStream_t st);
 hipError_t launch_antialias_bwd(const BagsAntialias& a, const float* grad_out, float* slab, float* g_opac, float* g_means3D, float* g_scales,
                                 float* g_rot, float* g_cov3D, float* g_view, float* g_intr, float* g_shift, hipStream_t st);
+// appearance.hip: per-camera vignetting and exposure on the V images of a step, and the adjoint; partials: n_rows *
+// appearance_slots(H, W) rows of 16 doubles, or nullptr when g_table is not wanted (carve_appearance in api.hip)
+int appearance_slots(int H, int W);
+hipError_t launch_appearance_fwd(const BagsAppearance& a, hipStream_t st);
+hipError_t launch_appearance_bwd(const BagsAppearance& a, const float* const* g_out, double* partials, float* const* g_image, float* g_table,
+                                 hipStream_t st);
 // lens_field.hip: the invertible-ResNet lens network on M points of R^2 (forward / fixed-point inverse in one launch, backward in two)
 __host__ __device__ static inline int lens_block_floats(int H, int n) { return 3 * H + n * (H * H + H) + 2 * H + 2; }   // of the flat vector, per block
 size_t lens_field_workspace_bytes(int B, int H, int n, long long M);

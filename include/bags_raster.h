@@ -714,6 +714,46 @@ int    bags_antialias_backward(const BagsAntialias* args, const float* grad_out,
                                float* g_opacities, float* g_means3D, float* g_scales, float* g_rotations, float* g_cov3D,
                                float* g_viewmatrix, float* g_intrinsic, float* g_shift_factors, void* stream);
 
+/* Per-camera appearance (csrc/appearance.hip): lens vignetting, then upstream 3DGS's per-image 3x4 exposure matrix, applied to the
+ * rendered image in sensor coordinates -- after the resample / stitch, in front of the loss.  The parameters of all N training
+ * images sit in one (N,16) device table, the image-space twin of BagsPoseBank; row r is
+ *     E (3,4) row-major in columns 0..11 | k1 k2 k3 in 12..14 | column 15 unused (never read; its gradient is exact zero).
+ * For pixel (x, y) of a (3,H,W) image with channels p_0..p_2, centre (cx, cy) in pixels and s2 = (W*W + H*H) / 4:
+ *     dx = x + 0.5 - cx ; dy = y + 0.5 - cy ; r2 = (dx*dx + dy*dy) / s2            (0 at the centre, 1 at a corner)
+ *     f  = 1 + r2*(k1 + r2*(k2 + r2*k3))
+ *     q_k = f * p_k
+ *     out_c = q_0*E[0][c] + q_1*E[1][c] + q_2*E[2][c] + E[c][3]                    (upstream: image^T @ E[:3,:3] + E[:3,3])
+ * evaluated in float32 in exactly this order; the neutral row E = [I | 0], k = 0 returns its input bit for bit.
+ * forward:  ONE launch for the n_rows <= BAGS_MAX_POSE_ROWS images of a step; image[v] goes through row rows[v] into out[v].  The
+ *           pointers and the row list travel by value: nothing is stacked, copied or uploaded.  out[v] must not overlap an input.
+ * backward: two launches.  g_image (NULL, or n_rows pointers of which any may be NULL) receives dL/dimage.  g_table (N,16), or
+ *           NULL, is written in EVERY element: the listed rows get their 15 sums -- per-workgroup partial rows in the workspace,
+ *           added in double in a fixed order and rounded once -- every other row and column 15 exact zeros (no fill launch is
+ *           needed in front).  No atomics, no host synchronisation; a repeated call gives the same bits, and each output the same
+ *           bits whichever other is wanted.  How many workgroups a view has is decided by H and W alone (the constants
+ *           below), so row v of a many-view call has the bits of a call of its own.  `out` of the struct is not read.
+ * A thread takes four consecutive pixels of a row: one 16-byte access per channel where W % 4 == 0 and every pointer of the call
+ * is 16-byte aligned, element by element otherwise, with the same bits either way.
+ * workspace: bags_appearance_workspace_size bytes (0 for invalid arguments), 16-byte aligned, no initialisation; needed only
+ *           when g_table is wanted.  H * W must be below 2^31. */
+#define BAGS_APPEARANCE_BLOCK 256            /* threads per workgroup; a workgroup's tile is 256 quads = up to 1024 pixels */
+#define BAGS_APPEARANCE_MIN_SLOTS 64         /* a view's backward has min(tiles, max(64, ceil(tiles / 4))) workgroups */
+#define BAGS_APPEARANCE_TILES_PER_SLOT 4
+typedef struct BagsAppearance {
+    int32_t N;                               /* rows of the table, >= 1 */
+    const float* table;                      /* (N,16) */
+    int32_t n_rows;                          /* 1..BAGS_MAX_POSE_ROWS */
+    int32_t rows[BAGS_MAX_POSE_ROWS];        /* distinct, each in [0, N) */
+    int32_t C, H, W;                         /* C == 3 */
+    float cx, cy;                            /* the optical centre in pixels; (W/2, H/2) is the image centre */
+    const float* image[BAGS_MAX_POSE_ROWS];  /* (3,H,W) each, the first n_rows given */
+    float* out[BAGS_MAX_POSE_ROWS];          /* (3,H,W) each (forward only) */
+} BagsAppearance;
+int    bags_appearance_forward(const BagsAppearance* app, void* stream);
+size_t bags_appearance_workspace_size(int32_t n_rows, int32_t H, int32_t W);
+int    bags_appearance_backward(const BagsAppearance* app, const float* const g_out[BAGS_MAX_POSE_ROWS], void* workspace,
+                                size_t workspace_bytes, float* const g_image[BAGS_MAX_POSE_ROWS], float* g_table, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
