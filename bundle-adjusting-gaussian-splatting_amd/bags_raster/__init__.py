@@ -9,6 +9,7 @@ from .render import render, render_views, PipelineParams
 from .gaussians import GaussianBag, eval_sh, sh_colors, sh_colors_views
 from .mcmc import compute_relocation, compute_relocation_torch, relocation_binoms
 from .antialias import antialias_opacity, antialias_opacity_torch
+from .filter3d import filter_3D, filter_3D_torch, filtered_activations_torch
 from .appearance import AppearanceBank, apply_appearance, appearance_torch
 from .io import save_ply, load_ply, save_checkpoint, load_checkpoint, save_exposure_json, load_exposure_json
 from .optim import GaussianAdam
@@ -22,4 +23,5 @@ __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gau
            "save_ply", "load_ply", "save_checkpoint", "load_checkpoint", "GaussianAdam",
            "PoseBank", "PoseAdam", "LensField", "lens_field", "lens_field_torch",
            "resample_faces", "resample_faces_torch", "cube_face_matrices",
-           "AppearanceBank", "apply_appearance", "appearance_torch", "save_exposure_json", "load_exposure_json"]
+           "AppearanceBank", "apply_appearance", "appearance_torch", "save_exposure_json", "load_exposure_json",
+           "filter_3D", "filter_3D_torch", "filtered_activations_torch"]

@@ -277,6 +277,10 @@ SYMBOLS = {    "bags_abi_version": (C.c_int, []),
     "bags_appearance_forward": (C.c_int, [C.POINTER(BagsAppearance), C.c_void_p]),
     "bags_appearance_workspace_size": (C.c_size_t, [C.c_int32] * 3),
     "bags_appearance_backward": (C.c_int, [C.POINTER(BagsAppearance), C.POINTER(c_fp), C.c_void_p, C.c_size_t, C.POINTER(c_fp), c_fp, C.c_void_p]),
+    "bags_filter3d_workspace_size": (C.c_size_t, [C.c_int32]),
+    "bags_filter3d_compute": (C.c_int, [c_fp, C.c_int32, c_fp, c_fp, c_fp, C.c_int32, C.c_float, C.c_void_p, C.c_size_t, c_fp, C.c_void_p]),
+    "bags_activations_filtered_forward": (C.c_int, [C.POINTER(BagsRawGaussians), c_fp] + [C.c_void_p] * 5),
+    "bags_activations_filtered_backward": (C.c_int, [C.POINTER(BagsRawGaussians), c_fp] + [C.c_void_p] * 10),
 }
 
 _lib = None

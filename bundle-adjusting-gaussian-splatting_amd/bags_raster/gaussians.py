@@ -25,6 +25,7 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import _lib as L
+from .filter3d import filter_3D, filter_3D_torch, filtered_activations_torch
 from .mcmc import N_MAX, relocation_binoms
 
 SH_C0 = 0.28209479177387814
@@ -116,6 +117,7 @@ class GaussianBag:
         e = torch.empty(0)
         self._xyz = self._features_dc = self._features_rest = self._scaling = self._rotation = self._opacity = e
         self.max_radii2D = self.xyz_gradient_accum = self.denom = e
+        self.filter_3D = None                # (P,1) once compute_3D_filter has run; None: everything is unfiltered
 
     # ---- construction
     @classmethod
@@ -168,17 +170,77 @@ class GaussianBag:
     def get_covariance(self, scaling_modifier: float = 1.0):
         return covariance_from_scaling_rotation(self.get_scaling, scaling_modifier, self._rotation)
 
+    # ---- Mip-Splatting's 3D smoothing filter (its scene/gaussian_model.py: compute_3D_filter and the two *_with_3D_filter properties)
+    def _checked_filter(self, what: str):
+        """``filter_3D`` if it fits the set as it is now; a filter left over from before the set changed size raises."""
+        f, P = self.filter_3D, self._xyz.shape[0]
+        if f is None:
+            raise RuntimeError(f"{what}: no 3D filter is set; call compute_3D_filter(viewmatrices, intrinsics, sizes) first")
+        if not torch.is_tensor(f) or f.numel() != P or f.shape[0] != P:
+            raise RuntimeError(f"{what}: filter_3D has {f.shape[0] if torch.is_tensor(f) and f.dim() else '?'} rows for {P} Gaussians: it is stale "
+                               "(densify_and_prune / add_new changed the set); recompute it with compute_3D_filter")
+        if f.device != self._xyz.device:
+            raise RuntimeError(f"{what}: filter_3D is on {f.device}, the Gaussians on {self._xyz.device}; recompute it with compute_3D_filter")
+        return f
+
+    def compute_3D_filter(self, viewmatrices, intrinsics, sizes, variance: float = 0.2):
+        """Set ``filter_3D`` ``(P,1)`` from the training cameras and return it: ``viewmatrices`` / ``intrinsics (N,4,4)`` (``get_matrices``'
+        ``viewmatrix`` and ``intrinsic`` of every camera, stacked) and ``sizes (N,2)`` integer ``(W, H)``.  Two HIP launches on a GPU
+        (bags_raster.filter_3D), ``filter_3D_torch`` on the host.  From then on ``activated()`` -- and so ``render()`` /
+        ``render_views()`` -- evaluates scale and opacity through the filter.  The filter belongs to the set as it is now: recompute
+        it after ``densify_and_prune``, ``add_new`` and ``relocate``, and whenever the poses have moved far enough."""
+        xyz = self._xyz.detach()
+        fn = filter_3D if xyz.is_cuda else filter_3D_torch
+        self.filter_3D = fn(xyz, viewmatrices, intrinsics, sizes, variance)
+        return self.filter_3D
+
+    @property
+    def get_scaling_with_3D_filter(self):
+        return filtered_activations_torch(self._opacity, self._scaling, self._checked_filter("GaussianBag.get_scaling_with_3D_filter"))[1]
+
+    @property
+    def get_opacity_with_3D_filter(self):
+        return filtered_activations_torch(self._opacity, self._scaling, self._checked_filter("GaussianBag.get_opacity_with_3D_filter"))[0]
+
+    @torch.no_grad()
+    def fuse_3D_filter(self) -> "GaussianBag":
+        """A new bag whose raw ``_opacity`` / ``_scaling`` are ``inverse_sigmoid(opacity')`` / ``log(scales')`` and whose ``filter_3D``
+        is None: upstream's ``save_fused_ply`` step, for viewers that know nothing of the filter.  Every other leaf is a detached
+        copy; the statistics are zeros."""
+        f = self._checked_filter("GaussianBag.fuse_3D_filter")
+        opacity, scales = filtered_activations_torch(self._opacity.detach(), self._scaling.detach(), f)
+        pc = GaussianBag(self.max_sh_degree)
+        pc.active_sh_degree = self.active_sh_degree
+        grad = self._xyz.requires_grad
+        for name in ("_xyz", "_features_dc", "_features_rest", "_rotation"):
+            setattr(pc, name, getattr(self, name).detach().clone().requires_grad_(grad))
+        pc._opacity = inverse_sigmoid(opacity).requires_grad_(grad)
+        pc._scaling = torch.log(scales).requires_grad_(grad)
+        P, dev = self._xyz.shape[0], self._xyz.device
+        pc.max_radii2D = torch.zeros(P, device=dev)
+        pc.xyz_gradient_accum = torch.zeros(P, 1, device=dev)
+        pc.denom = torch.zeros(P, 1, device=dev)
+        return pc
+
     def activated(self, features: bool = True):
         """(get_xyz, get_features, get_opacity, get_scaling, get_rotation) in one HIP launch each way on a GPU
         (bags_activations_forward / _backward, csrc/activations.hip); the same properties evaluated one by one on the host.
         ``features=False``: no concatenation (second entry None) -- for the rasterizer's ``shs`` / ``shs_rest`` pair, which
-        takes ``_features_dc`` and ``_features_rest`` as they are (bags_raster.render)."""
+        takes ``_features_dc`` and ``_features_rest`` as they are (bags_raster.render).
+
+        With ``filter_3D`` set, opacity and scaling are the filtered ones (``get_opacity_with_3D_filter`` /
+        ``get_scaling_with_3D_filter``): still one launch each way on a GPU (bags_activations_filtered_forward / _backward).  A filter
+        whose row count is not P is a RuntimeError."""
+        f = None if self.filter_3D is None else self._checked_filter("GaussianBag.activated")
         if self._xyz.is_cuda:
             if not features:
-                _, op, sc, rot = _FusedActivations.apply(None, None, self._opacity, self._scaling, self._rotation)
+                _, op, sc, rot = _FusedActivations.apply(None, None, self._opacity, self._scaling, self._rotation, f)
                 return self._xyz, None, op, sc, rot
-            shs, op, sc, rot = fused_activations(self._features_dc, self._features_rest, self._opacity, self._scaling, self._rotation)
+            shs, op, sc, rot = fused_activations(self._features_dc, self._features_rest, self._opacity, self._scaling, self._rotation, f)
             return self._xyz, shs, op, sc, rot
+        if f is not None:
+            op, sc = filtered_activations_torch(self._opacity, self._scaling, f)
+            return self.get_xyz, (self.get_features if features else None), op, sc, self.get_rotation
         return self.get_xyz, (self.get_features if features else None), self.get_opacity, self.get_scaling, self.get_rotation
 
     def oneupSHdegree(self):
@@ -367,7 +429,10 @@ class GaussianBag:
         ``sampled`` ``(D,)``, D the number of dead rows: the source of each dead row, in the order of the dead rows; it must list
         alive rows.  None: drawn here with ``torch.multinomial`` under ``generator``; on a GPU that draw does not repeat bit for bit at
         large P (its prefix sum does not), so view-sharded ranks draw once and pass one tensor.
-        No dead rows, or no alive ones: nothing happens.  Returns ``{"dead": D, "sources": distinct rows drawn}``."""
+        No dead rows, or no alive ones: nothing happens.  Returns ``{"dead": D, "sources": distinct rows drawn}``.
+
+        P stays, so a ``filter_3D`` that is set still fits and is NOT touched: the moved rows keep the filter of the place they
+        left until the caller recomputes it (``compute_3D_filter``)."""
         what = "GaussianBag.relocate"
         found = self._named_groups(optimizer, what)
         P = self._xyz.shape[0]
@@ -478,10 +543,11 @@ class GaussianBag:
 
 
 class _FusedActivations(torch.autograd.Function):
-    """``dc`` and ``rest`` may both be None (packed features): no SH concatenation, the first output is None."""
+    """``dc`` and ``rest`` may both be None (packed features): no SH concatenation, the first output is None.  ``filter_3D`` (P,1) or
+    None: the 3D smoothing filter applied to opacity and scaling (a constant: it gets no gradient)."""
 
     @staticmethod
-    def forward(ctx, dc, rest, opacity, scaling, rotation):
+    def forward(ctx, dc, rest, opacity, scaling, rotation, filter_3D):
         feats = dc is not None
         if (dc is None) != (rest is None):
             raise RuntimeError("fused_activations: features_dc and features_rest are given together or not at all")
@@ -494,13 +560,22 @@ class _FusedActivations(torch.autograd.Function):
         if (feats and (ts[0].shape != (P, 1, 3) or ts[1].shape != (P, K - 1, 3))) or ts[2].numel() != P or ts[3].shape != (P, 3) or ts[4].shape != (P, 4):
             raise RuntimeError("fused_activations: expected features_dc (P,1,3), features_rest (P,K-1,3), opacity (P,1), scaling (P,3), rotation (P,4)")
         dev = ts[3].device
+        filt = L.as_f32c(filter_3D)
+        if filt is not None:
+            L.require("fused_activations", "filter_3D", filt, gpu=True, on=ts[3], host=" (use the GaussianBag properties on the host)")
+            if filt.numel() != P or filt.shape[0] != P:
+                raise RuntimeError(f"fused_activations: filter_3D must be (P,1) with P = {P}, got {tuple(filt.shape)}")
         shs = torch.empty(P, K, 3, dtype=torch.float32, device=dev) if feats else None
         op = torch.empty(P, 1, dtype=torch.float32, device=dev)
         sc = torch.empty(P, 3, dtype=torch.float32, device=dev)
         rot = torch.empty(P, 4, dtype=torch.float32, device=dev)
         raw = L.BagsRawGaussians(P, K, *[L.ptr(t) for t in ts])
-        L.call("bags_activations_forward", dev, raw, L.ptr(shs), op.data_ptr(), sc.data_ptr(), rot.data_ptr())
+        if filt is None:
+            L.call("bags_activations_forward", dev, raw, L.ptr(shs), op.data_ptr(), sc.data_ptr(), rot.data_ptr())
+        else:
+            L.call("bags_activations_filtered_forward", dev, raw, filt.data_ptr(), L.ptr(shs), op.data_ptr(), sc.data_ptr(), rot.data_ptr())
         ctx.feats = feats
+        ctx.filt = filt                           # (not a differentiable input: kept beside the saved ones)
         ctx.save_for_backward(*[t for t in ts if t is not None])
         ctx.set_materialize_grads(False)          # an unused output arrives as None, not as 96 MB of zeros
         return shs, op, sc, rot
@@ -514,19 +589,28 @@ class _FusedActivations(torch.autograd.Function):
         K = 1 + ts[1].shape[1] if ctx.feats else 1
         need = ctx.needs_input_grad
         g_shs, g_op, g_sc, g_rot = L.as_f32c(g_shs), L.as_f32c(g_op), L.as_f32c(g_sc), L.as_f32c(g_rot)
+        filt = ctx.filt
+        # filtered: the opacity depends on the scaling too, so dL/d_scaling exists as soon as either cotangent does
+        g_for_scaling = g_sc is not None or (filt is not None and g_op is not None)
         out = [torch.empty_like(ts[0]) if (ctx.feats and need[0] and g_shs is not None) else None,
                torch.empty_like(ts[1]) if (ctx.feats and need[1] and g_shs is not None) else None,
                torch.empty_like(ts[2]) if (need[2] and g_op is not None) else None,
-               torch.empty_like(ts[3]) if (need[3] and g_sc is not None) else None,
+               torch.empty_like(ts[3]) if (need[3] and g_for_scaling) else None,
                torch.empty_like(ts[4]) if (need[4] and g_rot is not None) else None]
         raw = L.BagsRawGaussians(P, K, *[L.ptr(t) for t in ts])
-        L.call("bags_activations_backward", ts[3].device, raw, L.ptr(g_shs), L.ptr(g_op), L.ptr(g_sc), L.ptr(g_rot), *[L.ptr(o) for o in out])
-        return tuple(out)
+        cotangents = (L.ptr(g_shs), L.ptr(g_op), L.ptr(g_sc), L.ptr(g_rot))
+        if filt is None:
+            L.call("bags_activations_backward", ts[3].device, raw, *cotangents, *[L.ptr(o) for o in out])
+        else:
+            L.call("bags_activations_filtered_backward", ts[3].device, raw, filt.data_ptr(), *cotangents, *[L.ptr(o) for o in out])
+        return tuple(out) + (None,)
 
 
-def fused_activations(features_dc, features_rest, opacity, scaling, rotation):
-    """(get_features, get_opacity, get_scaling, get_rotation) of scene/gaussian_model.py:118-141 in one HIP launch."""
-    return _FusedActivations.apply(features_dc, features_rest, opacity, scaling, rotation)
+def fused_activations(features_dc, features_rest, opacity, scaling, rotation, filter_3D=None):
+    """(get_features, get_opacity, get_scaling, get_rotation) of scene/gaussian_model.py:118-141 in one HIP launch; with
+    ``filter_3D (P,1)`` the opacity and the scaling are Mip-Splatting's filtered ones (``filtered_activations_torch``), still one
+    launch each way."""
+    return _FusedActivations.apply(features_dc, features_rest, opacity, scaling, rotation, filter_3D)
 
 
 def _sh_saved(ctx):

@@ -9,6 +9,9 @@
   scalar property type, and picks properties by NAME as ``load_ply`` does.
 * ``chkpnt<iter>.pth`` -- ``torch.save((gaussians.capture(), iteration), ...)`` (train.py:487-489): ``capture()`` is the
   12-tuple of scene/gaussian_model.py:62-76; ``restore`` also accepts the 15-tuple of older checkpoints (:78-113).
+  ``GaussianBag.filter_3D`` (Mip-Splatting's 3D smoothing filter) is NOT in the tuple, which stays the reference's: a restored
+  bag has ``filter_3D = None``, and the filter is recomputed from the cameras after a load (``compute_3D_filter``).  The PLY holds
+  the raw leaves too; ``GaussianBag.fuse_3D_filter()`` gives the bag to save for a viewer that knows nothing of the filter.
 
 * ``exposure.json`` -- upstream 3DGS's per-image exposure file, ``{image_name: 3x4 nested list}`` (its train.py writes
   ``{name: scene.gaussians.get_exposure_from_name(name).detach().cpu().numpy().tolist()}``): ``save_exposure_json`` /

@@ -69,6 +69,9 @@ def _activate(pc, pipe, hybrid: bool, override_color) -> SimpleNamespace:
     # rasterizer-side SH colours and, on a GPU, the Python-side ones (bags_raster.sh_colors): the two feature parameters go to the
     # kernel as they are stored (shs = features_dc, shs_rest = features_rest), without get_features' torch.cat; every other colour
     # path needs the (P,K,3) tensor
+    if pipe.compute_cov3D_python and getattr(pc, "filter_3D", None) is not None:
+        raise NotImplementedError("render: pipe.compute_cov3D_python builds the covariance from the unfiltered leaves (get_covariance); with a "
+                                  "3D filter set (GaussianBag.filter_3D) use the scale / rotation path")
     raster_sh = override_color is None and not (hybrid or pipe.convert_SHs_python)
     fused_colors = override_color is None and not raster_sh and pc.get_xyz.is_cuda
     rest = getattr(pc, "_features_rest", None)

@@ -823,6 +823,29 @@ int bags_activations_backward(const BagsRawGaussians* r, const float* g_shs, con
     return BAGS_OK;
 }
 
+int bags_activations_filtered_forward(const BagsRawGaussians* r, const float* filter_3D, float* shs, float* opacity, float* scales,
+                                      float* rotations, void* stream)
+{
+    int rc = check_raw(r, shs != nullptr);
+    if (rc) return rc;
+    if (r->P > 0 && !filter_3D) return fail(BAGS_ERR_ARG, "activations_filtered_forward: NULL filter_3D");
+    HIP_TRY(launch_activations_fwd(r->P, r->K, r->features_dc, r->features_rest, r->opacity, r->scaling, r->rotation, shs, opacity,
+                                   scales, rotations, (hipStream_t)stream, filter_3D));
+    return BAGS_OK;
+}
+
+int bags_activations_filtered_backward(const BagsRawGaussians* r, const float* filter_3D, const float* g_shs, const float* g_opacity,
+                                       const float* g_scales, const float* g_rotations, float* g_dc, float* g_rest, float* g_opacity_raw,
+                                       float* g_scaling, float* g_rotation, void* stream)
+{
+    int rc = check_raw(r, g_shs != nullptr && (g_dc != nullptr || g_rest != nullptr));
+    if (rc) return rc;
+    if (r->P > 0 && !filter_3D) return fail(BAGS_ERR_ARG, "activations_filtered_backward: NULL filter_3D");
+    HIP_TRY(launch_activations_bwd(r->P, r->K, r->features_dc, r->features_rest, r->opacity, r->scaling, r->rotation, g_shs, g_opacity,
+                                   g_scales, g_rotations, g_dc, g_rest, g_opacity_raw, g_scaling, g_rotation, (hipStream_t)stream, filter_3D));
+    return BAGS_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- SH colours
 static int check_sh_colors(const BagsShColors* a)
 {
@@ -1349,6 +1372,36 @@ int bags_appearance_backward(const BagsAppearance* a, const float* const g_out[B
     for (int v = 0; g_image && v < a->n_rows; ++v) any_image |= g_image[v] != nullptr;
     if (!any_image && !g_table) return BAGS_OK;
     HIP_TRY(launch_appearance_bwd(*a, g_out, partials, any_image ? g_image : nullptr, g_table, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
+// ---- filter3d.hip: a dist per Gaussian and a maximum per workgroup between the two launches
+static size_t carve_filter3d(void* base, int P, float** dist, float** partials)
+{
+    Carver c(base);
+    float* d = c.take<float>((size_t)(P > 0 ? P : 0));
+    float* p = c.take<float>((size_t)filter3d_blocks(P));
+    if (dist) *dist = d;
+    if (partials) *partials = p;
+    return c.used();
+}
+
+size_t bags_filter3d_workspace_size(int32_t P) { return carve_filter3d(nullptr, P, nullptr, nullptr) + BASE_SLACK; }
+
+int bags_filter3d_compute(const float* xyz, int32_t P, const float* viewmatrices, const float* intrinsics, const int32_t* sizes, int32_t N,
+                          float variance, void* workspace, size_t workspace_bytes, float* out, void* stream)
+{
+    if (P < 0) return fail(BAGS_ERR_ARG, "filter3d_compute: P < 0 (got %d)", P);
+    if (N <= 0) return fail(BAGS_ERR_ARG, "filter3d_compute: needs at least one camera (N = %d)", N);
+    if (!(variance >= 0.0f)) return fail(BAGS_ERR_ARG, "filter3d_compute: variance is negative or NaN");
+    if (P == 0) return BAGS_OK;
+    if (!xyz || !viewmatrices || !intrinsics || !sizes || !out) return fail(BAGS_ERR_ARG, "filter3d_compute: NULL xyz / viewmatrices / intrinsics / sizes / out");
+    const size_t need = bags_filter3d_workspace_size(P);
+    if (!workspace || workspace_bytes < need)
+        return fail(BAGS_ERR_SIZE, "filter3d_compute: needs a workspace of %zu bytes (got %zu)", need, workspace ? workspace_bytes : (size_t)0);
+    float *dist = nullptr, *partials = nullptr;
+    carve_filter3d(workspace, P, &dist, &partials);
+    HIP_TRY(launch_filter3d(xyz, P, viewmatrices, intrinsics, sizes, N, variance, dist, partials, out, (hipStream_t)stream));
     return BAGS_OK;
 }
 

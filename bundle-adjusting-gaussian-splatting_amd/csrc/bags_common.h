@@ -291,13 +291,20 @@ hipError_t launch_resample_faces_bwd(const BagsFaces& f, const float* ctrl, int 
                                      const int8_t* face_index, const float* grad_out, void* workspace, float* const* grad_faces,
                                      float* grad_ctrl, hipStream_t st);
 size_t resample_faces_workspace_bytes(int F, int H, int W, int Hc, int Wc);
-// activations.hip: cat / sigmoid / exp / normalize of the raw Gaussian parameters, and the adjoint
+// activations.hip: cat / sigmoid / exp / normalize of the raw Gaussian parameters, and the adjoint; filter (P): the same with the 3D
+// smoothing filter applied to the scales and the opacity
 hipError_t launch_activations_fwd(int P, int K, const float* dc, const float* rest, const float* opacity, const float* scaling,
-                                  const float* rotation, float* shs, float* o_opacity, float* o_scales, float* o_rot, hipStream_t st);
+                                  const float* rotation, float* shs, float* o_opacity, float* o_scales, float* o_rot, hipStream_t st,
+                                  const float* filter = nullptr);
 hipError_t launch_activations_bwd(int P, int K, const float* dc, const float* rest, const float* opacity, const float* scaling,
                                   const float* rotation, const float* g_shs, const float* g_opacity, const float* g_scales,
                                   const float* g_rot, float* g_dc, float* g_rest, float* g_opacity_raw, float* g_scaling,
-                                  float* g_rotation, hipStream_t st);
+                                  float* g_rotation, hipStream_t st, const float* filter = nullptr);
+// filter3d.hip: the 3D smoothing filter of a Gaussian set under N cameras; dist: P floats, partials: filter3d_blocks(P) floats
+// (carve_filter3d in api.hip)
+int filter3d_blocks(int P);
+hipError_t launch_filter3d(const float* xyz, int P, const float* viewmatrices, const float* intrinsics, const int32_t* sizes, int N,
+                           float variance, float* dist, float* partials, float* out, hipStream_t st);
 // sh_colors.hip: SH -> RGB of the Python colour path (view direction, basis, +0.5, clamp at 0), and the adjoint; slab: SH_SLAB floats per
 // workgroup of 256 Gaussians (carve_sh_colors in api.hip)
 #define SH_SLAB 4

@@ -754,6 +754,37 @@ size_t bags_appearance_workspace_size(int32_t n_rows, int32_t H, int32_t W);
 int    bags_appearance_backward(const BagsAppearance* app, const float* const g_out[BAGS_MAX_POSE_ROWS], void* workspace,
                                 size_t workspace_bytes, float* const g_image[BAGS_MAX_POSE_ROWS], float* g_table, void* stream);
 
+/* Mip-Splatting's 3D smoothing filter (csrc/filter3d.hip), the other half of antialiased rendering: compute_3D_filter of its
+ * GaussianModel for N cameras at once.  viewmatrices and intrinsics are (N,16) in the operator's row-vector convention (v, k below:
+ * one camera's rows), sizes (N,2) int32 = (W, H) per camera.  Per Gaussian (x, y, z) and camera, in float32, each product and
+ * sum rounded once, left to right:
+ *     tx = x v0 + y v4 + z v8 + v12 ;  ty = x v1 + y v5 + z v9 + v13 ;  tz = x v2 + y v6 + z v10 + v14
+ *     fx = k0 * (0.5 W) ;  fy = k5 * (0.5 H) ;  px = tx / tz * fx + 0.5 W ;  py = ty / tz * fy + 0.5 H
+ *     valid = tz > 0.2  and  -0.15 W <= px <= 1.15 W  and  -0.15 H <= py <= 1.15 H
+ *     dist  = min of tz over the valid cameras ;  focal = max of fx over all cameras
+ *     dmax  = max of dist over the Gaussians with a valid camera (100000 when there is none)
+ *     out   = ((a camera is valid ? dist : dmax) / focal) * sqrt(variance)
+ * Two launches, no atomics, no host synchronisation, nothing allocated; min and max are exact, so the result repeats bit for bit
+ * and does not depend on the order of the rows or of the cameras.  The workspace (bags_filter3d_workspace_size bytes, no
+ * initialisation) holds dist and one maximum per workgroup.  P == 0 is a successful no-op; N <= 0 is an error. */
+size_t bags_filter3d_workspace_size(int32_t P);
+int    bags_filter3d_compute(const float* xyz /* (P,3) */, int32_t P, const float* viewmatrices, const float* intrinsics,
+                             const int32_t* sizes, int32_t N, float variance, void* workspace, size_t workspace_bytes,
+                             float* out /* (P) */, void* stream);
+
+/* bags_activations_forward / _backward with the 3D filter applied (get_scaling_with_3D_filter / get_opacity_with_3D_filter), still
+ * one launch each way; filter_3D (P) is the output of bags_filter3d_compute and a constant of the backward.  With s = exp(scaling),
+ * f = filter_3D, sig = sigmoid(opacity):
+ *     s'_a = sqrt(s_a^2 + f^2) ;  c = prod_a s_a / s'_a  ( = sqrt(prod s^2 / prod (s^2 + f^2)) )
+ *     scales = s' ;  opacity = sig * c ;  shs and rotations as bags_activations_forward
+ *     g_scaling_a = g_scales_a * s_a^2 / s'_a + g_opacity * sig * c * f^2 / s'_a^2 ;  g_opacity_raw = g_opacity * c * sig (1 - sig)
+ * A cotangent that is NULL counts as zero (the opacity depends on the scaling too); an output pointer that is NULL is not written. */
+int bags_activations_filtered_forward(const BagsRawGaussians* raw, const float* filter_3D, float* shs, float* opacity, float* scales,
+                                      float* rotations, void* stream);
+int bags_activations_filtered_backward(const BagsRawGaussians* raw, const float* filter_3D, const float* g_shs, const float* g_opacity,
+                                       const float* g_scales, const float* g_rotations, float* g_features_dc, float* g_features_rest,
+                                       float* g_opacity_raw, float* g_scaling, float* g_rotation, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
