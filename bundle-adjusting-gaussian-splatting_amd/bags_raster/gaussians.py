@@ -272,6 +272,39 @@ class GaussianBag:
 
     _ARG = dict(gpu=True, f32=True, contiguous=True, layout_error=TypeError)         # what the densify kernels take (_lib.require)
 
+    # ---- what densify_and_prune and add_new share: a set of another size is written in one launch (csrc/row_rebuild.h) and installed
+    def _resized_outputs(self, found, P_new: int):
+        """``({name: [param, exp_avg, exp_avg_sq]}, (accum, denom, radii))`` of ``P_new`` rows, uninitialised; no state: None moments."""
+        dev = self._xyz.device
+        new = {n: [torch.empty((P_new,) + tuple(p.shape[1:]), dtype=torch.float32, device=dev) for _ in range(3 if st is not None else 1)] + [None, None]
+               for n, (_, p, st) in found.items()}
+        return new, (torch.empty(P_new, 1, dtype=torch.float32, device=dev), torch.empty(P_new, 1, dtype=torch.float32, device=dev),
+                     torch.empty(P_new, dtype=torch.float32, device=dev))
+
+    def _group_structs(self, struct, found, outs=None):
+        """``(array, length)`` of ``L.BagsDensifyGroup`` or ``L.BagsMcmcGroup`` (one layout); ``outs``: of ``_resized_outputs``, or None."""
+        gs = []
+        for n, (_, p, st) in found.items():
+            m, v = (st["exp_avg"], st["exp_avg_sq"]) if st is not None else (None, None)
+            o = outs[n] if outs is not None else (None, None, None)
+            width = int(math.prod(p.shape[1:]))
+            if width:                                                             # (SH degree 0: _features_rest is (P,0,3), nothing to move)
+                gs.append(struct(p.data_ptr(), L.ptr(m), L.ptr(v), L.ptr(o[0]), L.ptr(o[1]), L.ptr(o[2]), width, self._GROUPS[n][1]))
+        return (struct * len(gs))(*gs), len(gs)
+
+    def _install_resized(self, optimizer, found, new, stats) -> None:
+        """New ``nn.Parameter`` s in the bag and in ``group["params"][0]``, the state re-keyed with the new moments, the statistics."""
+        for n, (group, p, st) in found.items():
+            param = torch.nn.Parameter(new[n][0].requires_grad_(True))
+            if p in optimizer.state:
+                stored = optimizer.state.pop(p)
+                if st is not None:
+                    stored["exp_avg"], stored["exp_avg_sq"] = new[n][1], new[n][2]
+                optimizer.state[param] = stored
+            group["params"][0] = param
+            setattr(self, self._GROUPS[n][0], param)
+        self.xyz_gradient_accum, self.denom, self.max_radii2D = stats
+
     @torch.no_grad()
     def densify_and_prune(self, optimizer, max_grad: float, min_opacity: float, extent: float, max_screen_size, percent_dense: float = 0.01,
                           N: int = 2, noise: Optional[torch.Tensor] = None, seed: Optional[int] = None, screen_size: str = "published"):
@@ -331,31 +364,13 @@ class GaussianBag:
         ws = L.workspace(L.load().bags_densify_workspace_size(P), dev)
         L.call("bags_densify_plan", dev, rule, ws.data_ptr(), ws.numel(), counts)
         P_new = int(counts[L.COUNT_P_NEW])
-        new, groups = {}, []
-        for n, (_, p, st) in found.items():
-            shape = (P_new,) + tuple(p.shape[1:])
-            out = [torch.empty(shape, dtype=torch.float32, device=dev) for _ in range(3 if st is not None else 1)] + [None, None]
-            new[n] = out
-            m, v = (st["exp_avg"], st["exp_avg_sq"]) if st is not None else (None, None)
-            groups.append(L.BagsDensifyGroup(p.data_ptr(), L.ptr(m), L.ptr(v), out[0].data_ptr(), L.ptr(out[1]), L.ptr(out[2]),
-                                             int(math.prod(p.shape[1:])), self._GROUPS[n][1]))
-        accum = torch.empty(P_new, 1, dtype=torch.float32, device=dev)
-        denom = torch.empty(P_new, 1, dtype=torch.float32, device=dev)
-        radii = torch.empty(P_new, dtype=torch.float32, device=dev)
+        new, stats = self._resized_outputs(found, P_new)
+        groups, n_groups = self._group_structs(L.BagsDensifyGroup, found, new)
         prov = torch.empty(P_new, 2, dtype=torch.int32, device=dev)
         if P > 0:
-            L.call("bags_densify_apply", dev, rule, (L.BagsDensifyGroup * len(groups))(*groups), len(groups), ws.data_ptr(), ws.numel(), P_new,
-                   accum.data_ptr(), denom.data_ptr(), radii.data_ptr(), prov.data_ptr())
-        for n, (group, p, st) in found.items():
-            param = torch.nn.Parameter(new[n][0].requires_grad_(True))
-            if p in optimizer.state:
-                stored = optimizer.state.pop(p)
-                if st is not None:
-                    stored["exp_avg"], stored["exp_avg_sq"] = new[n][1], new[n][2]
-                optimizer.state[param] = stored
-            group["params"][0] = param
-            setattr(self, self._GROUPS[n][0], param)
-        self.xyz_gradient_accum, self.denom, self.max_radii2D = accum, denom, radii
+            L.call("bags_densify_apply", dev, rule, groups, n_groups, ws.data_ptr(), ws.numel(), P_new,
+                   stats[0].data_ptr(), stats[1].data_ptr(), stats[2].data_ptr(), prov.data_ptr())
+        self._install_resized(optimizer, found, new, stats)
         return {"kept": int(counts[L.COUNT_KEPT]), "clones": int(counts[L.COUNT_CLONES]), "split": int(counts[L.COUNT_SPLIT]),
                 "pruned": int(counts[L.COUNT_PRUNED]), "P_new": P_new, "provenance": prov}
 
@@ -389,16 +404,6 @@ class GaussianBag:
                 L.require(what, f"{key} of group {n!r}", t, **self._ARG)
                 if t.shape != p.shape or t.shape[0] != P or t.device != dev:
                     raise RuntimeError(f"{what}: {key} of group {n!r} has shape {tuple(t.shape)} on {t.device}, expected {(P,) + tuple(p.shape[1:])} on {dev}")
-
-    def _mcmc_struct(self, found, outs=None):
-        gs = []
-        for n, (_, p, st) in found.items():
-            m, v = (st["exp_avg"], st["exp_avg_sq"]) if st is not None else (None, None)
-            o = outs[n] if outs is not None else (None, None, None)
-            width = int(math.prod(p.shape[1:]))
-            if width:                                                             # (SH degree 0: _features_rest is (P,0,3), nothing to move)
-                gs.append(L.BagsMcmcGroup(p.data_ptr(), L.ptr(m), L.ptr(v), L.ptr(o[0]), L.ptr(o[1]), L.ptr(o[2]), width, self._GROUPS[n][1]))
-        return (L.BagsMcmcGroup * len(gs))(*gs), len(gs)
 
     @staticmethod
     def _mcmc_rows(what: str, name: str, rows, P: int, like, count=None):
@@ -454,7 +459,7 @@ class GaussianBag:
         if sampled is None:
             alive = (~dead_mask).nonzero().reshape(-1)
             sampled = alive[self._mcmc_sample(torch.sigmoid(self._opacity.detach()[alive, 0]), D, generator)]
-        groups, n = self._mcmc_struct(found)
+        groups, n = self._group_structs(L.BagsMcmcGroup, found)
         dead32, sampled32 = dead.to(torch.int32), sampled.to(torch.int32).contiguous()
         ws = L.workspace(L.load().bags_mcmc_workspace_size(P), dev)
         L.call("bags_mcmc_relocate", dev, groups, n, P, dead32.data_ptr(), sampled32.data_ptr(), D, relocation_binoms(N_MAX, dev).data_ptr(), N_MAX,
@@ -484,28 +489,13 @@ class GaussianBag:
         if sampled is None:
             sampled = self._mcmc_sample(torch.sigmoid(self._opacity.detach()[:, 0]), A, generator)
         P_new = P + A
-        new = {}
-        for n, (_, p, st) in found.items():
-            shape = (P_new,) + tuple(p.shape[1:])
-            new[n] = [torch.empty(shape, dtype=torch.float32, device=dev) for _ in range(3 if st is not None else 1)] + [None, None]
-        groups, n_groups = self._mcmc_struct(found, new)
-        accum = torch.empty(P_new, 1, dtype=torch.float32, device=dev)
-        denom = torch.empty(P_new, 1, dtype=torch.float32, device=dev)
-        radii = torch.empty(P_new, dtype=torch.float32, device=dev)
+        new, stats = self._resized_outputs(found, P_new)
+        groups, n_groups = self._group_structs(L.BagsMcmcGroup, found, new)
         sampled32 = sampled.to(torch.int32).contiguous()
         ws = L.workspace(L.load().bags_mcmc_workspace_size(P), dev)
         L.call("bags_mcmc_add_new", dev, groups, n_groups, P, sampled32.data_ptr(), A, relocation_binoms(N_MAX, dev).data_ptr(), N_MAX, float(min_opacity),
-               ws.data_ptr(), ws.numel(), accum.data_ptr(), denom.data_ptr(), radii.data_ptr())
-        for n, (group, p, st) in found.items():
-            param = torch.nn.Parameter(new[n][0].requires_grad_(True))
-            if p in optimizer.state:
-                stored = optimizer.state.pop(p)
-                if st is not None:
-                    stored["exp_avg"], stored["exp_avg_sq"] = new[n][1], new[n][2]
-                optimizer.state[param] = stored
-            group["params"][0] = param
-            setattr(self, self._GROUPS[n][0], param)
-        self.xyz_gradient_accum, self.denom, self.max_radii2D = accum, denom, radii
+               ws.data_ptr(), ws.numel(), stats[0].data_ptr(), stats[1].data_ptr(), stats[2].data_ptr())
+        self._install_resized(optimizer, found, new, stats)
         return {"added": A, "P_new": P_new}
 
     @torch.no_grad()

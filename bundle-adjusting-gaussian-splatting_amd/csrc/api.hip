@@ -1032,38 +1032,62 @@ int bags_densify_plan(const BagsDensifyRule* r, void* workspace, size_t workspac
 
 static inline bool misaligned16(const void* p) { return (reinterpret_cast<size_t>(p) & 15u) != 0; }
 
+// What bags_densify_apply and the MCMC entry points both ask of their groups and of a resized set's outputs; the callers keep their order.
+static int check_group_count(const char* op, const void* groups, int32_t n_groups)
+{
+    if (n_groups < 1 || n_groups > BAGS_DENSIFY_MAX_GROUPS) return fail(BAGS_ERR_ARG, "%s: n_groups %d not in 1..%d", op, n_groups, BAGS_DENSIFY_MAX_GROUPS);
+    if (!groups) return fail(BAGS_ERR_ARG, "%s: NULL groups", op);
+    return BAGS_OK;
+}
+
+static int check_group_shape(const char* op, int k, int32_t width, int32_t role)
+{
+    if (width <= 0) return fail(BAGS_ERR_ARG, "%s: group %d: width %d <= 0", op, k, width);
+    if (role < BAGS_ROLE_OTHER || role > BAGS_ROLE_OPACITY) return fail(BAGS_ERR_ARG, "%s: group %d: unknown role %d", op, k, role);
+    const int want = role == BAGS_ROLE_XYZ || role == BAGS_ROLE_SCALING ? 3 : role == BAGS_ROLE_ROTATION ? 4 : role == BAGS_ROLE_OPACITY ? 1 : width;
+    if (width != want) return fail(BAGS_ERR_ARG, "%s: group %d: width %d, but its role %d has width %d", op, k, width, role, want);
+    return BAGS_OK;
+}
+
+static int check_group_aligned(const char* op, int k, const float* param_out, const float* exp_avg_out, const float* exp_avg_sq_out)
+{
+    if (misaligned16(param_out) || misaligned16(exp_avg_out) || misaligned16(exp_avg_sq_out))
+        return fail(BAGS_ERR_ARG, "%s: group %d: param_out / exp_avg_out / exp_avg_sq_out is not 16-byte aligned", op, k);
+    return BAGS_OK;
+}
+
+static int check_stats_out(const char* op, const float* accum_out, const float* denom_out, const float* radii_out)
+{
+    if (!accum_out || !denom_out || !radii_out) return fail(BAGS_ERR_ARG, "%s: NULL xyz_gradient_accum_out / denom_out / max_radii2D_out", op);
+    if (misaligned16(accum_out) || misaligned16(denom_out) || misaligned16(radii_out))
+        return fail(BAGS_ERR_ARG, "%s: xyz_gradient_accum_out / denom_out / max_radii2D_out is not 16-byte aligned", op);
+    return BAGS_OK;
+}
+
 int bags_densify_apply(const BagsDensifyRule* r, const BagsDensifyGroup* groups, int32_t n_groups, void* workspace, size_t workspace_bytes,
                        int64_t P_new, float* accum_out, float* denom_out, float* radii_out, int32_t* provenance, void* stream)
 {
     if (const int rc = check_densify_rule(r, workspace, workspace_bytes)) return rc;
-    if (n_groups < 1 || n_groups > BAGS_DENSIFY_MAX_GROUPS)
-        return fail(BAGS_ERR_ARG, "densify: n_groups %d not in 1..%d", n_groups, BAGS_DENSIFY_MAX_GROUPS);
-    if (!groups) return fail(BAGS_ERR_ARG, "densify: NULL groups");
+    if (const int rc = check_group_count("densify", groups, n_groups)) return rc;
     if (P_new < 0 || P_new > (int64_t)r->P * (r->N > 2 ? r->N : 2))
         return fail(BAGS_ERR_ARG, "densify: P_new %lld not in 0..P * max(2, N)", (long long)P_new);
     int n_xyz = 0, n_scaling = 0, n_rotation = 0;
     for (int k = 0; k < n_groups; ++k) {
         const BagsDensifyGroup& g = groups[k];
-        if (g.width <= 0) return fail(BAGS_ERR_ARG, "densify: group %d: width %d <= 0", k, g.width);
-        if (g.role < BAGS_ROLE_OTHER || g.role > BAGS_ROLE_OPACITY) return fail(BAGS_ERR_ARG, "densify: group %d: unknown role %d", k, g.role);
-        const int want = g.role == BAGS_ROLE_XYZ || g.role == BAGS_ROLE_SCALING ? 3 : g.role == BAGS_ROLE_ROTATION ? 4 : g.role == BAGS_ROLE_OPACITY ? 1 : g.width;
-        if (g.width != want) return fail(BAGS_ERR_ARG, "densify: group %d: width %d, but its role %d has width %d", k, g.width, g.role, want);
+        if (const int rc = check_group_shape("densify", k, g.width, g.role)) return rc;
         n_xyz += g.role == BAGS_ROLE_XYZ; n_scaling += g.role == BAGS_ROLE_SCALING; n_rotation += g.role == BAGS_ROLE_ROTATION;
         if (r->P > 0 && P_new > 0) {
             const int moments = (g.exp_avg != nullptr) + (g.exp_avg_sq != nullptr) + (g.exp_avg_out != nullptr) + (g.exp_avg_sq_out != nullptr);
             if (moments != 0 && moments != 4)
                 return fail(BAGS_ERR_ARG, "densify: group %d: exp_avg, exp_avg_sq and their outputs are given together or not at all (%d of 4 given)", k, moments);
             if (!g.param || !g.param_out) return fail(BAGS_ERR_ARG, "densify: group %d: NULL param / param_out", k);
-            if (misaligned16(g.param_out) || misaligned16(g.exp_avg_out) || misaligned16(g.exp_avg_sq_out))
-                return fail(BAGS_ERR_ARG, "densify: group %d: param_out / exp_avg_out / exp_avg_sq_out is not 16-byte aligned", k);
+            if (const int rc = check_group_aligned("densify", k, g.param_out, g.exp_avg_out, g.exp_avg_sq_out)) return rc;
         }
     }
     if (n_xyz != 1 || n_scaling != 1 || n_rotation != 1)
         return fail(BAGS_ERR_ARG, "densify: role xyz, scaling and rotation must each be given once (got %d, %d, %d)", n_xyz, n_scaling, n_rotation);
     if (r->P == 0 || P_new == 0) return BAGS_OK;
-    if (!accum_out || !denom_out || !radii_out) return fail(BAGS_ERR_ARG, "densify: NULL xyz_gradient_accum_out / denom_out / max_radii2D_out");
-    if (misaligned16(accum_out) || misaligned16(denom_out) || misaligned16(radii_out))
-        return fail(BAGS_ERR_ARG, "densify: xyz_gradient_accum_out / denom_out / max_radii2D_out is not 16-byte aligned");
+    if (const int rc = check_stats_out("densify", accum_out, denom_out, radii_out)) return rc;
     if (!provenance) return fail(BAGS_ERR_ARG, "densify: NULL provenance (it is the gather index of the copy)");
     if (misaligned16(provenance)) return fail(BAGS_ERR_ARG, "densify: provenance is not 16-byte aligned");
     HIP_TRY(launch_densify_apply(*r, groups, n_groups, workspace, (long long)P_new, accum_out, denom_out, radii_out, provenance, (hipStream_t)stream));
@@ -1187,17 +1211,13 @@ static int check_mcmc(const char* op, const BagsMcmcGroup* groups, int32_t n_gro
     if (P < 0) return fail(BAGS_ERR_ARG, "%s: P < 0 (got %d)", op, P);
     if (n_sampled < 0) return fail(BAGS_ERR_ARG, "%s: n_sampled < 0 (got %d)", op, n_sampled);
     if (!(min_opacity > 0.0 && min_opacity < 1.0)) return fail(BAGS_ERR_ARG, "%s: min_opacity %g not in (0, 1)", op, min_opacity);
-    if (n_groups < 1 || n_groups > BAGS_DENSIFY_MAX_GROUPS) return fail(BAGS_ERR_ARG, "%s: n_groups %d not in 1..%d", op, n_groups, BAGS_DENSIFY_MAX_GROUPS);
-    if (!groups) return fail(BAGS_ERR_ARG, "%s: NULL groups", op);
+    if (const int rc = check_group_count(op, groups, n_groups)) return rc;
     if (outputs && (int64_t)P + n_sampled > 0x7FFFFFFFll) return fail(BAGS_ERR_SIZE, "%s: the new set would hold %lld rows (> 2^31 - 1)", op, (long long)P + n_sampled);
     const bool work = P > 0 && n_sampled > 0;
     int n_opacity = 0, n_scaling = 0;
     for (int k = 0; k < n_groups; ++k) {
         const BagsMcmcGroup& g = groups[k];
-        if (g.width <= 0) return fail(BAGS_ERR_ARG, "%s: group %d: width %d <= 0", op, k, g.width);
-        if (g.role < BAGS_ROLE_OTHER || g.role > BAGS_ROLE_OPACITY) return fail(BAGS_ERR_ARG, "%s: group %d: unknown role %d", op, k, g.role);
-        const int want = g.role == BAGS_ROLE_XYZ || g.role == BAGS_ROLE_SCALING ? 3 : g.role == BAGS_ROLE_ROTATION ? 4 : g.role == BAGS_ROLE_OPACITY ? 1 : g.width;
-        if (g.width != want) return fail(BAGS_ERR_ARG, "%s: group %d: width %d, but its role %d has width %d", op, k, g.width, g.role, want);
+        if (const int rc = check_group_shape(op, k, g.width, g.role)) return rc;
         n_opacity += g.role == BAGS_ROLE_OPACITY; n_scaling += g.role == BAGS_ROLE_SCALING;
         if (!work) continue;
         if (!g.param) return fail(BAGS_ERR_ARG, "%s: group %d: NULL param", op, k);
@@ -1206,8 +1226,7 @@ static int check_mcmc(const char* op, const BagsMcmcGroup* groups, int32_t n_gro
             if (!g.param_out) return fail(BAGS_ERR_ARG, "%s: group %d: NULL param_out", op, k);
             if ((g.exp_avg != nullptr) != (g.exp_avg_out != nullptr) || (g.exp_avg != nullptr) != (g.exp_avg_sq_out != nullptr))
                 return fail(BAGS_ERR_ARG, "%s: group %d: exp_avg_out and exp_avg_sq_out are given exactly when the moments are", op, k);
-            if (misaligned16(g.param_out) || misaligned16(g.exp_avg_out) || misaligned16(g.exp_avg_sq_out))
-                return fail(BAGS_ERR_ARG, "%s: group %d: param_out / exp_avg_out / exp_avg_sq_out is not 16-byte aligned", op, k);
+            if (const int rc = check_group_aligned(op, k, g.param_out, g.exp_avg_out, g.exp_avg_sq_out)) return rc;
         }
     }
     if (n_opacity != 1 || n_scaling != 1) return fail(BAGS_ERR_ARG, "%s: role opacity and scaling must each be given once (got %d, %d)", op, n_opacity, n_scaling);
@@ -1234,9 +1253,7 @@ int bags_mcmc_add_new(const BagsMcmcGroup* groups, int32_t n_groups, int32_t P, 
 {
     if (const int rc = check_mcmc("mcmc_add_new", groups, n_groups, P, sampled, n_sampled, binoms, n_max, min_opacity, workspace, workspace_bytes, true)) return rc;
     if (P == 0 || n_sampled == 0) return BAGS_OK;
-    if (!accum_out || !denom_out || !radii_out) return fail(BAGS_ERR_ARG, "mcmc_add_new: NULL xyz_gradient_accum_out / denom_out / max_radii2D_out");
-    if (misaligned16(accum_out) || misaligned16(denom_out) || misaligned16(radii_out))
-        return fail(BAGS_ERR_ARG, "mcmc_add_new: xyz_gradient_accum_out / denom_out / max_radii2D_out is not 16-byte aligned");
+    if (const int rc = check_stats_out("mcmc_add_new", accum_out, denom_out, radii_out)) return rc;
     HIP_TRY(launch_mcmc_add_new(groups, n_groups, P, sampled, n_sampled, binoms, n_max, min_opacity, workspace, accum_out, denom_out, radii_out,
                                 (hipStream_t)stream));
     return BAGS_OK;

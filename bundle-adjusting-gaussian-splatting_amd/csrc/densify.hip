@@ -15,19 +15,17 @@
 // Output order (what the reference's cat / mask sequence produces): kept originals in source order, clones in source order, then
 // the children block with child k of the j-th surviving split row at k * S + j.
 // Fixed order, no atomics: bitwise reproducible.  Built with -ffp-contract=off: the children's values are the operations spelled
-// here, each rounded once.
+// here, each rounded once.  apply's walk over the output elements is the one of csrc/row_rebuild.h, which mcmc_add_new_kernel shares.
 #include "bags_common.h"
 #include "binning_common.h"
 #include "philox_normal.h"
+#include "row_rebuild.h"
 
 #define DENS_BLOCK 256
-#define DENS_UNROLL 4
-#define DENS_CHUNK (DENS_BLOCK * DENS_UNROLL * 4)          // output elements per workgroup of densify_apply
 #define DENS_COUNTS 5                                       // kept, clones out, split rows out, clone-selected, split-selected
-#define DENS_MAX_SEGS (3 * BAGS_DENSIFY_MAX_GROUPS + 3)
 
 enum { F_KEPT = 1, F_CLONE = 2, F_CHILD = 4, F_CLONE_SEL = 8, F_SPLIT_SEL = 16 };
-enum { SEG_COPY = 0, SEG_XYZ = 1, SEG_SCALING = 2, SEG_MOMENT = 3, SEG_ZERO = 4 };
+enum { SEG_XYZ = 1, SEG_SCALING = 2 };                      // beside ROWSEG_COPY / MOMENT / ZERO
 
 struct DensWorkspace { u32* cls; u32* sums; u32* totals; int nb; };
 
@@ -159,13 +157,8 @@ __global__ void __launch_bounds__(DENS_BLOCK) densify_map_kernel(const u32* __re
 }
 
 // ------------------------------------------------------------------------------------------------ apply
-struct DensSeg {
-    const float* src; float* dst;
-    u32 first_block;               // of this segment in the grid; 0xFFFFFFFF for an unused slot
-    u32 width, mode, pad;
-};
 struct ApplyParams {
-    DensSeg seg[DENS_MAX_SEGS];
+    RowSeg seg[ROWSEG_MAX_SEGS];
     const int2* prov;
     const float* xyz; const float* scaling; const float* rotation; const float* noise;
     long long P_new;
@@ -193,12 +186,12 @@ __device__ __forceinline__ float child_xyz(const ApplyParams& a, const size_t s,
     return (m0 * v0 + m1 * v1 + m2 * v2) + a.xyz[3 * s + c];
 }
 
-__device__ __forceinline__ float dens_value(const ApplyParams& a, const DensSeg& G, const int2 ent, const u32 c)
+__device__ __forceinline__ float dens_value(const ApplyParams& a, const RowSeg& G, const int2 ent, const u32 c)
 {
     if ((u32)ent.x >= (u32)a.P || ent.y >= 2 + a.N) return 0.0f;      // a map the plan did not write (mismatched calls): nothing is read
     const size_t s = (size_t)ent.x;
     const int kind = ent.y;
-    if (G.mode == SEG_MOMENT) return kind == 0 ? G.src[s * G.width + c] : 0.0f;
+    if (G.mode == ROWSEG_MOMENT) return kind == 0 ? G.src[s * G.width + c] : 0.0f;
     if (kind >= 2) {
         if (G.mode == SEG_XYZ) return child_xyz(a, s, (u32)(kind - 2), c);
         if (G.mode == SEG_SCALING) return logf(expf(G.src[s * G.width + c]) / a.child_div);
@@ -206,53 +199,11 @@ __device__ __forceinline__ float dens_value(const ApplyParams& a, const DensSeg&
     return G.src[s * G.width + c];
 }
 
-__global__ void __launch_bounds__(DENS_BLOCK) densify_apply_kernel(const ApplyParams a)
+__global__ void __launch_bounds__(ROWSEG_BLOCK) densify_apply_kernel(const ApplyParams a)
 {
-    const u32 b = blockIdx.x;
-    DensSeg G = a.seg[0];
-#pragma unroll
-    for (int k = 1; k < DENS_MAX_SEGS; ++k)
-        if (b >= a.seg[k].first_block) G = a.seg[k];
-    const u32 w = G.width;
-    const size_t n = (size_t)a.P_new * w;
-    const size_t e0 = (size_t)(b - G.first_block) * DENS_CHUNK;           // first element of the chunk, < n
-    const size_t n4 = n >> 2;                                            // dst is 16-byte aligned (validated by the caller)
-    float4* __restrict__ dst4 = reinterpret_cast<float4*>(G.dst);
-
-    if (G.mode == SEG_ZERO) {
-#pragma unroll
-        for (int j = 0; j < DENS_UNROLL; ++j) {
-            const size_t i = (e0 >> 2) + (size_t)j * DENS_BLOCK + threadIdx.x;
-            if (i < n4) dst4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        if (e0 + DENS_CHUNK >= n) { const size_t t = (n4 << 2) + threadIdx.x; if (t < n) G.dst[t] = 0.0f; }
-        return;
-    }
-
-    const size_t row_base = e0 / w;                                      // wave-uniform
-    const u32 rem_base = (u32)(e0 - row_base * w);                       // < w
-#pragma unroll
-    for (int j = 0; j < DENS_UNROLL; ++j) {
-        const u32 li = (u32)j * DENS_BLOCK + threadIdx.x;                // float4 within the chunk
-        const size_t i = (e0 >> 2) + li;
-        if (i >= n4) continue;
-        const u32 t = rem_base + 4u * li;                                // < w + DENS_CHUNK
-        const u32 q = t / w;
-        u32 c = t - q * w;
-        size_t row = row_base + q;
-        int2 ent = a.prov[row];
-        float o[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            o[k] = dens_value(a, G, ent, c);
-            if (++c == w) { c = 0; ++row; if (k < 3 && row < (size_t)a.P_new) ent = a.prov[row]; }
-        }
-        dst4[i] = make_float4(o[0], o[1], o[2], o[3]);
-    }
-    if (e0 + DENS_CHUNK >= n) {                                          // the n % 4 elements after the last float4
-        const size_t t = (n4 << 2) + threadIdx.x;
-        if (t < n) { const size_t row = t / w; G.dst[t] = dens_value(a, G, a.prov[row], (u32)(t - row * w)); }
-    }
+    RowSeg G;                                                            // found here, not in the walker: see row_rebuild.h
+    rowseg_find(G, a.seg, blockIdx.x);
+    rowseg_walk(G, a.P_new, [&](const size_t row) { return a.prov[row]; }, [&](const int2 ent, const u32 c) { return dens_value(a, G, ent, c); });
 }
 
 // ------------------------------------------------------------------------------------------------ reset_opacity
@@ -292,32 +243,22 @@ hipError_t launch_densify_apply(const BagsDensifyRule& r, const BagsDensifyGroup
     hipLaunchKernelGGL(densify_map_kernel, dim3((unsigned)w.nb), dim3(DENS_BLOCK), 0, st, w.cls, w.sums, w.totals, w.nb, r.P, r.N, P_new,
                        reinterpret_cast<int2*>(provenance));
     ApplyParams a;
-    size_t blocks = 0;
-    int n_seg = 0;
-    auto add = [&](const float* src, float* dst, int width, u32 mode) {
-        DensSeg& G = a.seg[n_seg++];
-        G = DensSeg{src, dst, (u32)blocks, (u32)width, mode, 0};
-        blocks += ((size_t)P_new * (size_t)width + DENS_CHUNK - 1) / DENS_CHUNK;
-    };
     a.xyz = a.scaling = a.rotation = nullptr;
     for (int k = 0; k < n_groups; ++k) {
-        const BagsDensifyGroup& g = groups[k];
-        const u32 mode = g.role == BAGS_ROLE_XYZ ? SEG_XYZ : g.role == BAGS_ROLE_SCALING ? SEG_SCALING : SEG_COPY;
-        if (g.role == BAGS_ROLE_XYZ) a.xyz = g.param;
-        if (g.role == BAGS_ROLE_SCALING) a.scaling = g.param;
-        if (g.role == BAGS_ROLE_ROTATION) a.rotation = g.param;
-        add(g.param, g.param_out, g.width, mode);
-        if (g.exp_avg) { add(g.exp_avg, g.exp_avg_out, g.width, SEG_MOMENT); add(g.exp_avg_sq, g.exp_avg_sq_out, g.width, SEG_MOMENT); }
+        if (groups[k].role == BAGS_ROLE_XYZ) a.xyz = groups[k].param;
+        if (groups[k].role == BAGS_ROLE_SCALING) a.scaling = groups[k].param;
+        if (groups[k].role == BAGS_ROLE_ROTATION) a.rotation = groups[k].param;
     }
-    add(nullptr, accum_out, 1, SEG_ZERO); add(nullptr, denom_out, 1, SEG_ZERO); add(nullptr, radii_out, 1, SEG_ZERO);
-    for (int k = n_seg; k < DENS_MAX_SEGS; ++k) a.seg[k] = DensSeg{nullptr, nullptr, 0xFFFFFFFFu, 1, SEG_ZERO, 0};
-    if (blocks >= 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const unsigned blocks = rowseg_table(a.seg, groups, n_groups, P_new,
+                                         [](int role) -> u32 { return role == BAGS_ROLE_XYZ ? SEG_XYZ : role == BAGS_ROLE_SCALING ? SEG_SCALING : ROWSEG_COPY; },
+                                         accum_out, denom_out, radii_out);
+    if (!blocks) return hipErrorInvalidValue;
     a.prov = reinterpret_cast<const int2*>(provenance);
     a.noise = r.noise;
     a.P_new = P_new; a.P = r.P; a.N = r.N;
     a.seed_lo = (u32)r.seed; a.seed_hi = (u32)(r.seed >> 32);
     a.child_div = (float)(0.8 * r.N);
-    hipLaunchKernelGGL(densify_apply_kernel, dim3((unsigned)blocks), dim3(DENS_BLOCK), 0, st, a);
+    hipLaunchKernelGGL(densify_apply_kernel, dim3(blocks), dim3(ROWSEG_BLOCK), 0, st, a);
     return hipGetLastError();
 }
 

@@ -14,18 +14,16 @@
 //
 // compute_relocation's alternating sum is ill-conditioned, and the relocated values pass through logit / log; both, and the noise step,
 // are evaluated in double from the fp32 inputs and rounded to fp32 once.  Built with -ffp-contract=off.  No floating-point atomics:
-// two runs give the same bits.
+// two runs give the same bits.  add_new's walk over the output elements is the one of csrc/row_rebuild.h, which densify_apply_kernel shares.
 #include "bags_common.h"
 #include "philox_normal.h"
+#include "row_rebuild.h"
 #include <float.h>
 
 #define MCMC_BLOCK 256
-#define MCMC_UNROLL 4
-#define MCMC_CHUNK (MCMC_BLOCK * MCMC_UNROLL * 4)          // output elements per workgroup of mcmc_add_new_kernel
-#define MCMC_MAX_SEGS (3 * BAGS_DENSIFY_MAX_GROUPS + 3)
 #define MCMC_TABLE (BAGS_MCMC_MAX_BINOMS * BAGS_MCMC_MAX_BINOMS)
 
-enum { MSEG_COPY = 0, MSEG_OPACITY = 1, MSEG_SCALING = 2, MSEG_MOMENT = 3, MSEG_ZERO = 4 };
+enum { MSEG_OPACITY = 1, MSEG_SCALING = 2 };               // beside ROWSEG_COPY / MOMENT / ZERO
 
 struct McmcWorkspace { u32* count; float4* stage; };
 
@@ -133,7 +131,7 @@ struct RelocParams {
 __global__ void __launch_bounds__(MCMC_BLOCK) mcmc_relocate_kernel(const RelocParams a)
 {
     const u32 b = blockIdx.x;
-    RelocSeg G = a.seg[0];
+    RelocSeg G = a.seg[0];                                               // rowseg_find (row_rebuild.h) costs this kernel 16 SGPRs: spelled here
 #pragma unroll
     for (int k = 1; k < BAGS_DENSIFY_MAX_GROUPS; ++k)
         if (b >= a.seg[k].first_block) G = a.seg[k];
@@ -145,7 +143,7 @@ __global__ void __launch_bounds__(MCMC_BLOCK) mcmc_relocate_kernel(const RelocPa
     const int s = a.sampled[j], d = a.dead[j];
     if ((u32)s >= (u32)a.P || (u32)d >= (u32)a.P) return;                 // rows outside the set: nothing is read or written
     const size_t se = (size_t)s * w + c, de = (size_t)d * w + c;
-    if (G.mode == MSEG_COPY) G.param[de] = G.param[se];
+    if (G.mode == ROWSEG_COPY) G.param[de] = G.param[se];
     else {                                                               // every j that lists s stores the same bits to it
         const float val = staged(a.stage[s], G.mode, c);
         G.param[de] = val; G.param[se] = val;
@@ -154,13 +152,8 @@ __global__ void __launch_bounds__(MCMC_BLOCK) mcmc_relocate_kernel(const RelocPa
 }
 
 // ------------------------------------------------------------------------------------------------ add_new
-struct AddSeg {
-    const float* src; float* dst;
-    u32 first_block;
-    u32 width, mode, pad;
-};
 struct AddParams {
-    AddSeg seg[MCMC_MAX_SEGS];
+    RowSeg seg[ROWSEG_MAX_SEGS];
     const int32_t* sampled; const u32* count; const float4* stage;
     long long P_new;
     int P;
@@ -175,61 +168,19 @@ __device__ __forceinline__ AddRow add_row(const AddParams& a, const size_t row)
     return r;
 }
 
-__device__ __forceinline__ float add_value(const AddParams& a, const AddSeg& G, const AddRow r, const u32 c)
+__device__ __forceinline__ float add_value(const AddParams& a, const RowSeg& G, const AddRow r, const u32 c)
 {
     if (!r.valid) return 0.0f;
-    if (G.mode == MSEG_MOMENT) return r.source ? 0.0f : G.src[r.s * G.width + c];
-    if (r.source && G.mode != MSEG_COPY) return staged(a.stage[r.s], G.mode, c);
+    if (G.mode == ROWSEG_MOMENT) return r.source ? 0.0f : G.src[r.s * G.width + c];
+    if (r.source && G.mode != ROWSEG_COPY) return staged(a.stage[r.s], G.mode, c);
     return G.src[r.s * G.width + c];
 }
 
-__global__ void __launch_bounds__(MCMC_BLOCK) mcmc_add_new_kernel(const AddParams a)
+__global__ void __launch_bounds__(ROWSEG_BLOCK) mcmc_add_new_kernel(const AddParams a)
 {
-    const u32 b = blockIdx.x;
-    AddSeg G = a.seg[0];
-#pragma unroll
-    for (int k = 1; k < MCMC_MAX_SEGS; ++k)
-        if (b >= a.seg[k].first_block) G = a.seg[k];
-    const u32 w = G.width;
-    const size_t n = (size_t)a.P_new * w;
-    const size_t e0 = (size_t)(b - G.first_block) * MCMC_CHUNK;           // first element of the chunk, < n
-    const size_t n4 = n >> 2;                                            // dst is 16-byte aligned (validated by the caller)
-    float4* __restrict__ dst4 = reinterpret_cast<float4*>(G.dst);
-
-    if (G.mode == MSEG_ZERO) {
-#pragma unroll
-        for (int j = 0; j < MCMC_UNROLL; ++j) {
-            const size_t i = (e0 >> 2) + (size_t)j * MCMC_BLOCK + threadIdx.x;
-            if (i < n4) dst4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        if (e0 + MCMC_CHUNK >= n) { const size_t t = (n4 << 2) + threadIdx.x; if (t < n) G.dst[t] = 0.0f; }
-        return;
-    }
-
-    const size_t row_base = e0 / w;                                      // wave-uniform
-    const u32 rem_base = (u32)(e0 - row_base * w);                       // < w
-#pragma unroll
-    for (int j = 0; j < MCMC_UNROLL; ++j) {
-        const u32 li = (u32)j * MCMC_BLOCK + threadIdx.x;                // float4 within the chunk
-        const size_t i = (e0 >> 2) + li;
-        if (i >= n4) continue;
-        const u32 t = rem_base + 4u * li;                                // < w + MCMC_CHUNK
-        const u32 q = t / w;
-        u32 c = t - q * w;
-        size_t row = row_base + q;
-        AddRow ent = add_row(a, row);
-        float o[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            o[k] = add_value(a, G, ent, c);
-            if (++c == w) { c = 0; ++row; if (k < 3 && row < (size_t)a.P_new) ent = add_row(a, row); }
-        }
-        dst4[i] = make_float4(o[0], o[1], o[2], o[3]);
-    }
-    if (e0 + MCMC_CHUNK >= n) {                                          // the n % 4 elements after the last float4
-        const size_t t = (n4 << 2) + threadIdx.x;
-        if (t < n) { const size_t row = t / w; G.dst[t] = add_value(a, G, add_row(a, row), (u32)(t - row * w)); }
-    }
+    RowSeg G;                                                            // found here, not in the walker: see row_rebuild.h
+    rowseg_find(G, a.seg, blockIdx.x);
+    rowseg_walk(G, a.P_new, [&](const size_t row) { return add_row(a, row); }, [&](const AddRow r, const u32 c) { return add_value(a, G, r, c); });
 }
 
 // ------------------------------------------------------------------------------------------------ noise
@@ -289,7 +240,7 @@ static hipError_t launch_mcmc_stage(const BagsMcmcGroup* groups, int n_groups, i
     return hipGetLastError();
 }
 
-static inline u32 mcmc_mode(int role) { return role == BAGS_ROLE_OPACITY ? MSEG_OPACITY : role == BAGS_ROLE_SCALING ? MSEG_SCALING : MSEG_COPY; }
+static inline u32 mcmc_mode(int role) { return role == BAGS_ROLE_OPACITY ? MSEG_OPACITY : role == BAGS_ROLE_SCALING ? MSEG_SCALING : ROWSEG_COPY; }
 
 hipError_t launch_mcmc_relocate(const BagsMcmcGroup* groups, int n_groups, int P, const int32_t* dead, const int32_t* sampled, int n_sampled,
                                 const float* binoms, int n_max, double min_opacity, void* workspace, hipStream_t st)
@@ -304,7 +255,7 @@ hipError_t launch_mcmc_relocate(const BagsMcmcGroup* groups, int n_groups, int P
         a.seg[k] = RelocSeg{g.param, g.exp_avg, g.exp_avg_sq, (u32)blocks, (u32)g.width, mcmc_mode(g.role), 0};
         blocks += ((size_t)n_sampled * (size_t)g.width + MCMC_BLOCK - 1) / MCMC_BLOCK;
     }
-    for (int k = n_groups; k < BAGS_DENSIFY_MAX_GROUPS; ++k) a.seg[k] = RelocSeg{nullptr, nullptr, nullptr, 0xFFFFFFFFu, 1, MSEG_COPY, 0};
+    for (int k = n_groups; k < BAGS_DENSIFY_MAX_GROUPS; ++k) a.seg[k] = RelocSeg{nullptr, nullptr, nullptr, 0xFFFFFFFFu, 1, ROWSEG_COPY, 0};
     if (blocks >= 0x7FFFFFFFull) return hipErrorInvalidValue;
     a.dead = dead; a.sampled = sampled; a.stage = w.stage; a.P = P; a.D = n_sampled;
     hipLaunchKernelGGL(mcmc_relocate_kernel, dim3((unsigned)blocks), dim3(MCMC_BLOCK), 0, st, a);
@@ -319,23 +270,10 @@ hipError_t launch_mcmc_add_new(const BagsMcmcGroup* groups, int n_groups, int P,
     if (e != hipSuccess) return e;
     const long long P_new = (long long)P + n_sampled;
     AddParams a;
-    size_t blocks = 0;
-    int n_seg = 0;
-    auto add = [&](const float* src, float* dst, int width, u32 mode) {
-        AddSeg& G = a.seg[n_seg++];
-        G = AddSeg{src, dst, (u32)blocks, (u32)width, mode, 0};
-        blocks += ((size_t)P_new * (size_t)width + MCMC_CHUNK - 1) / MCMC_CHUNK;
-    };
-    for (int k = 0; k < n_groups; ++k) {
-        const BagsMcmcGroup& g = groups[k];
-        add(g.param, g.param_out, g.width, mcmc_mode(g.role));
-        if (g.exp_avg) { add(g.exp_avg, g.exp_avg_out, g.width, MSEG_MOMENT); add(g.exp_avg_sq, g.exp_avg_sq_out, g.width, MSEG_MOMENT); }
-    }
-    add(nullptr, accum_out, 1, MSEG_ZERO); add(nullptr, denom_out, 1, MSEG_ZERO); add(nullptr, radii_out, 1, MSEG_ZERO);
-    for (int k = n_seg; k < MCMC_MAX_SEGS; ++k) a.seg[k] = AddSeg{nullptr, nullptr, 0xFFFFFFFFu, 1, MSEG_ZERO, 0};
-    if (blocks >= 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const unsigned blocks = rowseg_table(a.seg, groups, n_groups, P_new, mcmc_mode, accum_out, denom_out, radii_out);
+    if (!blocks) return hipErrorInvalidValue;
     a.sampled = sampled; a.count = w.count; a.stage = w.stage; a.P_new = P_new; a.P = P;
-    hipLaunchKernelGGL(mcmc_add_new_kernel, dim3((unsigned)blocks), dim3(MCMC_BLOCK), 0, st, a);
+    hipLaunchKernelGGL(mcmc_add_new_kernel, dim3(blocks), dim3(ROWSEG_BLOCK), 0, st, a);
     return hipGetLastError();
 }
 

@@ -78,7 +78,7 @@ def _compare(label, opt, bag, stats, noise, N=2, mode="published", rule=D.RULE, 
             assert float(st["step"]) == steps[n] == float(st32["step"]) and not st["step"].is_cuda, n
             for key in ("exp_avg", "exp_avg_sq"):
                 assert torch.equal(st[key].cpu(), st32[key]), (n, key)              # kept rows bit for bit, new rows exact zeros
-                if int((kind != D.KEPT).sum()):
+                if int((kind != D.KEPT).sum()) and st[key].numel():                 # (a group of width 0 has no element to look at)
                     assert st[key].cpu()[kind != D.KEPT].abs().max().item() == 0.0
     assert len(opt.state) == sum(s is not None for s in steps.values())           # the old parameters' entries are gone
     for name, shape in (("xyz_gradient_accum", (b["P_new"], 1)), ("denom", (b["P_new"], 1)), ("max_radii2D", (b["P_new"],))):
@@ -165,6 +165,24 @@ def test_without_state_and_with_torch_adam():
         q.grad = torch.full_like(q, 0.01)
     opt.step()                                                      # torch.optim.Adam goes on with the moved state
     assert all(float(opt.state[q]["step"]) == 4.0 for q in bag.leaves())
+
+
+def test_degree_zero_bag():
+    """SH degree 0: ``_features_rest`` is (P,0,3), a group with nothing to move.  It is left out of the launch (as relocate and add_new
+    leave it out) and comes back (P_new,0,3), installed in the optimizer like the other five; before csrc/row_rebuild.h the call raised
+    ``group 2: width 0 <= 0``.  The restatement on the CPU, fp32 and fp64: kept 11, clones 11, split 54, pruned 0, P_new 130, margin
+    6.8e-3; nothing is pruned, hence populated=False."""
+    import mcmc_reference as M
+    from bags_raster import GaussianAdam
+    opt, stats = M.make_case(65, 1, GaussianAdam, DEV, sh_degree=0)
+    bag = _bag_of(opt, stats, GaussianBag(0))
+    bag.active_sh_degree = 0
+    noise = torch.randn(65, 2, 3, generator=torch.Generator().manual_seed(65))
+    out, ref = _compare("degree0", opt, bag, stats, noise, populated=False)
+    assert (ref["kept"], ref["clones"], ref["split"], ref["pruned"], ref["P_new"]) == (11, 11, 54, 0, 130)
+    rest = bag._features_rest
+    assert tuple(rest.shape) == (130, 0, 3) and rest is D.params(opt)["f_rest"] and rest.is_leaf and rest.requires_grad
+    assert len(opt.state) == 6 and tuple(opt.state[rest]["exp_avg"].shape) == tuple(opt.state[rest]["exp_avg_sq"].shape) == (130, 0, 3)
 
 
 def _run(seed_case, **kw):

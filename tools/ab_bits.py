@@ -24,7 +24,14 @@ Since csrc/sh_rows.h (the SH gradient row write-out shared by K9, sh_grad_from_v
 also holds, at the same image size: steps of V = 3 views through rasterizer.FactoredSH, the second step accumulating (M = 16 packed
 and split: sh_grad_from_views_kernel<0> / <1>; M = 9 packed and M = 4 split: the generic kernel; P in {129, 257, 3000}), and the
 backwards of sh_colors and sh_colors_views with V = 3 and every gradient asked for (K in {16, 9, 4} packed and split, K = 1 packed,
-P in {1, 257, 3000}: the store pass and the campos reduction both run).  They count as the others do."""
+P in {1, 257, 3000}: the store pass and the campos reduction both run).  They count as the others do.
+
+Since csrc/row_rebuild.h (the rebuild of a resized set shared by densify_apply_kernel and mcmc_add_new_kernel) the list also holds
+GaussianBag.densify_and_prune (P in {63, 1001}, N = 2 and, at 1001, N = 3; the children's normals given and from the in-kernel
+generator; with and without optimizer state) and GaussianBag.add_new / relocate (P in {64, 65, 257, 4099}, SH degree 0 and 3, with
+and without state, ``sampled`` given: the multinomial draw does not repeat at large P and must not decide a comparison).  Saved:
+every parameter, both moments, the three statistics, provenance and the returned counts.  densify_and_prune at degree 0 runs on
+the product only (before row_rebuild.h the call raised there): it must run, and is not compared."""
 import argparse
 import itertools
 import os
@@ -76,10 +83,69 @@ def case_list():
         for K, colour in ((16, "packed"), (16, "split"), (9, "packed"), (9, "split"), (4, "packed"), (4, "split"), (1, "packed")):
             add(f"shc_k{K}_{colour}_p{P}", P, 90 + K, colour)
             cases[-1].update(kind="shc", M=K)
+    # csrc/row_rebuild.h: the resized set of densify_and_prune and add_new; relocate beside them (it shares the stage kernels)
+    def resize(kind, name, P, seed, **kw):
+        add(name, P, seed)
+        cases[-1].update(kind=kind, **kw)
+    for P, N in ((63, 2), (1001, 2), (1001, 3)):
+        for given, state in itertools.product((True, False), repeat=2):
+            resize("densify", f"dens_p{P}_n{N}_{'noise' if given else 'seed'}_{'state' if state else 'stateless'}", P, 110 + N, N=N, given=given, state=state)
+    for kind, P, deg, state in itertools.product(("add_new", "relocate"), (64, 65, 257, 4099), (0, 3), (True, False)):
+        resize(kind, f"{kind}_p{P}_deg{deg}_{'state' if state else 'stateless'}", P, 120 + deg, deg=deg, state=state)
+    resize("densify", "dens_p65_deg0", 65, 1, N=2, given=True, state=True, deg=0, product_only=True)
     return cases
 
 
 VIEWS = 3
+LEAF = {"xyz": "_xyz", "f_dc": "_features_dc", "f_rest": "_features_rest", "opacity": "_opacity", "scaling": "_scaling", "rotation": "_rotation"}
+
+
+def run_resize(c, dev):
+    """GPU (child): one call of densify_and_prune / add_new / relocate on a seeded set; everything the call may write is saved."""
+    import densify_reference as D
+    import mcmc_reference as M
+    from bags_raster import GaussianAdam
+    from bags_raster.gaussians import GaussianBag
+    P, kind, deg = c["P"], c["kind"], c.get("deg", 3)
+    g = torch.Generator().manual_seed(3000 + c["seed"])
+    if kind == "densify" and deg == 3:
+        opt, stats, noise = D.make_case(P, c["seed"], GaussianAdam, dev, steps=3 if c["state"] else 0)
+        if not c["state"]:
+            opt.state.clear()
+    else:
+        opt, stats = M.make_case(P, c["seed"], GaussianAdam, dev, sh_degree=deg, state=c["state"])
+        noise = torch.randn(P, 3, 3, generator=g)
+    bag = GaussianBag(deg)
+    for n, q in D.params(opt).items():
+        setattr(bag, LEAF[n], q)
+    bag.xyz_gradient_accum, bag.denom, bag.max_radii2D = stats["xyz_gradient_accum"], stats["denom"], stats["max_radii2D"]
+    bag.active_sh_degree = deg
+    res = {}
+    if kind == "densify":
+        how = dict(noise=noise[:, :c["N"]].contiguous().to(dev)) if c["given"] else dict(seed=1234 + P)
+        out = bag.densify_and_prune(opt, N=c["N"], **how, **D.RULE)
+        res["provenance"] = out.pop("provenance")
+    elif kind == "add_new":
+        A = int(1.05 * P) - P
+        sampled = torch.randint(0, P, (A,), generator=g)
+        sampled[-1] = sampled[0]                                     # a source drawn twice
+        out = bag.add_new(opt, 10 * P, sampled=sampled.to(dev))
+    else:
+        dead = torch.zeros(P, dtype=torch.bool)
+        dead[::3] = True
+        alive = (~dead).nonzero().reshape(-1)
+        sampled = alive[torch.randint(0, alive.numel(), (int(dead.sum()),), generator=g)]
+        sampled[-1] = sampled[0]
+        out = bag.relocate(opt, dead.to(dev), sampled=sampled.to(dev))
+    res["counts"] = torch.tensor([int(v) for _, v in sorted(out.items())])
+    for n, q in D.params(opt).items():
+        assert q is getattr(bag, LEAF[n])
+        res[n] = q.detach()
+        if q in opt.state:
+            res[n + ".exp_avg"], res[n + ".exp_avg_sq"] = opt.state[q]["exp_avg"], opt.state[q]["exp_avg_sq"]
+    res.update(xyz_gradient_accum=bag.xyz_gradient_accum, denom=bag.denom, max_radii2D=bag.max_radii2D, num_rendered=torch.tensor([0]))
+    torch.cuda.synchronize(dev)
+    return {k: t.cpu().numpy() for k, t in res.items()}
 
 
 def run_factored(c, dev):
@@ -214,6 +280,8 @@ def run_case(c, dev):
         return run_factored(c, dev)
     if c.get("kind") == "shc":
         return run_shc(c, dev)
+    if c.get("kind") in ("densify", "add_new", "relocate"):
+        return run_resize(c, dev)
     from bags_raster import GaussianRasterizer, debug_views
     from bags_raster import rasterizer as R
     from scenes import camera_tensors, hip_settings
@@ -273,6 +341,8 @@ def child(path):
     from bags_raster import _lib
     out = {}
     for c in case_list():
+        if c.get("product_only") and os.environ.get("BAGS_RASTER_LIB"):
+            continue
         for k, a in run_case(c, dev).items():
             out[f"{c['name']}/{k}"] = a
     np.savez(path, **out)
@@ -319,6 +389,11 @@ def main():
     same = lambda u, v: u.dtype == v.dtype and u.shape == v.shape and u.tobytes() == v.tobytes()     # noqa: E731
     bad, covered_k9, covered_k1, covered_rows = 0, set(), set(), set()
     for c in cases:
+        if c.get("product_only"):
+            n = sum(k.startswith(c["name"] + "/") for k in runs["product"].files)
+            print(f"{c['name']:22s} product only: {n} tensors saved, not compared")
+            bad += n == 0
+            continue
         keys = sorted(k for k in runs["alt_1"].files if k.startswith(c["name"] + "/"))
         if sorted(k for k in runs["product"].files if k.startswith(c["name"] + "/")) != keys:
             print(f"{c['name']}: the product saved other tensors than the alternative"); bad += 1
@@ -335,6 +410,9 @@ def main():
         elif c.get("kind") == "shc":
             rows = ("sh_colors(_views)_bwd", c["M"], c["colour"])
             k9, tag = None, "%s K=%d %s" % rows
+        elif c.get("kind"):
+            rows = ("row_rebuild", c["kind"])
+            k9, tag = None, "%s %s" % rows
         if unstable:
             print(f"{c['name']:22s} NOT BIT-STABLE on the alternative itself, not counted ({tag}): " + " ".join(k.split("/")[1] for k in unstable))
             continue
@@ -352,10 +430,12 @@ def main():
     miss1 = [t for t in itertools.product((False, True), repeat=2) if t not in covered_k1]
     want_rows = {("sh_grad_from_views", (16, "packed")), ("sh_grad_from_views", (16, "split")), ("sh_grad_from_views", 9), ("sh_grad_from_views", 4)}
     want_rows |= {("sh_colors(_views)_bwd", K, col) for K in (16, 9, 4) for col in ("packed", "split")} | {("sh_colors(_views)_bwd", 1, "packed")}
+    want_rows |= {("row_rebuild", kind) for kind in ("densify", "add_new", "relocate")}
     miss_rows = sorted(map(str, want_rows - covered_rows))
     print(f"instances covered by stable cases: preprocess_bwd_kernel {len(covered_k9)} of 16, K1 {len(covered_k1)} of 4, "
           f"sh_grad_from_views {sum(r[0] == 'sh_grad_from_views' for r in covered_rows)} of 4, "
-          f"colour backwards {sum(r[0] != 'sh_grad_from_views' for r in covered_rows)} of 7")
+          f"colour backwards {sum(r[0] == 'sh_colors(_views)_bwd' for r in covered_rows)} of 7, "
+          f"resized sets {sum(r[0] == 'row_rebuild' for r in covered_rows)} of 3")
     if miss9 or miss1 or miss_rows:
         print("FAIL: not covered:", miss9, miss1, miss_rows)
         return 1
