@@ -195,6 +195,18 @@ class BagsAppearance(C.Structure):          # the images of one step and their r
                 ("out", c_fp * MAX_POSE_ROWS)]
 
 
+DEPTH_PRIOR_BLOCK, DEPTH_PRIOR_MIN_SLOTS, DEPTH_PRIOR_TILES_PER_SLOT, DEPTH_PRIOR_STATS = 256, 64, 4, 8      # include/bags_raster.h: BAGS_DEPTH_PRIOR_*
+DEPTH_PRIOR_PEARSON, DEPTH_PRIOR_L1 = 0, 1
+DEPTH_PRIOR_DEPTH, DEPTH_PRIOR_INVERSE = 0, 1
+
+
+class BagsDepthPrior(C.Structure):          # the depth / weights / prior / mask maps of one step's views (csrc/depth_prior.hip); None = NULL
+    _fields_ = [("mode", C.c_int32), ("space", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("min_weight", C.c_float),
+                ("n_rows", C.c_int32), ("N", C.c_int32), ("reserved", C.c_int32), ("table", c_fp), ("rows", C.c_int32 * MAX_POSE_ROWS),
+                ("depth", c_fp * MAX_POSE_ROWS), ("weights", c_fp * MAX_POSE_ROWS), ("prior", c_fp * MAX_POSE_ROWS),
+                ("mask", c_fp * MAX_POSE_ROWS)]
+
+
 SYMBOLS = {    "bags_abi_version": (C.c_int, []),
     "bags_build_info": (C.c_char_p, []),
     "bags_last_error": (C.c_char_p, []),
@@ -277,6 +289,9 @@ SYMBOLS = {    "bags_abi_version": (C.c_int, []),
     "bags_appearance_forward": (C.c_int, [C.POINTER(BagsAppearance), C.c_void_p]),
     "bags_appearance_workspace_size": (C.c_size_t, [C.c_int32] * 3),
     "bags_appearance_backward": (C.c_int, [C.POINTER(BagsAppearance), C.POINTER(c_fp), C.c_void_p, C.c_size_t, C.POINTER(c_fp), c_fp, C.c_void_p]),
+    "bags_depth_prior_workspace_size": (C.c_size_t, [C.c_int32] * 3),
+    "bags_depth_prior_forward": (C.c_int, [C.POINTER(BagsDepthPrior), C.c_void_p, C.c_size_t, c_fp, c_fp, c_fp, C.c_void_p]),
+    "bags_depth_prior_backward": (C.c_int, [C.POINTER(BagsDepthPrior), c_fp, c_fp, C.POINTER(c_fp), C.POINTER(c_fp), c_fp, C.c_void_p]),
     "bags_filter3d_workspace_size": (C.c_size_t, [C.c_int32]),
     "bags_filter3d_compute": (C.c_int, [c_fp, C.c_int32, c_fp, c_fp, c_fp, C.c_int32, C.c_float, C.c_void_p, C.c_size_t, c_fp, C.c_void_p]),
     "bags_activations_filtered_forward": (C.c_int, [C.POINTER(BagsRawGaussians), c_fp] + [C.c_void_p] * 5),

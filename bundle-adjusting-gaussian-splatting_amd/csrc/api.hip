@@ -1422,4 +1422,74 @@ int bags_filter3d_compute(const float* xyz, int32_t P, const float* viewmatrices
     return BAGS_OK;
 }
 
+// ---- depth_prior.hip: one row of 8 doubles per workgroup of the sums kernel, view-major
+static size_t carve_depth_prior(void* base, int n_rows, int H, int W, double** partials)
+{
+    Carver c(base, false);                       // the base as given: a misaligned one is refused, not rounded
+    double* p = c.take<double>((size_t)n_rows * depth_prior_slots(H, W) * BAGS_DEPTH_PRIOR_STATS);
+    if (partials) *partials = p;
+    return c.used();
+}
+
+static bool depth_prior_image_ok(int H, int W) { return H >= 1 && W >= 1 && (long long)H * W < (1ll << 31); }
+
+size_t bags_depth_prior_workspace_size(int32_t n_rows, int32_t H, int32_t W)
+{
+    if (n_rows < 1 || n_rows > BAGS_MAX_POSE_ROWS || !depth_prior_image_ok(H, W)) return 0;
+    return carve_depth_prior(nullptr, n_rows, H, W, nullptr);
+}
+
+static int check_depth_prior(const char* op, const BagsDepthPrior* a)
+{
+    if (!a) return fail(BAGS_ERR_ARG, "%s: null struct", op);
+    if (a->mode != BAGS_DEPTH_PRIOR_PEARSON && a->mode != BAGS_DEPTH_PRIOR_L1) return fail(BAGS_ERR_ARG, "%s: unknown mode %d", op, a->mode);
+    if (a->space != BAGS_DEPTH_PRIOR_DEPTH && a->space != BAGS_DEPTH_PRIOR_INVERSE) return fail(BAGS_ERR_ARG, "%s: unknown space %d", op, a->space);
+    if (a->table) {
+        if (a->mode == BAGS_DEPTH_PRIOR_PEARSON) return fail(BAGS_ERR_ARG, "%s: a table with the pearson mode (it has no parameters)", op);
+        if (const int rc = check_pose_rows(op, a->N, a->n_rows, a->rows)) return rc;
+    } else if (a->n_rows < 1 || a->n_rows > BAGS_MAX_POSE_ROWS)
+        return fail(BAGS_ERR_ARG, "%s: n_rows %d not in 1..%d", op, a->n_rows, BAGS_MAX_POSE_ROWS);
+    if (a->H < 1 || a->W < 1) return fail(BAGS_ERR_ARG, "%s: empty image %dx%d", op, a->W, a->H);
+    if (!depth_prior_image_ok(a->H, a->W)) return fail(BAGS_ERR_ARG, "%s: image %dx%d has 2^31 pixels or more", op, a->W, a->H);
+    if (!(a->min_weight == a->min_weight)) return fail(BAGS_ERR_ARG, "%s: min_weight is NaN", op);
+    for (int v = 0; v < a->n_rows; ++v) {
+        if (!a->depth[v]) return fail(BAGS_ERR_ARG, "%s: null depth[%d]", op, v);
+        if (!a->weights[v]) return fail(BAGS_ERR_ARG, "%s: null weights[%d]", op, v);
+        if (!a->prior[v]) return fail(BAGS_ERR_ARG, "%s: null prior[%d]", op, v);
+    }
+    return BAGS_OK;
+}
+
+int bags_depth_prior_forward(const BagsDepthPrior* a, void* workspace, size_t workspace_bytes, float* loss, float* count, double* stats,
+                             void* stream)
+{
+    if (const int rc = check_depth_prior("depth_prior_forward", a)) return rc;
+    if (!loss || !count || !stats) return fail(BAGS_ERR_ARG, "depth_prior_forward: null loss / count / stats");
+    const size_t need = bags_depth_prior_workspace_size(a->n_rows, a->H, a->W);
+    if (!workspace || workspace_bytes < need)
+        return fail(BAGS_ERR_ARG, "depth_prior_forward: needs a workspace of %zu bytes (got %zu)", need, workspace ? workspace_bytes : (size_t)0);
+    if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return fail(BAGS_ERR_ARG, "depth_prior_forward: the workspace is not 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(stats) % 8 != 0) return fail(BAGS_ERR_ARG, "depth_prior_forward: stats is not 8-byte aligned");
+    double* partials = nullptr;
+    carve_depth_prior(workspace, a->n_rows, a->H, a->W, &partials);
+    HIP_TRY(launch_depth_prior_fwd(*a, partials, loss, count, stats, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
+int bags_depth_prior_backward(const BagsDepthPrior* a, const double* stats, const float* g_loss, float* const g_depth[BAGS_MAX_POSE_ROWS],
+                              float* const g_weights[BAGS_MAX_POSE_ROWS], float* g_table, void* stream)
+{
+    if (const int rc = check_depth_prior("depth_prior_backward", a)) return rc;
+    if (!stats) return fail(BAGS_ERR_ARG, "depth_prior_backward: null stats");
+    if (reinterpret_cast<uintptr_t>(stats) % 8 != 0) return fail(BAGS_ERR_ARG, "depth_prior_backward: stats is not 8-byte aligned");
+    if (!g_loss) return fail(BAGS_ERR_ARG, "depth_prior_backward: null g_loss");
+    if (g_table && !a->table) return fail(BAGS_ERR_ARG, "depth_prior_backward: g_table is asked for but no table was given");
+    if (g_table && g_table == a->table) return fail(BAGS_ERR_ARG, "depth_prior_backward: g_table must not be the table");
+    bool any_map = false;
+    for (int v = 0; v < a->n_rows; ++v) any_map |= (g_depth && g_depth[v]) || (g_weights && g_weights[v]);
+    if (!any_map && !g_table) return BAGS_OK;
+    HIP_TRY(launch_depth_prior_bwd(*a, stats, g_loss, g_depth, g_weights, g_table, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
 }  // extern "C"

@@ -344,6 +344,12 @@ hipError_t launch_antialias_bwd(const BagsAntialias& a, const float* grad_out, f
 // appearance.hip: per-camera vignetting and exposure on the V images of a step, and the adjoint; partials: n_rows *
 // appearance_slots(H, W) rows of 16 doubles, or nullptr when g_table is not wanted (carve_appearance in api.hip)
 int appearance_slots(int H, int W);
+// depth_prior.hip: the Pearson / L1 depth prior on the V views of a step; partials: n_rows * depth_prior_slots(H, W) rows of 8
+// doubles (carve_depth_prior in api.hip); stats (n_rows,8) goes from the forward to the backward
+int depth_prior_slots(int H, int W);
+hipError_t launch_depth_prior_fwd(const BagsDepthPrior& a, double* partials, float* loss, float* count, double* stats, hipStream_t st);
+hipError_t launch_depth_prior_bwd(const BagsDepthPrior& a, const double* stats, const float* g_loss, float* const* g_depth,
+                                  float* const* g_weights, float* g_table, hipStream_t st);
 hipError_t launch_appearance_fwd(const BagsAppearance& a, hipStream_t st);
 hipError_t launch_appearance_bwd(const BagsAppearance& a, const float* const* g_out, double* partials, float* const* g_image, float* g_table,
                                  hipStream_t st);

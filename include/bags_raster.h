@@ -785,6 +785,60 @@ int bags_activations_filtered_backward(const BagsRawGaussians* raw, const float*
                                        const float* g_scales, const float* g_rotations, float* g_features_dc, float* g_features_rest,
                                        float* g_opacity_raw, float* g_scaling, float* g_rotation, void* stream);
 
+/* Depth priors on the rasterizer's maps (csrc/depth_prior.hip): depth D = sum w_i z_i and weights A = 1 - T_final of a view, a prior
+ * p and an optional pixel weight m >= 0 (NULL: 1), all (H,W) float32.  A pixel is valid iff m > 0, A >= min_weight, D > 0 and
+ * p > 0 (a NaN prior fails the last test); elsewhere nothing is summed and the gradients are exact zeros.  On valid pixels
+ *     x = D / A (BAGS_DEPTH_PRIOR_DEPTH)  or  x = A / D (BAGS_DEPTH_PRIOR_INVERSE: the prior is an inverse depth), one float32
+ *     division; w = m; n = sum w; everything after x is evaluated in double.
+ *     BAGS_DEPTH_PRIOR_L1:       r = x - (a*p + b), L = sum w|r| / n, sign(0) = 0; (a, b) = row rows[v] of the (N,2) table (upstream's
+ *                                depth_params), or (1, 0) with table == NULL.  n <= 0: L = 0.
+ *     BAGS_DEPTH_PRIOR_PEARSON:  L = 1 - rho, rho = C / sqrt(Vx*Vp), Vx = sum w x^2 / n - (sum w x / n)^2, Vp likewise,
+ *                                C = sum w x p / n - (sum w x / n)(sum w p / n).  A view with n <= 0, Vx <= 1e-12 * sum w x^2 / n or
+ *                                Vp <= 1e-12 * sum w p^2 / n is degenerate: L = 0 and every gradient zero, never NaN.  table must be NULL.
+ * forward:  two launches for the n_rows <= BAGS_MAX_POSE_ROWS views of a step (pointers by value, nothing stacked): a pixels kernel
+ *           leaves one row of 8 doubles per workgroup in the workspace, a finalize kernel adds a view's rows in a fixed order and
+ *           writes loss[v], count[v] = n and row v of stats (n_rows,8) float64:
+ *               xbar, pbar, 1/sqrt(Vx*Vp), rho/Vx, 1/n, sum w sign(r) p, sum w sign(r), degenerate flag (1.0 or 0.0).
+ *           No atomics, no memset, no host synchronisation.  A view has min(tiles, max(64, ceil(tiles / 4))) workgroups whatever
+ *           n_rows is, so its results have the bits of a call of its own.
+ * backward: g_loss (n_rows) are the cotangents of loss.  g_depth / g_weights (NULL, or n_rows pointers of which any may be NULL)
+ *           receive dL/dD and dL/dA of every pixel, each rounded once from double, in one launch; g_table (N,2) or NULL (L1 with a
+ *           table only) is written in EVERY element by one small launch from the stats row alone: listed rows
+ *           g_v * (-sum w sign(r) p / n, -sum w sign(r) / n), every other row exact zeros.  stats is the forward's, for the same
+ *           struct.  Each output has the same bits whichever other is wanted.
+ * A thread takes four consecutive pixels of a row: one 16-byte access per map where W % 4 == 0 and every pointer of the call is
+ * 16-byte aligned, element by element otherwise, with the same bits either way.
+ * workspace: bags_depth_prior_workspace_size bytes (0 for invalid arguments), 16-byte aligned, no initialisation (forward only).
+ * H * W must be below 2^31. */
+#define BAGS_DEPTH_PRIOR_BLOCK 256           /* threads per workgroup; a workgroup's tile is 256 quads = up to 1024 pixels */
+#define BAGS_DEPTH_PRIOR_MIN_SLOTS 64        /* a view's sums kernel has min(tiles, max(64, ceil(tiles / 4))) workgroups */
+#define BAGS_DEPTH_PRIOR_TILES_PER_SLOT 4
+#define BAGS_DEPTH_PRIOR_STATS 8             /* doubles per stats row (and per partial row of the workspace) */
+#define BAGS_DEPTH_PRIOR_PEARSON 0           /* mode */
+#define BAGS_DEPTH_PRIOR_L1 1
+#define BAGS_DEPTH_PRIOR_DEPTH 0             /* space */
+#define BAGS_DEPTH_PRIOR_INVERSE 1
+typedef struct BagsDepthPrior {
+    int32_t mode, space;
+    int32_t H, W;
+    float min_weight;
+    int32_t n_rows;                          /* views of the call, 1..BAGS_MAX_POSE_ROWS */
+    int32_t N;                               /* rows of the table (>= 1) when table is given, else ignored */
+    int32_t reserved;
+    const float* table;                      /* (N,2) rows (a, b), BAGS_DEPTH_PRIOR_L1 only; NULL: (1, 0) for every view */
+    int32_t rows[BAGS_MAX_POSE_ROWS];        /* with a table: distinct, each in [0, N) */
+    const float* depth[BAGS_MAX_POSE_ROWS];  /* (H,W) each, the first n_rows given */
+    const float* weights[BAGS_MAX_POSE_ROWS];
+    const float* prior[BAGS_MAX_POSE_ROWS];
+    const float* mask[BAGS_MAX_POSE_ROWS];   /* any of them NULL: every pixel weighs 1 */
+} BagsDepthPrior;
+size_t bags_depth_prior_workspace_size(int32_t n_rows, int32_t H, int32_t W);
+int    bags_depth_prior_forward(const BagsDepthPrior* args, void* workspace, size_t workspace_bytes, float* loss /* (n_rows) */,
+                                float* count /* (n_rows) */, double* stats /* (n_rows,8) */, void* stream);
+int    bags_depth_prior_backward(const BagsDepthPrior* args, const double* stats, const float* g_loss /* (n_rows) */,
+                                 float* const g_depth[BAGS_MAX_POSE_ROWS], float* const g_weights[BAGS_MAX_POSE_ROWS],
+                                 float* g_table /* (N,2) */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
