@@ -12,6 +12,7 @@ from .antialias import antialias_opacity, antialias_opacity_torch
 from .filter3d import filter_3D, filter_3D_torch, filtered_activations_torch
 from .appearance import AppearanceBank, apply_appearance, appearance_torch
 from .depth_prior import DepthPriorBank, depth_prior_loss, depth_prior_loss_torch
+from .normal_prior import normal_prior_loss, normal_prior_loss_torch, depth_to_normal, depth_to_normal_torch, pinhole_of
 from .io import save_ply, load_ply, save_checkpoint, load_checkpoint, save_exposure_json, load_exposure_json
 from .optim import GaussianAdam
 from .pose_bank import PoseBank, PoseAdam
@@ -26,4 +27,5 @@ __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gau
            "resample_faces", "resample_faces_torch", "cube_face_matrices",
            "AppearanceBank", "apply_appearance", "appearance_torch", "save_exposure_json", "load_exposure_json",
            "filter_3D", "filter_3D_torch", "filtered_activations_torch",
-           "DepthPriorBank", "depth_prior_loss", "depth_prior_loss_torch"]
+           "DepthPriorBank", "depth_prior_loss", "depth_prior_loss_torch",
+           "normal_prior_loss", "normal_prior_loss_torch", "depth_to_normal", "depth_to_normal_torch", "pinhole_of"]

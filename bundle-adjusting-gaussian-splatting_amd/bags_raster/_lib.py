@@ -207,6 +207,17 @@ class BagsDepthPrior(C.Structure):          # the depth / weights / prior / mask
                 ("mask", c_fp * MAX_POSE_ROWS)]
 
 
+NORMAL_PRIOR_TILE_W, NORMAL_PRIOR_TILE_H, NORMAL_PRIOR_STATS = 32, 8, 2      # include/bags_raster.h: BAGS_NORMAL_PRIOR_*
+NORMAL_PRIOR_COS, NORMAL_PRIOR_L1 = 0, 1
+
+
+class BagsNormalPrior(C.Structure):         # the maps, pinholes and prior normals of one step's views (csrc/normal_prior.hip); None = NULL
+    _fields_ = [("mode", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("min_weight", C.c_float), ("max_jump", C.c_float),
+                ("n_rows", C.c_int32), ("pinhole", (C.c_double * 4) * MAX_POSE_ROWS),
+                ("depth", c_fp * MAX_POSE_ROWS), ("weights", c_fp * MAX_POSE_ROWS), ("prior", c_fp * MAX_POSE_ROWS),
+                ("mask", c_fp * MAX_POSE_ROWS)]
+
+
 SYMBOLS = {    "bags_abi_version": (C.c_int, []),
     "bags_build_info": (C.c_char_p, []),
     "bags_last_error": (C.c_char_p, []),
@@ -292,6 +303,10 @@ SYMBOLS = {    "bags_abi_version": (C.c_int, []),
     "bags_depth_prior_workspace_size": (C.c_size_t, [C.c_int32] * 3),
     "bags_depth_prior_forward": (C.c_int, [C.POINTER(BagsDepthPrior), C.c_void_p, C.c_size_t, c_fp, c_fp, c_fp, C.c_void_p]),
     "bags_depth_prior_backward": (C.c_int, [C.POINTER(BagsDepthPrior), c_fp, c_fp, C.POINTER(c_fp), C.POINTER(c_fp), c_fp, C.c_void_p]),
+    "bags_normal_prior_workspace_size": (C.c_size_t, [C.c_int32] * 3),
+    "bags_normal_prior_forward": (C.c_int, [C.POINTER(BagsNormalPrior), C.c_void_p, C.c_size_t, c_fp, c_fp, c_fp, C.c_void_p]),
+    "bags_normal_prior_backward": (C.c_int, [C.POINTER(BagsNormalPrior), c_fp, c_fp, C.POINTER(c_fp), C.POINTER(c_fp), C.c_void_p]),
+    "bags_depth_to_normal": (C.c_int, [c_fp, c_fp, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_float, C.c_float, c_fp, C.c_void_p, C.c_void_p]),
     "bags_filter3d_workspace_size": (C.c_size_t, [C.c_int32]),
     "bags_filter3d_compute": (C.c_int, [c_fp, C.c_int32, c_fp, c_fp, c_fp, C.c_int32, C.c_float, C.c_void_p, C.c_size_t, c_fp, C.c_void_p]),
     "bags_activations_filtered_forward": (C.c_int, [C.POINTER(BagsRawGaussians), c_fp] + [C.c_void_p] * 5),

@@ -1492,4 +1492,100 @@ int bags_depth_prior_backward(const BagsDepthPrior* a, const double* stats, cons
     return BAGS_OK;
 }
 
+// ---- normal_prior.hip: one row of 2 doubles per tile, view-major
+static size_t carve_normal_prior(void* base, int n_rows, int H, int W, double** partials)
+{
+    Carver c(base, false);                       // the base as given: a misaligned one is refused, not rounded
+    double* p = c.take<double>((size_t)n_rows * (size_t)normal_prior_tiles(H, W) * BAGS_NORMAL_PRIOR_STATS);
+    if (partials) *partials = p;
+    return c.used();
+}
+
+// the rows of tiles are grid dimension y
+static bool normal_prior_image_ok(int H, int W)
+{
+    return H >= 1 && W >= 1 && (long long)H * W < (1ll << 31) && (H + BAGS_NORMAL_PRIOR_TILE_H - 1) / BAGS_NORMAL_PRIOR_TILE_H <= 65535;
+}
+
+size_t bags_normal_prior_workspace_size(int32_t n_rows, int32_t H, int32_t W)
+{
+    if (n_rows < 1 || n_rows > BAGS_MAX_POSE_ROWS || !normal_prior_image_ok(H, W)) return 0;
+    return carve_normal_prior(nullptr, n_rows, H, W, nullptr);
+}
+
+static int check_normal_geometry(const char* op, int H, int W, float min_weight, float max_jump)
+{
+    if (H < 1 || W < 1) return fail(BAGS_ERR_ARG, "%s: empty image %dx%d", op, W, H);
+    if ((long long)H * W >= (1ll << 31)) return fail(BAGS_ERR_ARG, "%s: image %dx%d has 2^31 pixels or more", op, W, H);
+    if (!normal_prior_image_ok(H, W)) return fail(BAGS_ERR_ARG, "%s: image %dx%d has more than %d rows", op, W, H, 65535 * BAGS_NORMAL_PRIOR_TILE_H);
+    if (!(min_weight > 0.0f) || std::isinf(min_weight)) return fail(BAGS_ERR_ARG, "%s: min_weight must be a positive number", op);
+    if (!(max_jump >= 0.0f)) return fail(BAGS_ERR_ARG, "%s: max_jump must be a non-negative number or inf", op);
+    return BAGS_OK;
+}
+
+static int check_pinhole(const char* op, int v, const double* p)
+{
+    for (int j = 0; j < 4; ++j)
+        if (!std::isfinite(p[j])) return fail(BAGS_ERR_ARG, "%s: pinhole[%d] is not finite", op, v);
+    if (p[0] == 0.0 || p[1] == 0.0) return fail(BAGS_ERR_ARG, "%s: pinhole[%d] has a zero focal length", op, v);
+    return BAGS_OK;
+}
+
+static int check_normal_prior(const char* op, const BagsNormalPrior* a)
+{
+    if (!a) return fail(BAGS_ERR_ARG, "%s: null struct", op);
+    if (a->mode != BAGS_NORMAL_PRIOR_COS && a->mode != BAGS_NORMAL_PRIOR_L1) return fail(BAGS_ERR_ARG, "%s: unknown mode %d", op, a->mode);
+    if (a->n_rows < 1 || a->n_rows > BAGS_MAX_POSE_ROWS) return fail(BAGS_ERR_ARG, "%s: n_rows %d not in 1..%d", op, a->n_rows, BAGS_MAX_POSE_ROWS);
+    if (const int rc = check_normal_geometry(op, a->H, a->W, a->min_weight, a->max_jump)) return rc;
+    for (int v = 0; v < a->n_rows; ++v) {
+        if (const int rc = check_pinhole(op, v, a->pinhole[v])) return rc;
+        if (!a->depth[v]) return fail(BAGS_ERR_ARG, "%s: null depth[%d]", op, v);
+        if (!a->weights[v]) return fail(BAGS_ERR_ARG, "%s: null weights[%d]", op, v);
+        if (!a->prior[v]) return fail(BAGS_ERR_ARG, "%s: null prior[%d]", op, v);
+    }
+    return BAGS_OK;
+}
+
+int bags_normal_prior_forward(const BagsNormalPrior* a, void* workspace, size_t workspace_bytes, float* loss, float* count, double* stats,
+                              void* stream)
+{
+    if (const int rc = check_normal_prior("normal_prior_forward", a)) return rc;
+    if (!loss || !count || !stats) return fail(BAGS_ERR_ARG, "normal_prior_forward: null loss / count / stats");
+    const size_t need = bags_normal_prior_workspace_size(a->n_rows, a->H, a->W);
+    if (!workspace || workspace_bytes < need)
+        return fail(BAGS_ERR_ARG, "normal_prior_forward: needs a workspace of %zu bytes (got %zu)", need, workspace ? workspace_bytes : (size_t)0);
+    if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return fail(BAGS_ERR_ARG, "normal_prior_forward: the workspace is not 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(stats) % 8 != 0) return fail(BAGS_ERR_ARG, "normal_prior_forward: stats is not 8-byte aligned");
+    double* partials = nullptr;
+    carve_normal_prior(workspace, a->n_rows, a->H, a->W, &partials);
+    HIP_TRY(launch_normal_prior_fwd(*a, partials, loss, count, stats, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
+int bags_normal_prior_backward(const BagsNormalPrior* a, const double* stats, const float* g_loss, float* const g_depth[BAGS_MAX_POSE_ROWS],
+                               float* const g_weights[BAGS_MAX_POSE_ROWS], void* stream)
+{
+    if (const int rc = check_normal_prior("normal_prior_backward", a)) return rc;
+    if (!stats) return fail(BAGS_ERR_ARG, "normal_prior_backward: null stats");
+    if (reinterpret_cast<uintptr_t>(stats) % 8 != 0) return fail(BAGS_ERR_ARG, "normal_prior_backward: stats is not 8-byte aligned");
+    if (!g_loss) return fail(BAGS_ERR_ARG, "normal_prior_backward: null g_loss");
+    bool any_map = false;
+    for (int v = 0; v < a->n_rows; ++v) any_map |= (g_depth && g_depth[v]) || (g_weights && g_weights[v]);
+    if (!any_map) return BAGS_OK;
+    HIP_TRY(launch_normal_prior_bwd(*a, stats, g_loss, g_depth, g_weights, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
+int bags_depth_to_normal(const float* depth, const float* weights, int32_t H, int32_t W, const double pinhole[4], float min_weight,
+                         float max_jump, float* normal, uint8_t* valid, void* stream)
+{
+    if (const int rc = check_normal_geometry("depth_to_normal", H, W, min_weight, max_jump)) return rc;
+    if (!pinhole) return fail(BAGS_ERR_ARG, "depth_to_normal: null pinhole");
+    if (const int rc = check_pinhole("depth_to_normal", 0, pinhole)) return rc;
+    if (!depth || !weights) return fail(BAGS_ERR_ARG, "depth_to_normal: null depth / weights");
+    if (!normal || !valid) return fail(BAGS_ERR_ARG, "depth_to_normal: null normal / valid");
+    HIP_TRY(launch_depth_to_normal(depth, weights, H, W, pinhole, min_weight, max_jump, normal, valid, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
 }  // extern "C"

@@ -350,6 +350,14 @@ int depth_prior_slots(int H, int W);
 hipError_t launch_depth_prior_fwd(const BagsDepthPrior& a, double* partials, float* loss, float* count, double* stats, hipStream_t st);
 hipError_t launch_depth_prior_bwd(const BagsDepthPrior& a, const double* stats, const float* g_loss, float* const* g_depth,
                                   float* const* g_weights, float* g_table, hipStream_t st);
+// normal_prior.hip: the normals of the rendered depth held to a prior, on the V views of a step; partials: n_rows *
+// normal_prior_tiles(H, W) rows of 2 doubles (carve_normal_prior in api.hip); stats (n_rows,2) goes from the forward to the backward
+long long normal_prior_tiles(int H, int W);
+hipError_t launch_normal_prior_fwd(const BagsNormalPrior& a, double* partials, float* loss, float* count, double* stats, hipStream_t st);
+hipError_t launch_normal_prior_bwd(const BagsNormalPrior& a, const double* stats, const float* g_loss, float* const* g_depth,
+                                   float* const* g_weights, hipStream_t st);
+hipError_t launch_depth_to_normal(const float* depth, const float* weights, int H, int W, const double* pinhole, float min_weight, float max_jump,
+                                  float* normal, uint8_t* valid, hipStream_t st);
 hipError_t launch_appearance_fwd(const BagsAppearance& a, hipStream_t st);
 hipError_t launch_appearance_bwd(const BagsAppearance& a, const float* const* g_out, double* partials, float* const* g_image, float* g_table,
                                  hipStream_t st);

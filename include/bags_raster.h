@@ -839,6 +839,65 @@ int    bags_depth_prior_backward(const BagsDepthPrior* args, const double* stats
                                  float* const g_depth[BAGS_MAX_POSE_ROWS], float* const g_weights[BAGS_MAX_POSE_ROWS],
                                  float* g_table /* (N,2) */, void* stream);
 
+/* A normal prior on the rasterizer's maps (csrc/normal_prior.hip): the normals of the rendered depth by central differences, held
+ * to a prior normal map.  Per view: maps D, A (H,W) float32, a pinhole (fx, fy, cx, cy) in pixels, prior normals p (3,H,W) in the
+ * camera frame of the operator's view space (x right, y down, z forward), an optional pixel weight m >= 0 (H,W) (NULL: 1).
+ *     solid(u,v)  = A >= min_weight  and  D > 0
+ *     z           = D / A                      one division in the dtype of the maps; everything after it in float64
+ *     P(u,v)      = z * ((u - cx)/fx, (v - cy)/fy, 1)
+ *     dx = P(u+1,v) - P(u-1,v) ;  dy = P(u,v+1) - P(u,v-1)          (central differences, as 2DGS's depth_to_normal)
+ *     N  = dy x dx ;  q = |N|^2 ;  n = N / sqrt(q)                   (faces the camera: n_z < 0 for a fronto-parallel wall)
+ *     geometric(u,v) = the pixel and its four neighbours are inside the image and solid,
+ *                      |z(u+1,v) - z(u-1,v)| <= max_jump * z(u,v)  and  |z(u,v+1) - z(u,v-1)| <= max_jump * z(u,v),
+ *                      q is a positive finite number
+ *     valid(u,v)  = geometric  and  m > 0  and  |p|^2 is finite and > 0.25      (a zero or NaN prior: "no prior here")
+ *     ph = p / |p| ;  w = m on valid pixels ;  cnt = sum w
+ *     mode="cos":  l = 1 - n . ph          mode="l1":  l = |n - ph|_1   (sign(0) = 0)
+ *     L_v = sum w l / cnt                  cnt <= 0 (also every image with H < 3 or W < 3): L_v = 0, all gradients zero, never NaN
+ * max_jump = inf switches the guard off.  Validity and the guard are decisions, not differentiated through; invalid pixels get
+ * exact-zero gradients.  The pinhole is constant data (host doubles, by value): no gradient to it.  Backward, with
+ * s = cot_v * w_c / cnt_v, g = dl/dn (-ph for cos, sign(n - ph) for l1) and G = s * (g - n (n . g)) / sqrt(q):
+ *     dL/ddy = dx x G ;   dL/ddx = G x dy
+ *     dL/dP(u+1,v) += dL/ddx ;  dL/dP(u-1,v) -= dL/ddx ;  dL/dP(u,v+1) += dL/ddy ;  dL/dP(u,v-1) -= dL/ddy
+ *     dL/dz = ray . dL/dP ,  ray = ((u-cx)/fx, (v-cy)/fy, 1) ;   dL/dD = dL/dz / A ;   dL/dA = -(z / A) dL/dz
+ * The centre pixel's own z enters only the guard.
+ * forward:  two launches for the n_rows <= BAGS_MAX_POSE_ROWS views of a step (pointers and pinholes by value).  A workgroup takes
+ *           a tile of BAGS_NORMAL_PRIOR_TILE_W x BAGS_NORMAL_PRIOR_TILE_H pixels, stages z and solid of the tile and a one-pixel
+ *           halo in LDS and leaves one row (sum w l, sum w) of doubles in the workspace; a finalize kernel adds a view's rows in a
+ *           fixed order and writes loss[v], count[v] = cnt and row v of stats (n_rows,2) float64: 1/cnt (0 where cnt <= 0), cnt.
+ * backward: one launch.  g_loss (n_rows) are the cotangents of loss; g_depth / g_weights (NULL, or n_rows pointers of which any
+ *           may be NULL) receive dL/dD and dL/dA of EVERY pixel, each rounded once from double; a pixel gathers from its four
+ *           neighbouring centres in the fixed order left, right, upper, lower.  stats is the forward's, for the same struct.
+ * No atomics, no memset, no host synchronisation; a view's loss, count and gradients have the bits of a call of its own.
+ * bags_depth_to_normal: one launch, one view: normal (3,H,W) float32 = n and valid (H,W) uint8 by the geometric rule alone (no
+ *           prior, no mask), zeros where not valid.
+ * workspace: bags_normal_prior_workspace_size bytes (0 for invalid arguments), 16-byte aligned, no initialisation (forward only).
+ * min_weight must be a positive number, max_jump a non-negative number or inf.  H * W must be below 2^31. */
+#define BAGS_NORMAL_PRIOR_TILE_W 32          /* a workgroup of 256 threads takes a tile of 32 x 8 pixels */
+#define BAGS_NORMAL_PRIOR_TILE_H 8
+#define BAGS_NORMAL_PRIOR_STATS 2            /* doubles per stats row (and per partial row of the workspace) */
+#define BAGS_NORMAL_PRIOR_COS 0              /* mode */
+#define BAGS_NORMAL_PRIOR_L1 1
+typedef struct BagsNormalPrior {
+    int32_t mode;
+    int32_t H, W;
+    float min_weight;
+    float max_jump;
+    int32_t n_rows;                          /* views of the call, 1..BAGS_MAX_POSE_ROWS */
+    double pinhole[BAGS_MAX_POSE_ROWS][4];   /* (fx, fy, cx, cy) in pixels per view; fx, fy non-zero and finite */
+    const float* depth[BAGS_MAX_POSE_ROWS];  /* (H,W) each, the first n_rows given */
+    const float* weights[BAGS_MAX_POSE_ROWS];
+    const float* prior[BAGS_MAX_POSE_ROWS];  /* (3,H,W) each */
+    const float* mask[BAGS_MAX_POSE_ROWS];   /* any of them NULL: every pixel weighs 1 */
+} BagsNormalPrior;
+size_t bags_normal_prior_workspace_size(int32_t n_rows, int32_t H, int32_t W);
+int    bags_normal_prior_forward(const BagsNormalPrior* args, void* workspace, size_t workspace_bytes, float* loss /* (n_rows) */,
+                                 float* count /* (n_rows) */, double* stats /* (n_rows,2) */, void* stream);
+int    bags_normal_prior_backward(const BagsNormalPrior* args, const double* stats, const float* g_loss /* (n_rows) */,
+                                  float* const g_depth[BAGS_MAX_POSE_ROWS], float* const g_weights[BAGS_MAX_POSE_ROWS], void* stream);
+int    bags_depth_to_normal(const float* depth, const float* weights, int32_t H, int32_t W, const double pinhole[4], float min_weight,
+                            float max_jump, float* normal /* (3,H,W) */, uint8_t* valid /* (H,W) */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
