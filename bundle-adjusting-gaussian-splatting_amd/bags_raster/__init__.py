@@ -11,6 +11,7 @@ from .mcmc import compute_relocation, compute_relocation_torch, relocation_binom
 from .antialias import antialias_opacity, antialias_opacity_torch
 from .filter3d import filter_3D, filter_3D_torch, filtered_activations_torch
 from .appearance import AppearanceBank, apply_appearance, appearance_torch
+from .bilagrid import BilateralGridBank, apply_bilagrid, bilagrid_torch, bilagrid_tv_loss, bilagrid_tv_loss_torch
 from .depth_prior import DepthPriorBank, depth_prior_loss, depth_prior_loss_torch
 from .normal_prior import normal_prior_loss, normal_prior_loss_torch, depth_to_normal, depth_to_normal_torch, pinhole_of
 from .io import save_ply, load_ply, save_checkpoint, load_checkpoint, save_exposure_json, load_exposure_json
@@ -26,6 +27,7 @@ __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gau
            "PoseBank", "PoseAdam", "LensField", "lens_field", "lens_field_torch",
            "resample_faces", "resample_faces_torch", "cube_face_matrices",
            "AppearanceBank", "apply_appearance", "appearance_torch", "save_exposure_json", "load_exposure_json",
+           "BilateralGridBank", "apply_bilagrid", "bilagrid_torch", "bilagrid_tv_loss", "bilagrid_tv_loss_torch",
            "filter_3D", "filter_3D_torch", "filtered_activations_torch",
            "DepthPriorBank", "depth_prior_loss", "depth_prior_loss_torch",
            "normal_prior_loss", "normal_prior_loss_torch", "depth_to_normal", "depth_to_normal_torch", "pinhole_of"]

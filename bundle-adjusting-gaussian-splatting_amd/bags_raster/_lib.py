@@ -195,6 +195,17 @@ class BagsAppearance(C.Structure):          # the images of one step and their r
                 ("out", c_fp * MAX_POSE_ROWS)]
 
 
+BILAGRID_TILE_W, BILAGRID_TILE_H, BILAGRID_STAGE_VERTS, BILAGRID_MAX_G, BILAGRID_MAX_L = 64, 4, 9, 64, 16      # include/bags_raster.h: BAGS_BILAGRID_*
+BILAGRID_TV_BLOCK, BILAGRID_TV_MAX_BLOCKS = 256, 1024
+BILAGRID_PATH_AUTO, BILAGRID_PATH_DIRECT = 0, 1
+
+
+class BagsBilagrid(C.Structure):            # the images of one step and their rows of the (N,12,L,Gy,Gx) bilateral grids (csrc/bilagrid.hip)
+    _fields_ = [("N", C.c_int32), ("grids", c_fp), ("n_rows", C.c_int32), ("rows", C.c_int32 * MAX_POSE_ROWS), ("C", C.c_int32),
+                ("H", C.c_int32), ("W", C.c_int32), ("Gx", C.c_int32), ("Gy", C.c_int32), ("L", C.c_int32), ("path", C.c_int32),
+                ("image", c_fp * MAX_POSE_ROWS), ("out", c_fp * MAX_POSE_ROWS)]
+
+
 DEPTH_PRIOR_BLOCK, DEPTH_PRIOR_MIN_SLOTS, DEPTH_PRIOR_TILES_PER_SLOT, DEPTH_PRIOR_STATS = 256, 64, 4, 8      # include/bags_raster.h: BAGS_DEPTH_PRIOR_*
 DEPTH_PRIOR_PEARSON, DEPTH_PRIOR_L1 = 0, 1
 DEPTH_PRIOR_DEPTH, DEPTH_PRIOR_INVERSE = 0, 1
@@ -300,6 +311,12 @@ SYMBOLS = {    "bags_abi_version": (C.c_int, []),
     "bags_appearance_forward": (C.c_int, [C.POINTER(BagsAppearance), C.c_void_p]),
     "bags_appearance_workspace_size": (C.c_size_t, [C.c_int32] * 3),
     "bags_appearance_backward": (C.c_int, [C.POINTER(BagsAppearance), C.POINTER(c_fp), C.c_void_p, C.c_size_t, C.POINTER(c_fp), c_fp, C.c_void_p]),
+    "bags_bilagrid_forward": (C.c_int, [C.POINTER(BagsBilagrid), C.c_void_p]),
+    "bags_bilagrid_workspace_size": (C.c_size_t, [C.c_int32] * 3),
+    "bags_bilagrid_backward": (C.c_int, [C.POINTER(BagsBilagrid), C.POINTER(c_fp), C.c_void_p, C.c_size_t, C.POINTER(c_fp), c_fp, C.c_void_p]),
+    "bags_bilagrid_tv_workspace_size": (C.c_size_t, [C.c_int32] * 4),
+    "bags_bilagrid_tv_forward": (C.c_int, [c_fp] + [C.c_int32] * 4 + [C.c_void_p, C.c_size_t, c_fp, C.c_void_p]),
+    "bags_bilagrid_tv_backward": (C.c_int, [c_fp] + [C.c_int32] * 4 + [c_fp, c_fp, C.c_void_p]),
     "bags_depth_prior_workspace_size": (C.c_size_t, [C.c_int32] * 3),
     "bags_depth_prior_forward": (C.c_int, [C.POINTER(BagsDepthPrior), C.c_void_p, C.c_size_t, c_fp, c_fp, c_fp, C.c_void_p]),
     "bags_depth_prior_backward": (C.c_int, [C.POINTER(BagsDepthPrior), c_fp, c_fp, C.POINTER(c_fp), C.POINTER(c_fp), c_fp, C.c_void_p]),

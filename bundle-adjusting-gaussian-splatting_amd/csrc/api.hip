@@ -1392,6 +1392,104 @@ int bags_appearance_backward(const BagsAppearance* a, const float* const g_out[B
     return BAGS_OK;
 }
 
+// ---- bilagrid.hip: the slice and its adjoint keep nothing between launches; the TV forward one row of 4 doubles per workgroup
+static bool bilagrid_grid_ok(int Gx, int Gy, int L)
+{
+    return Gx >= 1 && Gx <= BAGS_BILAGRID_MAX_G && Gy >= 1 && Gy <= BAGS_BILAGRID_MAX_G && L >= 1 && L <= BAGS_BILAGRID_MAX_L;
+}
+
+static int check_bilagrid_grid(const char* op, int Gx, int Gy, int L)
+{
+    if (bilagrid_grid_ok(Gx, Gy, L)) return BAGS_OK;
+    return fail(BAGS_ERR_ARG, "%s: grid (Gx, Gy, L) = (%d, %d, %d) is outside 1..%d, 1..%d, 1..%d (bilagrid_torch is the same function in PyTorch for any size)",
+                op, Gx, Gy, L, BAGS_BILAGRID_MAX_G, BAGS_BILAGRID_MAX_G, BAGS_BILAGRID_MAX_L);
+}
+
+static int check_bilagrid(const char* op, const BagsBilagrid* a)
+{
+    if (!a) return fail(BAGS_ERR_ARG, "%s: null struct", op);
+    if (!a->grids) return fail(BAGS_ERR_ARG, "%s: null grids", op);
+    if (const int rc = check_pose_rows(op, a->N, a->n_rows, a->rows)) return rc;
+    if (a->C != 3) return fail(BAGS_ERR_ARG, "%s: C must be 3 (got %d)", op, a->C);
+    if (a->H < 1 || a->W < 1) return fail(BAGS_ERR_ARG, "%s: empty image %dx%d", op, a->W, a->H);
+    if (!appearance_image_ok(a->H, a->W))
+        return fail(BAGS_ERR_ARG, "%s: image %dx%d has 2^31 pixels or more (bilagrid_torch is the same function in PyTorch for any size)", op, a->W, a->H);
+    if (const int rc = check_bilagrid_grid(op, a->Gx, a->Gy, a->L)) return rc;
+    if (a->path != BAGS_BILAGRID_PATH_AUTO && a->path != BAGS_BILAGRID_PATH_DIRECT) return fail(BAGS_ERR_ARG, "%s: path %d is not a BAGS_BILAGRID_PATH_*", op, a->path);
+    for (int v = 0; v < a->n_rows; ++v)
+        if (!a->image[v]) return fail(BAGS_ERR_ARG, "%s: null image[%d]", op, v);
+    return BAGS_OK;
+}
+
+int bags_bilagrid_forward(const BagsBilagrid* a, void* stream)
+{
+    if (const int rc = check_bilagrid("bilagrid_forward", a)) return rc;
+    for (int v = 0; v < a->n_rows; ++v)
+        if (!a->out[v]) return fail(BAGS_ERR_ARG, "bilagrid_forward: null out[%d]", v);
+    HIP_TRY(launch_bilagrid_fwd(*a, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
+size_t bags_bilagrid_workspace_size(int32_t, int32_t, int32_t) { return 0; }     // a vertex's sums are one workgroup's: nothing is kept
+
+int bags_bilagrid_backward(const BagsBilagrid* a, const float* const g_out[BAGS_MAX_POSE_ROWS], void* /*workspace*/, size_t /*workspace_bytes*/,
+                           float* const g_image[BAGS_MAX_POSE_ROWS], float* g_grids, void* stream)
+{
+    if (const int rc = check_bilagrid("bilagrid_backward", a)) return rc;
+    if (!g_out) return fail(BAGS_ERR_ARG, "bilagrid_backward: null g_out");
+    for (int v = 0; v < a->n_rows; ++v)
+        if (!g_out[v]) return fail(BAGS_ERR_ARG, "bilagrid_backward: null g_out[%d]", v);
+    if (g_grids == a->grids) return fail(BAGS_ERR_ARG, "bilagrid_backward: g_grids must not be the grids");
+    bool any_image = false;
+    for (int v = 0; g_image && v < a->n_rows; ++v) any_image |= g_image[v] != nullptr;
+    if (!any_image && !g_grids) return BAGS_OK;
+    HIP_TRY(launch_bilagrid_bwd(*a, g_out, any_image ? g_image : nullptr, g_grids, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
+static size_t carve_bilagrid_tv(void* base, int N, int Gx, int Gy, int L, double** partials)
+{
+    Carver c(base, false);                       // the base as given: a misaligned one is refused, not rounded
+    double* p = c.take<double>((size_t)bilagrid_tv_blocks((long long)N * 12 * L * Gy * Gx) * 4);
+    if (partials) *partials = p;
+    return c.used();
+}
+
+size_t bags_bilagrid_tv_workspace_size(int32_t N, int32_t Gx, int32_t Gy, int32_t L)
+{
+    if (N < 1 || !bilagrid_grid_ok(Gx, Gy, L)) return 0;
+    return carve_bilagrid_tv(nullptr, N, Gx, Gy, L, nullptr);
+}
+
+int bags_bilagrid_tv_forward(const float* grids, int32_t N, int32_t Gx, int32_t Gy, int32_t L, void* workspace, size_t workspace_bytes, float* loss,
+                             void* stream)
+{
+    if (N < 1) return fail(BAGS_ERR_ARG, "bilagrid_tv_forward: N %d < 1", N);
+    if (const int rc = check_bilagrid_grid("bilagrid_tv_forward", Gx, Gy, L)) return rc;
+    if (!grids) return fail(BAGS_ERR_ARG, "bilagrid_tv_forward: null grids");
+    if (!loss) return fail(BAGS_ERR_ARG, "bilagrid_tv_forward: null loss");
+    const size_t need = bags_bilagrid_tv_workspace_size(N, Gx, Gy, L);
+    if (!workspace || workspace_bytes < need)
+        return fail(BAGS_ERR_ARG, "bilagrid_tv_forward: needs a workspace of %zu bytes (got %zu)", need, workspace ? workspace_bytes : (size_t)0);
+    if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return fail(BAGS_ERR_ARG, "bilagrid_tv_forward: the workspace is not 16-byte aligned");
+    double* partials = nullptr;
+    carve_bilagrid_tv(workspace, N, Gx, Gy, L, &partials);
+    HIP_TRY(launch_bilagrid_tv_fwd(grids, N, Gx, Gy, L, partials, loss, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
+int bags_bilagrid_tv_backward(const float* grids, int32_t N, int32_t Gx, int32_t Gy, int32_t L, const float* g_loss, float* g_grids, void* stream)
+{
+    if (N < 1) return fail(BAGS_ERR_ARG, "bilagrid_tv_backward: N %d < 1", N);
+    if (const int rc = check_bilagrid_grid("bilagrid_tv_backward", Gx, Gy, L)) return rc;
+    if (!grids) return fail(BAGS_ERR_ARG, "bilagrid_tv_backward: null grids");
+    if (!g_loss) return fail(BAGS_ERR_ARG, "bilagrid_tv_backward: null g_loss");
+    if (!g_grids) return fail(BAGS_ERR_ARG, "bilagrid_tv_backward: null g_grids");
+    if (g_grids == grids) return fail(BAGS_ERR_ARG, "bilagrid_tv_backward: g_grids must not be the grids");
+    HIP_TRY(launch_bilagrid_tv_bwd(grids, N, Gx, Gy, L, g_loss, g_grids, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
 // ---- filter3d.hip: a dist per Gaussian and a maximum per workgroup between the two launches
 static size_t carve_filter3d(void* base, int P, float** dist, float** partials)
 {

@@ -361,6 +361,13 @@ hipError_t launch_depth_to_normal(const float* depth, const float* weights, int 
 hipError_t launch_appearance_fwd(const BagsAppearance& a, hipStream_t st);
 hipError_t launch_appearance_bwd(const BagsAppearance& a, const float* const* g_out, double* partials, float* const* g_image, float* g_table,
                                  hipStream_t st);
+// bilagrid.hip: the per-image bilateral grid on the V images of a step and its adjoint (no workspace: a vertex's sums are one
+// workgroup's), and the total variation of the grids; partials: bilagrid_tv_blocks(elems) rows of 4 doubles (carve_bilagrid_tv in api.hip)
+int bilagrid_tv_blocks(long long elems);
+hipError_t launch_bilagrid_fwd(const BagsBilagrid& a, hipStream_t st);
+hipError_t launch_bilagrid_bwd(const BagsBilagrid& a, const float* const* g_out, float* const* g_image, float* g_grids, hipStream_t st);
+hipError_t launch_bilagrid_tv_fwd(const float* grids, int N, int Gx, int Gy, int L, double* partials, float* loss, hipStream_t st);
+hipError_t launch_bilagrid_tv_bwd(const float* grids, int N, int Gx, int Gy, int L, const float* g_loss, float* g_grids, hipStream_t st);
 // lens_field.hip: the invertible-ResNet lens network on M points of R^2 (forward / fixed-point inverse in one launch, backward in two)
 __host__ __device__ static inline int lens_block_floats(int H, int n) { return 3 * H + n * (H * H + H) + 2 * H + 2; }   // of the flat vector, per block
 size_t lens_field_workspace_bytes(int B, int H, int n, long long M);

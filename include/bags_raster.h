@@ -898,6 +898,69 @@ int    bags_normal_prior_backward(const BagsNormalPrior* args, const double* sta
 int    bags_depth_to_normal(const float* depth, const float* weights, int32_t H, int32_t W, const double pinhole[4], float min_weight,
                             float max_jump, float* normal /* (3,H,W) */, uint8_t* valid /* (H,W) */, void* stream);
 
+/* Per-image bilateral-grid colour (csrc/bilagrid.hip): gsplat's lib_bilagrid slice-and-apply on the rendered image, behind the
+ * appearance step and in front of the loss, and the total variation of the grids.  The grids of all N training images are one
+ * (N,12,L,Gy,Gx) device tensor in gsplat's layout: coefficient k = 4*c + j of a vertex is entry [c][j] of a 3x4 affine matrix; the
+ * neutral grid is [I | 0] at every vertex.  For pixel (x, y) of a (3,H,W) image with channels p_0..p_2 and the grid G of its row:
+ *     u = (x + 0.5) / W * (Gx - 1) ;  x0 = min(floor(u), Gx-1) ;  x1 = min(x0+1, Gx-1) ;  tx = u - x0      (v, y0, y1, ty likewise)
+ *     luma = 0.299 p_0 + 0.587 p_1 + 0.114 p_2 ;  s = luma * (L-1) ;  w = clamp(s, 0, L-1)
+ *     z0 = min(floor(w), L-1) ;  z1 = min(z0+1, L-1) ;  tz = w - z0 ;  lerp(a, b, t) = a + t * (b - a)
+ *     plane(z) = lerp( lerp(G[k,z,y0,x0], G[k,z,y0,x1], tx), lerp(G[k,z,y1,x0], G[k,z,y1,x1], tx), ty )
+ *     A[k] = lerp(plane(z0), plane(z1), tz) ;  out_c = A[4c] p_0 + A[4c+1] p_1 + A[4c+2] p_2 + A[4c+3]
+ * in float32 in exactly this order (F.grid_sample, bilinear, align_corners, border padding, in its lerp form); the neutral grid
+ * returns a finite image bit for bit.  dL/dimage has the direct term sum_c g_c A[4c+j] and the term through the guidance,
+ * dtz * (L-1) * (0.299, 0.587, 0.114) with dtz = sum_k dL/dA[k] * (plane(z1)[k] - plane(z0)[k]), exactly zero where s <= 0 or
+ * s >= L-1; nothing flows to u or v.
+ * forward:  ONE launch for the n_rows <= BAGS_MAX_POSE_ROWS images of a step; image[v] goes through grid rows[v] into out[v].
+ *           Pointers and the row list travel by value.  A workgroup takes a tile of BAGS_BILAGRID_TILE_W x BAGS_BILAGRID_TILE_H
+ *           pixels; a tile that reaches at most BAGS_BILAGRID_STAGE_VERTS xy-vertices reads them from LDS, any other tile (an
+ *           image smaller than its grid) from the grid directly, with the same bits; path = BAGS_BILAGRID_PATH_DIRECT makes
+ *           every tile read directly.  out[v] must not overlap an input.
+ * backward: at most two launches.  g_image (NULL, or n_rows pointers of which any may be NULL) receives dL/dimage in one pass
+ *           over the pixels.  g_grids (N,12,L,Gy,Gx), or NULL, is written in EVERY element by one launch: a workgroup per
+ *           (xy-vertex, output channel, view) walks the vertex's support rectangle, adds in double in a fixed order and rounds
+ *           once; vertices no pixel reaches and rows that are not listed are exact zeros (no fill launch in front).  No atomics,
+ *           no host synchronisation; a repeated call gives the same bits, each output the same bits whichever other is wanted,
+ *           and a row of a many-view call the bits of a call of its own.  `out` of the struct is not read.
+ * workspace: this decomposition keeps no partial sums; the size query is there for callers written against the other entry points
+ *           of this header and reports 0 bytes, and the backward takes (NULL, 0).
+ * total variation (gsplat's total_variation_loss): per axis d with n_d >= 2 the sum of the squared forward differences along d over
+ *           12 * (n_d - 1) * the product of the other two sizes; the three terms added and divided by N; an axis of one vertex
+ *           counts 0.  Forward: two launches (per-workgroup partial sums in double, then the one scalar `loss`); the workgroup
+ *           count is decided by the element count alone.  Backward: one launch, a gather that writes every element of g_grids
+ *           from the cotangent g_loss (one float on the device).  Its workspace holds the partial rows, no initialisation.
+ * Supported: 1 <= Gx, Gy <= BAGS_BILAGRID_MAX_G, 1 <= L <= BAGS_BILAGRID_MAX_L, H * W below 2^31; anything else is an argument
+ * error whose text points to bilagrid_torch, the same function in PyTorch. */
+#define BAGS_BILAGRID_TILE_W 64              /* a workgroup of 256 threads takes a tile of 64 x 4 pixels, a thread a pixel */
+#define BAGS_BILAGRID_TILE_H 4
+#define BAGS_BILAGRID_STAGE_VERTS 9          /* xy-vertices a tile may reach and still stage them in LDS (3 x 3) */
+#define BAGS_BILAGRID_MAX_G 64
+#define BAGS_BILAGRID_MAX_L 16
+#define BAGS_BILAGRID_TV_BLOCK 256           /* the TV forward has min(ceil(elements / 256), 1024) workgroups */
+#define BAGS_BILAGRID_TV_MAX_BLOCKS 1024
+#define BAGS_BILAGRID_PATH_AUTO 0            /* path */
+#define BAGS_BILAGRID_PATH_DIRECT 1
+typedef struct BagsBilagrid {
+    int32_t N;                               /* grids of the bank, >= 1 */
+    const float* grids;                      /* (N,12,L,Gy,Gx) */
+    int32_t n_rows;                          /* 1..BAGS_MAX_POSE_ROWS */
+    int32_t rows[BAGS_MAX_POSE_ROWS];        /* distinct, each in [0, N) */
+    int32_t C, H, W;                         /* C == 3 */
+    int32_t Gx, Gy, L;
+    int32_t path;                            /* BAGS_BILAGRID_PATH_* */
+    const float* image[BAGS_MAX_POSE_ROWS];  /* (3,H,W) each, the first n_rows given */
+    float* out[BAGS_MAX_POSE_ROWS];          /* (3,H,W) each (forward only) */
+} BagsBilagrid;
+int    bags_bilagrid_forward(const BagsBilagrid* grid, void* stream);
+size_t bags_bilagrid_workspace_size(int32_t n_rows, int32_t H, int32_t W);
+int    bags_bilagrid_backward(const BagsBilagrid* grid, const float* const g_out[BAGS_MAX_POSE_ROWS], void* workspace,
+                              size_t workspace_bytes, float* const g_image[BAGS_MAX_POSE_ROWS], float* g_grids, void* stream);
+size_t bags_bilagrid_tv_workspace_size(int32_t N, int32_t Gx, int32_t Gy, int32_t L);
+int    bags_bilagrid_tv_forward(const float* grids, int32_t N, int32_t Gx, int32_t Gy, int32_t L, void* workspace,
+                                size_t workspace_bytes, float* loss /* (1) */, void* stream);
+int    bags_bilagrid_tv_backward(const float* grids, int32_t N, int32_t Gx, int32_t Gy, int32_t L, const float* g_loss /* (1) */,
+                                 float* g_grids, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
