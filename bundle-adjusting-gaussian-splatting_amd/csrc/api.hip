@@ -1686,4 +1686,96 @@ int bags_depth_to_normal(const float* depth, const float* weights, int32_t H, in
     return BAGS_OK;
 }
 
+// ---- correspondence.hip: per pair and chunk one row of 2 doubles forward, 12 doubles backward; one size serves both
+static size_t carve_correspondence(void* base, int n_rows, int H, int W, double** partials)
+{
+    Carver c(base, false);                       // the base as given: a misaligned one is refused, not rounded
+    double* p = c.take<double>((size_t)n_rows * (size_t)correspondence_chunks(H, W) * BAGS_CORRESPONDENCE_SUMS);
+    if (partials) *partials = p;
+    return c.used();
+}
+
+static bool correspondence_image_ok(int H, int W) { return H >= 1 && W >= 1 && (long long)H * W < (1ll << 31); }
+
+size_t bags_correspondence_workspace_size(int32_t n_rows, int32_t H, int32_t W)
+{
+    if (n_rows < 1 || n_rows > BAGS_MAX_POSE_ROWS || !correspondence_image_ok(H, W)) return 0;
+    return carve_correspondence(nullptr, n_rows, H, W, nullptr);
+}
+
+static int check_correspondence(const char* op, const BagsCorrespondence* a, bool matches)
+{
+    if (!a) return fail(BAGS_ERR_ARG, "%s: null struct", op);
+    if (a->n_rows < 1 || a->n_rows > BAGS_MAX_POSE_ROWS) return fail(BAGS_ERR_ARG, "%s: n_rows %d not in 1..%d", op, a->n_rows, BAGS_MAX_POSE_ROWS);
+    if (a->H < 1 || a->W < 1) return fail(BAGS_ERR_ARG, "%s: empty image %dx%d", op, a->W, a->H);
+    if (!correspondence_image_ok(a->H, a->W)) return fail(BAGS_ERR_ARG, "%s: image %dx%d has 2^31 pixels or more", op, a->W, a->H);
+    if (!(a->min_weight > 0.0f) || std::isinf(a->min_weight)) return fail(BAGS_ERR_ARG, "%s: min_weight must be a positive number", op);
+    if (!(a->min_depth > 0.0) || std::isinf(a->min_depth)) return fail(BAGS_ERR_ARG, "%s: min_depth must be a positive number", op);
+    if (!(a->delta > 0.0)) return fail(BAGS_ERR_ARG, "%s: delta must be a positive number or inf", op);
+    for (int k = 0; k < a->n_rows; ++k) {
+        if (const int rc = check_pinhole(op, k, a->pinhole_src[k])) return rc;
+        if (const int rc = check_pinhole(op, k, a->pinhole_dst[k])) return rc;
+        if (!a->depth[k]) return fail(BAGS_ERR_ARG, "%s: null depth[%d]", op, k);
+        if (!a->weights[k]) return fail(BAGS_ERR_ARG, "%s: null weights[%d]", op, k);
+        if (matches && !a->match[k]) return fail(BAGS_ERR_ARG, "%s: null match[%d]", op, k);
+        if (!a->view_src[k] || !a->view_dst[k]) return fail(BAGS_ERR_ARG, "%s: null view_src[%d] / view_dst[%d]", op, k, k);
+    }
+    return BAGS_OK;
+}
+
+static int check_correspondence_workspace(const char* op, const BagsCorrespondence* a, void* workspace, size_t workspace_bytes)
+{
+    const size_t need = bags_correspondence_workspace_size(a->n_rows, a->H, a->W);
+    if (!workspace || workspace_bytes < need)
+        return fail(BAGS_ERR_ARG, "%s: needs a workspace of %zu bytes (got %zu)", op, need, workspace ? workspace_bytes : (size_t)0);
+    if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return fail(BAGS_ERR_ARG, "%s: the workspace is not 16-byte aligned", op);
+    return BAGS_OK;
+}
+
+int bags_correspondence_forward(const BagsCorrespondence* a, void* workspace, size_t workspace_bytes, float* loss, float* count, double* stats,
+                                void* stream)
+{
+    if (const int rc = check_correspondence("correspondence_forward", a, true)) return rc;
+    if (!loss || !count || !stats) return fail(BAGS_ERR_ARG, "correspondence_forward: null loss / count / stats");
+    if (const int rc = check_correspondence_workspace("correspondence_forward", a, workspace, workspace_bytes)) return rc;
+    if (reinterpret_cast<uintptr_t>(stats) % 8 != 0) return fail(BAGS_ERR_ARG, "correspondence_forward: stats is not 8-byte aligned");
+    double* partials = nullptr;
+    carve_correspondence(workspace, a->n_rows, a->H, a->W, &partials);
+    HIP_TRY(launch_correspondence_fwd(*a, partials, loss, count, stats, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
+int bags_correspondence_backward(const BagsCorrespondence* a, const double* stats, const float* g_loss, void* workspace, size_t workspace_bytes,
+                                 float* const g_depth[BAGS_MAX_POSE_ROWS], float* const g_weights[BAGS_MAX_POSE_ROWS],
+                                 float* const g_view_src[BAGS_MAX_POSE_ROWS], float* const g_view_dst[BAGS_MAX_POSE_ROWS], void* stream)
+{
+    if (const int rc = check_correspondence("correspondence_backward", a, true)) return rc;
+    if (!stats) return fail(BAGS_ERR_ARG, "correspondence_backward: null stats");
+    if (reinterpret_cast<uintptr_t>(stats) % 8 != 0) return fail(BAGS_ERR_ARG, "correspondence_backward: stats is not 8-byte aligned");
+    if (!g_loss) return fail(BAGS_ERR_ARG, "correspondence_backward: null g_loss");
+    bool any_map = false, any_view = false;
+    for (int k = 0; k < a->n_rows; ++k) {
+        any_map |= (g_depth && g_depth[k]) || (g_weights && g_weights[k]);
+        any_view |= (g_view_src && g_view_src[k]) || (g_view_dst && g_view_dst[k]);
+    }
+    if (!any_map && !any_view) return BAGS_OK;
+    double* sums = nullptr;
+    if (any_view) {
+        if (const int rc = check_correspondence_workspace("correspondence_backward", a, workspace, workspace_bytes)) return rc;
+        carve_correspondence(workspace, a->n_rows, a->H, a->W, &sums);
+    }
+    HIP_TRY(launch_correspondence_bwd(*a, stats, g_loss, sums, g_depth, g_weights, g_view_src, g_view_dst, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
+int bags_reproject_pixels(const BagsCorrespondence* a, int32_t H_dst, int32_t W_dst, float* proj, uint8_t* valid, void* stream)
+{
+    if (const int rc = check_correspondence("reproject_pixels", a, false)) return rc;
+    if (a->n_rows != 1) return fail(BAGS_ERR_ARG, "reproject_pixels: one pair per call (n_rows = %d)", a->n_rows);
+    if (H_dst < 1 || W_dst < 1) return fail(BAGS_ERR_ARG, "reproject_pixels: empty target image %dx%d", W_dst, H_dst);
+    if (!proj || !valid) return fail(BAGS_ERR_ARG, "reproject_pixels: null proj / valid");
+    HIP_TRY(launch_reproject_pixels(*a, H_dst, W_dst, proj, valid, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
 }  // extern "C"

@@ -358,6 +358,13 @@ hipError_t launch_normal_prior_bwd(const BagsNormalPrior& a, const double* stats
                                    float* const* g_weights, hipStream_t st);
 hipError_t launch_depth_to_normal(const float* depth, const float* weights, int H, int W, const double* pinhole, float min_weight, float max_jump,
                                   float* normal, uint8_t* valid, hipStream_t st);
+// correspondence.hip: the reprojection of matched pixels on the ordered pairs of a step; partials: n_rows *
+// correspondence_chunks(H, W) rows of 2 doubles forward, 12 doubles backward (carve_correspondence in api.hip); stats (n_rows,2)
+long long correspondence_chunks(int H, int W);
+hipError_t launch_correspondence_fwd(const BagsCorrespondence& a, double* partials, float* loss, float* count, double* stats, hipStream_t st);
+hipError_t launch_correspondence_bwd(const BagsCorrespondence& a, const double* stats, const float* g_loss, double* sums, float* const* g_depth,
+                                     float* const* g_weights, float* const* g_view_src, float* const* g_view_dst, hipStream_t st);
+hipError_t launch_reproject_pixels(const BagsCorrespondence& a, int H_dst, int W_dst, float* proj, uint8_t* valid, hipStream_t st);
 hipError_t launch_appearance_fwd(const BagsAppearance& a, hipStream_t st);
 hipError_t launch_appearance_bwd(const BagsAppearance& a, const float* const* g_out, double* partials, float* const* g_image, float* g_table,
                                  hipStream_t st);

@@ -898,6 +898,70 @@ int    bags_normal_prior_backward(const BagsNormalPrior* args, const double* sta
 int    bags_depth_to_normal(const float* depth, const float* weights, int32_t H, int32_t W, const double pinhole[4], float min_weight,
                             float max_jump, float* normal /* (3,H,W) */, uint8_t* valid /* (H,W) */, void* stream);
 
+/* The multi-view correspondence loss on the rasterizer's maps (csrc/correspondence.hip): a pixel of the source view is un-projected
+ * with the rendered depth, carried into the target view with the two view matrices and held to the pixel a matcher says it
+ * corresponds to (SPARF, CoR-GS).  Row vectors, x_cam = [X_w, 1] @ viewmatrix; view space x right, y down, z forward.  Per ordered
+ * pair: source maps D, A (H,W) float32, view matrices Vi, Vj (4,4) float32 row-major ON THE DEVICE (the host never reads them),
+ * match (2,H,W) = the target pixel (x, y) of source pixel (u, v), an optional confidence conf >= 0 (H,W) (NULL: 1), and host
+ * pinholes (fx, fy, cx, cy) in pixels of both sides.
+ *     solid(u,v) = A >= min_weight and D > 0
+ *     z          = D / A                      one division in the dtype of the maps; everything after it in float64
+ *     Ai = Vi[:3,:3]  bi = Vi[3,:3]  Aj = Vj[:3,:3]  bj = Vj[3,:3]
+ *     M  = inv(Ai) @ Aj ;  c = bj - bi @ M    (the true inverse adj(Ai) / det(Ai), not the transpose)
+ *     x_i = z * ((u - cx_i)/fx_i, (v - cy_i)/fy_i, 1) ;  x_j = x_i @ M + c
+ *     valid(u,v) = solid and conf > 0 and match finite (both components) and x_j.z >= min_depth
+ *     proj = (fx_j x_j.x / x_j.z + cx_j,  fy_j x_j.y / x_j.z + cy_j) ;  r = proj - match ;  e = |r|_2
+ *     rho  = e^2 / 2 where e <= delta,  delta (e - delta / 2) elsewhere        (delta = inf: half the squared distance)
+ *     w = conf on valid pixels ;  cnt = sum w ;  L_k = sum w rho / cnt
+ * cnt <= 0, or det(Ai) zero or not finite: L_k = 0 and every gradient an exact zero, never NaN.  Validity is a decision, not
+ * differentiated through; invalid pixels get exact-zero gradients.  No gradient to match, conf or the pinholes.
+ * forward:  two launches for the n_rows <= BAGS_MAX_POSE_ROWS pairs of a call (pointers and pinholes by value).  A thread is a
+ *           pixel, a workgroup the BAGS_CORRESPONDENCE_CHUNK consecutive pixels of a chunk, the grid (chunk, pair); lane 0 of a
+ *           workgroup forms M and c in double.  A workgroup leaves one row (sum w rho, sum w) of doubles in the workspace; a
+ *           finalize kernel adds a pair's rows in a fixed order and writes loss[k], count[k] = cnt and row k of stats (n_rows,2)
+ *           float64: 1/cnt (0 where cnt <= 0), cnt.
+ * backward: at most two launches.  g_loss (n_rows) are the cotangents of loss.  g_depth / g_weights (NULL, or n_rows pointers of
+ *           which any may be NULL) receive dL/dD and dL/dA of EVERY pixel, each rounded once from double.  g_view_src / g_view_dst
+ *           (likewise) receive dL/dVi and dL/dVj, all 16 floats each, the fourth column exact zeros: the pixel kernel leaves twelve
+ *           partial sums per workgroup (sum x_i^T g_xj and sum g_xj) in the workspace and a second kernel adds them in a fixed
+ *           order and chains in double through c = bj - bi @ M, M = inv(Ai) @ Aj and d inv(A) = -inv(A) dA inv(A).  The workspace
+ *           is needed only where a matrix gradient is wanted.  stats is the forward's, for the same struct.
+ * No atomics, no memset, no host synchronisation; a pair's loss, count and gradients have the bits of a call of its own, and each
+ * output the same bits whichever other is wanted.
+ * bags_reproject_pixels: one launch, the first pair of the struct alone (n_rows == 1; match and conf are not read): proj (2,H,W)
+ *           float32 where the pixel is solid and x_j.z >= min_depth, zeros elsewhere; valid (H,W) uint8 where proj also lies inside
+ *           the W_dst x H_dst image, -0.5 <= x < W_dst - 0.5 and -0.5 <= y < H_dst - 0.5.
+ * workspace: bags_correspondence_workspace_size bytes (0 for invalid arguments), 16-byte aligned, no initialisation; one size
+ *           serves the forward and the backward.
+ * min_weight, min_depth and delta must be positive, delta may be inf.  H * W must be below 2^31. */
+#define BAGS_CORRESPONDENCE_CHUNK 256        /* pixels per workgroup: a workgroup of 256 threads, a thread a pixel */
+#define BAGS_CORRESPONDENCE_STATS 2          /* doubles per stats row (and per partial row of the forward) */
+#define BAGS_CORRESPONDENCE_SUMS 12          /* doubles per workgroup of the backward's partial sums */
+typedef struct BagsCorrespondence {
+    int32_t H, W;
+    int32_t n_rows;                          /* pairs of the call, 1..BAGS_MAX_POSE_ROWS */
+    float min_weight;
+    double min_depth;
+    double delta;
+    double pinhole_src[BAGS_MAX_POSE_ROWS][4];   /* (fx, fy, cx, cy) in pixels per pair; fx, fy non-zero and finite */
+    double pinhole_dst[BAGS_MAX_POSE_ROWS][4];
+    const float* depth[BAGS_MAX_POSE_ROWS];  /* (H,W) each, the first n_rows given: the SOURCE view's maps */
+    const float* weights[BAGS_MAX_POSE_ROWS];
+    const float* match[BAGS_MAX_POSE_ROWS];  /* (2,H,W) each */
+    const float* conf[BAGS_MAX_POSE_ROWS];   /* any of them NULL: every pixel weighs 1 */
+    const float* view_src[BAGS_MAX_POSE_ROWS];   /* (4,4) each, on the device */
+    const float* view_dst[BAGS_MAX_POSE_ROWS];
+} BagsCorrespondence;
+size_t bags_correspondence_workspace_size(int32_t n_rows, int32_t H, int32_t W);
+int    bags_correspondence_forward(const BagsCorrespondence* args, void* workspace, size_t workspace_bytes, float* loss /* (n_rows) */,
+                                   float* count /* (n_rows) */, double* stats /* (n_rows,2) */, void* stream);
+int    bags_correspondence_backward(const BagsCorrespondence* args, const double* stats, const float* g_loss /* (n_rows) */,
+                                    void* workspace, size_t workspace_bytes, float* const g_depth[BAGS_MAX_POSE_ROWS],
+                                    float* const g_weights[BAGS_MAX_POSE_ROWS], float* const g_view_src[BAGS_MAX_POSE_ROWS],
+                                    float* const g_view_dst[BAGS_MAX_POSE_ROWS], void* stream);
+int    bags_reproject_pixels(const BagsCorrespondence* args, int32_t H_dst, int32_t W_dst, float* proj /* (2,H,W) */,
+                             uint8_t* valid /* (H,W) */, void* stream);
+
 /* Per-image bilateral-grid colour (csrc/bilagrid.hip): gsplat's lib_bilagrid slice-and-apply on the rendered image, behind the
  * appearance step and in front of the loss, and the total variation of the grids.  The grids of all N training images are one
  * (N,12,L,Gy,Gx) device tensor in gsplat's layout: coefficient k = 4*c + j of a vertex is entry [c][j] of a 3x4 affine matrix; the
