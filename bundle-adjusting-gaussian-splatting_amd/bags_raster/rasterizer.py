@@ -590,7 +590,8 @@ def _alloc_backward(lib, need, k, shapes, P, dev, ws_instances, gaussian_grads=T
         want = [(n, sh, False) for n, sh, _ in want]
     sizes = {n: (math.prod(sh) if f else 0) for n, sh, f in want}
     total = sum((v + 63) // 64 * 64 for v in sizes.values())
-    flat = torch.empty(total, dtype=torch.float32, device=dev) if total else None
+    # (P = 0: every wanted slice is empty and total is 0 -- still a buffer to carve the empty gradients from)
+    flat = torch.empty(total, dtype=torch.float32, device=dev) if any(f for _, _, f in want) else None
     carved, off = {}, 0
     for n, sh, f in want:
         carved[n] = flat[off:off + sizes[n]].view(sh) if f else None

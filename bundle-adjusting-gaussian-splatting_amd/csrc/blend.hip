@@ -339,6 +339,11 @@ blend_bwd_scan_kernel(int W, int H, int grid_x, int T, const uint4* __restrict__
     // 64-slot segment (a byte each, from a ballot of the staging wave), segtot[segment] the segment's four totals
     __shared__ u32 rk4[CH];
     __shared__ __attribute__((aligned(16))) u32 segtot[4];
+    // the LDS budget of SCAN_WG_PER_CU workgroups on a CU's 160 KB, every instance: EXTRA pays for its fourth float4 per pixel pair and
+    // for recZ with EXTRA_SLOTS slots per wave copy (with EXTRA_SLOTS 0 its instances take 55.6 .. 56.7 KB and run two per CU)
+    static_assert(sizeof(recA) + sizeof(recB) + sizeof(recC) + sizeof(pixq) + sizeof(recZ) + sizeof(lists) + sizeof(masks) + sizeof(acc)
+                  + sizeof(blk_maxc) + sizeof(chunk_pos) + sizeof(rk4) + sizeof(segtot) <= 160 * 1024 / SCAN_WG_PER_CU,
+                  "blend_bwd_scan_kernel: the instance's LDS does not fit SCAN_WG_PER_CU workgroups per CU");
 
     PH(unsigned long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};)
     PH(unsigned long long tlast = __builtin_amdgcn_s_memtime();)

@@ -7,7 +7,7 @@ import torch
 
 from oracle import raster_oracle as O
 from parity import GRAD_NAMES
-from scenes import camera_tensors, hip_settings, oracle_settings, rel_err
+from scenes import camera_tensors, hip_settings, make_case, oracle_settings, rel_err
 
 TILE = O.TILE
 
@@ -114,9 +114,10 @@ def oracle_inputs(scene, shift=None, colors=None, cov3D=None):
 
 
 def run_hip_ex(scene, cam, deg, g_img, g_depth, g_weights, bg=None, shift=None, colors=None, cov3D=None, depth_key="z",
-               tile_bounds="opacity", binning="auto", frozen_camera=False, depth_weights_grad=True):
+               tile_bounds="opacity", binning="auto", frozen_camera=False, depth_weights_grad=True, scale_modifier=1.0,
+               clamp_grad="stock", conic_grad="stock"):
     """Forward + backward through the product op with depth_weights_grad; any cotangent may be None (that output is not in the
-    loss).  Returns (outputs, grads)."""
+    loss; all three None: the forward alone, grads is None).  Returns (outputs, grads)."""
     from bags_raster import GaussianRasterizer
     dev = torch.device("cuda")
     t = {k: v.to(dev).clone().requires_grad_(True) for k, v in scene.items()}
@@ -127,13 +128,16 @@ def run_hip_ex(scene, cam, deg, g_img, g_depth, g_weights, bg=None, shift=None, 
     sf = None if frozen_camera else (torch.zeros(3) if shift is None else shift).to(dev).requires_grad_(True)
     col = None if colors is None else colors.to(dev).clone().requires_grad_(True)
     cov = None if cov3D is None else cov3D.to(dev).clone().requires_grad_(True)
-    st = hip_settings(cam, deg, dev, bg=bg, depth_key=depth_key, tensors=ct, tile_bounds=tile_bounds, binning=binning)
+    st = hip_settings(cam, deg, dev, bg=bg, scale_modifier=scale_modifier, depth_key=depth_key, tensors=ct, tile_bounds=tile_bounds,
+                      binning=binning, clamp_grad=clamp_grad, conic_grad=conic_grad)
     st = st._replace(depth_weights_grad=depth_weights_grad)
     outs = GaussianRasterizer(st)(means3D=t["means3D"], means2D=m2, means2D_densify=m2d, shift_factors=sf,
                                   shs=None if col is not None else t["shs"], colors_precomp=col, opacities=t["opacities"],
                                   scales=None if cov is not None else t["scales"], rotations=None if cov is not None else t["rotations"],
                                   cov3D_precomp=cov)
     pairs = [(o, g) for o, g in ((outs[0], g_img), (outs[2], g_depth), (outs[3], g_weights)) if g is not None]
+    if not pairs:
+        return [o.detach().cpu() for o in outs], None
     torch.autograd.backward([o for o, _ in pairs], [g.to(dev) for _, g in pairs])
     src = dict(means3D=t["means3D"], means2D=m2, means2D_densify=m2d, shift_factors=sf, shs=t["shs"], colors_precomp=col,
                opacities=t["opacities"], scales=t["scales"], rotations=t["rotations"], cov3D_precomp=cov, **ct)
@@ -151,8 +155,14 @@ def cotangents(H, W, seed, image=True, depth=True, weights=True, mask=None):
     return gi, gd, gw
 
 
-def compare_ex(scene, cam, deg, seed=1, check_fp64=True, tiles=None, image=True, depth=True, weights=True, **kw):
-    """HIP (depth_weights_grad) against the fp32 reference and its fp64 replay: relative error of every gradient tensor."""
+ORACLE_KW = ("bg", "scale_modifier", "depth_key", "tile_bounds", "clamp_grad", "conic_grad")
+
+
+def compare_ex(scene, cam, deg, seed=1, check_fp64=True, tiles=None, image=True, depth=True, weights=True, return_oracle=False, **kw):
+    """HIP (depth_weights_grad) against the fp32 reference and its fp64 replay: relative error of every gradient tensor.  The forward
+    is held to itself here (asserted: the five outputs with the keyword on are torch.equal to those with it off; parity.compare holds
+    them to the oracle).  return_oracle: also the fp32 reference's lists and preprocessed values, for host derivations that
+    must not lean on the code under test (parity.chunk_quadrant_counts)."""
     H, W = cam.image_height, cam.image_width
     mask = None
     if tiles is not None:
@@ -163,13 +173,109 @@ def compare_ex(scene, cam, deg, seed=1, check_fp64=True, tiles=None, image=True,
             mask[ty * 16:ty * 16 + 16, tx * 16:tx * 16 + 16] = 1.0
     gi, gd, gw = cotangents(H, W, seed, image, depth, weights, mask)
     outs, grads = run_hip_ex(scene, cam, deg, gi, gd, gw, **kw)
-    okw = {k: v for k, v in kw.items() if k in ("bg", "depth_key", "tile_bounds")}
-    s = oracle_settings(cam, deg, **okw)
+    outs_off, _ = run_hip_ex(scene, cam, deg, None, None, None, **{**kw, "depth_weights_grad": False})
+    s = oracle_settings(cam, deg, **{k: v for k, v in kw.items() if k in ORACLE_KW})
     inp = oracle_inputs(scene, kw.get("shift"), kw.get("colors"), kw.get("cov3D"))
     st32, gr32 = render_and_grad_ex(inp, s, gi, gd, gw, torch.float32, tiles=tiles)
+    for name, a, b in zip(("image", "radii", "depth", "weights", "mean2D"), outs, outs_off):
+        assert torch.equal(a, b), f"forward output {name} differs between depth_weights_grad on and off"
     rep = {"grad_rel_fp32": {k: rel_err(grads[k], gr32[k]) for k in GRAD_NAMES if grads.get(k) is not None and k in gr32}}
     if check_fp64:
         _, gr64 = render_and_grad_ex(inp, s, gi, gd, gw, torch.float64, discrete=O.discrete_of(st32), tiles=tiles)
         rep["grad_rel_fp64"] = {k: rel_err(grads[k], gr64[k]) for k in GRAD_NAMES if grads.get(k) is not None and k in gr64}
         rep["oracle32_vs_64"] = {k: rel_err(gr32[k], gr64[k]) for k in GRAD_NAMES if k in gr32 and k in gr64}
+    if return_oracle:
+        return rep, oracle_lists(st32)
     return rep
+
+
+def oracle_lists(st):
+    """What the host derivations need of an oracle forward: its lists, ranges, n_contrib and preprocessed xy / conic / opacity."""
+    pre = st.pre
+    return dict(point_list=st.point_list.numpy(), ranges=st.ranges.numpy(), n_contrib=st.n_contrib.numpy(), gx=st.gx,
+                xy=pre.xy.detach().double().numpy(), conic=pre.conic.detach().double().numpy(),
+                opacity=pre.opacity.detach().double().numpy())
+
+
+def oracle_forward(scene, cam, deg, **kw):
+    """The fp32 oracle's forward alone (no gradients) with compare_ex's keywords."""
+    s = oracle_settings(cam, deg, **{k: v for k, v in kw.items() if k in ORACLE_KW})
+    leaf, s2 = leaves_of(oracle_inputs(scene, kw.get("shift"), kw.get("colors"), kw.get("cov3D")), s, torch.float32, want=False)
+    with torch.no_grad():
+        return forward(leaf, s2, torch.float32)
+
+
+def bwd_constants():
+    """The sizes launch_blend_bwd and blend_bwd_scan_kernel decide with, read from csrc/blend.hip (the shipped build defines none of
+    them on the command line)."""
+    import os
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src = open(os.path.join(root, "bundle-adjusting-gaussian-splatting_amd", "csrc", "blend.hip")).read()
+    return {n: int(re.search(r"#define\s+%s\s+(\d+)" % n, src).group(1)) for n in
+            ("BCHUNK", "BSLOTS", "WCHUNK", "WSLOTS", "BWD_SPARSE_PER_TILE", "BWD_DENSE_PER_TILE", "COMPACT_DENSITY_NUM", "EXTRA_SLOTS")}
+
+
+def bwd_path(n_instances, T, tile_bounds, extra=True, binning="auto"):
+    """launch_blend_bwd's choice for a backward of n_instances list entries on T tiles, as the code makes it: the chunk geometry
+    (sparse: WCHUNK / WSLOTS up to BWD_SPARSE_PER_TILE instances per tile; the stock tile rule on the tile-binned path stages only
+    its record holders and scales the count by COMPACT_DENSITY_NUM / 5), the dense-scene mode, and the resulting chunk length CH and
+    slots SL per wave copy (8 fewer for the compacted lists, EXTRA_SLOTS fewer with the depth / weights cotangents)."""
+    c = bwd_constants()
+    compact = binning != "radix" and tile_bounds != "opacity"
+    x5 = n_instances * (c["COMPACT_DENSITY_NUM"] if compact else 5)
+    sparse = x5 <= 5 * c["BWD_SPARSE_PER_TILE"] * T
+    SL = (c["WSLOTS"] if sparse else c["BSLOTS"]) - (8 if compact else 0) - (c["EXTRA_SLOTS"] if extra else 0)
+    return dict(compact=compact, sparse=sparse, dense=n_instances > c["BWD_DENSE_PER_TILE"] * T,
+                CH=c["WCHUNK"] if sparse else c["BCHUNK"], SL=SL, SL_default=SL + (c["EXTRA_SLOTS"] if extra else 0))
+
+
+def scene_chunks(scene, cam, deg, tile_bounds="opacity", **kw):
+    """(bwd_path of the scene, its chunks as parity.chunk_quadrant_counts lists them, the oracle forward), from the oracle alone."""
+    from parity import chunk_quadrant_counts
+    st = oracle_forward(scene, cam, deg, tile_bounds=tile_bounds, **kw)
+    o = oracle_lists(st)
+    path = bwd_path(int(st.point_list.numel()), st.gx * st.gy, tile_bounds)
+    rec = None
+    if path["compact"]:          # the record holders: the (tile, Gaussian) pairs of the opacity rule's lists
+        ro = oracle_lists(oracle_forward(scene, cam, deg, tile_bounds="opacity", **kw))
+        rec = (ro["point_list"], ro["ranges"])
+    chunks = chunk_quadrant_counts(o["point_list"], o["ranges"], o["n_contrib"], o["xy"], o["conic"], o["opacity"], o["gx"], path["CH"], rec)
+    return path, chunks, st
+
+
+# ---- small scenes, each built to take one path of the EXTRA backward (tests/test_depth_grad_cpu.py proves the path from the oracle
+# alone, tests/test_depth_grad_gpu.py holds the kernels to the oracle on it).  All on a 64 x 48 image (12 tiles) unless named otherwise.
+def _faint(scene):
+    scene["opacities"] = scene["opacities"] * 0.2
+    return scene
+
+
+def _huge_and_small(n_huge, n_small, sm_small, seed=21):
+    """n_huge faint screen-filling splats (every one reaches every quadrant of every tile) among n_small small ones (each reaches a
+    quadrant or two): the small ones fill a chunk's staged slots without filling any one wave copy."""
+    a, cam = make_case(n_huge, 64, 48, 8.0, 1, seed=seed)
+    b, _ = make_case(n_small, 64, 48, sm_small, 1, seed=seed + 1)
+    return _faint({k: torch.cat([a[k], b[k]], 0) for k in a}), cam
+
+
+BAND_DENSE = {"opacity": (160, 1500, 1.0), "aabb": (150, 1000, 2.0)}
+
+
+def path_scene(name, tile_bounds="opacity"):
+    """(scene, camera, SH degree) of a named path scene."""
+    if name == "band_sparse":          # chunks of 240, some with SL - 16 < reach <= SL: one pass in the default kernel, two with the extras
+        return _huge_and_small(115, 1500, 0.5) + (1,)
+    if name == "band_dense":           # the same band in the 224-splat geometry (one scene per tile rule: the stock rule needs 500 per tile)
+        return _huge_and_small(*BAND_DENSE[tile_bounds]) + (1,)
+    if name == "overflow":             # test_wide_chunks_that_overflow_a_wave_copy's scene: every full chunk in two halves
+        scene, cam = make_case(420, 64, 48, 8.0, 1, seed=21)
+        return _faint(scene), cam, 1
+    if name == "dense_mode":           # the same family above BWD_DENSE_PER_TILE: live bytes instead of zero records
+        scene, cam = make_case(600, 64, 48, 8.0, 1, seed=21)
+        return _faint(scene), cam, 1
+    if name == "saturated":            # test_saturated_alpha_and_early_termination's scene
+        scene, cam = make_case(800, 96, 96, 6.0, 1, seed=11)
+        scene["opacities"] = torch.full_like(scene["opacities"], 0.999)
+        return scene, cam, 1
+    raise KeyError(name)

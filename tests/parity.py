@@ -250,6 +250,43 @@ def tile_sort_paths(keys_sorted, ranges):
     return out
 
 
+def chunk_quadrant_counts(point_list, ranges, n_contrib, xy, conic, opacity, gx, CH, record_lists=None):
+    """The backward's chunks (csrc/blend.hip, blend_bwd_scan_kernel), re-derived on the host: every tile's list is consumed back to
+    front from its deepest contributor (the largest n_contrib of its pixels) in chunks of CH staged splats, and a wave's copy of the
+    sums holds a slot for every staged splat whose 4x4-block reach mask (analysis_geometries.sub_masks: block_mask16's rule) touches
+    the wave's quadrant.  Returns {tile: [(staged, largest per-quadrant reach count), ...]}, deepest chunk first; a chunk whose count
+    exceeds the kernel's SL runs its group phase in two halves.
+    record_lists = (point_list, ranges) of the opacity rule: the stock rule on the tile-binned path (COMPACT) stages its chunks from
+    the compacted list of the positions that hold a gradient record -- the (tile, Gaussian) pairs the opacity rule emits -- starting
+    at the number of those in front of the deepest contributor.  xy / conic / opacity: the preprocessed (P, .) arrays (numpy, fp64)."""
+    import numpy as np
+    from analysis_geometries import sub_masks, quadrant_groups
+    pl = np.asarray(point_list).astype(np.int64)
+    rg = np.asarray(ranges).astype(np.int64)
+    nc = np.asarray(n_contrib)
+    quads = quadrant_groups(4, 4)
+    out = {}
+    for t in range(rg.shape[0]):
+        ty, tx = divmod(t, gx)
+        tile_nc = nc[ty * 16:ty * 16 + 16, tx * 16:tx * 16 + 16]
+        hi = int(tile_nc.max()) if tile_nc.size else 0               # the tile's deepest contributor: where its chunks start
+        ids = pl[rg[t, 0]:rg[t, 0] + hi]
+        if record_lists is not None:
+            rpl, rrg = np.asarray(record_lists[0]).astype(np.int64), np.asarray(record_lists[1]).astype(np.int64)
+            ids = ids[np.isin(ids, rpl[rrg[t, 0]:rrg[t, 1]])]
+            hi = ids.size
+        chunks = []
+        while hi > 0:
+            cnt = min(hi, CH)
+            c = ids[hi - cnt:hi]
+            m = sub_masks(xy[c, 0], xy[c, 1], conic[c, 0], conic[c, 1], conic[c, 2], opacity[c], np.full(cnt, tx * 16.0),
+                          np.full(cnt, ty * 16.0), 4, 4)
+            chunks.append((cnt, max(int(m[:, q].any(1).sum()) for q in quads)))
+            hi -= cnt
+        out[t] = chunks
+    return out
+
+
 INT_KEYS = ("radii_equal", "tiles_touched_equal", "rect_equal", "depth_bits_equal", "point_list_equal", "keys_equal",
             "ranges_equal")
 

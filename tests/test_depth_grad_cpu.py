@@ -8,7 +8,7 @@ import torch
 
 from bags_raster import _lib
 from oracle import raster_oracle as O
-from depth_oracle import backward_ex, forward, leaves_of
+from depth_oracle import backward_ex, bwd_constants, bwd_path, forward, leaves_of, oracle_forward, path_scene, scene_chunks
 from scenes import make_case, oracle_settings
 
 
@@ -71,20 +71,17 @@ def test_depth_weights_grad_keyword():
     f = GaussianRasterizationSettings._fields
     assert f[-1] == "depth_weights_grad" and GaussianRasterizationSettings._field_defaults["depth_weights_grad"] is False
     assert inspect.signature(render).parameters["depth_weights_grad"].default is False
-    eye = torch.eye(4)
-    st = GaussianRasterizationSettings(32, 32, 0.5, 0.5, torch.zeros(3), 1.0, eye, eye, eye, 0, torch.zeros(3), False, False, 0,
-                                       depth_weights_grad="yes")
+    # every tensor on the machine's device: with a GPU the keyword is then the call's only defect (a CPU bg next to CUDA tensors was
+    # reported first: "bg is on cpu"), without one the device check comes first
     x = torch.zeros(4, 3, device="cuda" if torch.cuda.is_available() else "cpu")
+    dev = x.device
+    eye = torch.eye(4, device=dev)
+    st = GaussianRasterizationSettings(32, 32, 0.5, 0.5, torch.zeros(3, device=dev), 1.0, eye, eye, eye, 0, torch.zeros(3, device=dev),
+                                       False, False, 0, depth_weights_grad="yes")
     from bags_raster.rasterizer import _Packed
-    with pytest.raises((ValueError, RuntimeError), match="depth_weights_grad|AMD GPU"):
-        _Packed(st, x, None, None, None, x, torch.ones_like(x[:, :1]), x, torch.zeros(4, 4, device=x.device), None, eye, eye, eye,
-                torch.zeros(3))
-    if x.is_cuda:      # (on a CPU host the device check comes first)
-        dev = x.device
-        st = st._replace(bg=st.bg.to(dev))
-        with pytest.raises(ValueError, match="depth_weights_grad must be True or False"):
-            _Packed(st, x, None, None, None, x, torch.ones_like(x[:, :1]), x, torch.zeros(4, 4, device=dev), None,
-                    eye.to(dev), eye.to(dev), eye.to(dev), torch.zeros(3, device=dev))
+    with pytest.raises((ValueError, RuntimeError), match="depth_weights_grad must be True or False" if x.is_cuda else "AMD GPU"):
+        _Packed(st, x, None, None, None, x, torch.ones_like(x[:, :1]), x, torch.zeros(4, 4, device=dev), None, eye, eye, eye,
+                torch.zeros(3, device=dev))
     assert GaussianRasterizer is not None
 
 
@@ -184,3 +181,112 @@ def test_weights_cotangent_has_the_closed_form():
         assert bool((dG[~c] == 0).all())
         n_pairs += int(c.sum())
     assert n_pairs > 100
+
+
+# ---- the path scenes of tests/test_depth_grad_gpu.py: that each takes the path it is named for, from the oracle alone
+def _quadrant_counts(name, tile_bounds):
+    scene, cam, deg = path_scene(name, tile_bounds)
+    path, chunks, st = scene_chunks(scene, cam, deg, tile_bounds=tile_bounds)
+    return path, [c for per_tile in chunks.values() for c in per_tile], st, cam
+
+
+def test_launch_constants_are_the_ones_the_scenes_were_tuned_for():
+    """bwd_path reads them from csrc/blend.hip; the counts in the docstrings below were found with these."""
+    assert bwd_constants() == dict(BCHUNK=224, BSLOTS=176, WCHUNK=240, WSLOTS=168, BWD_SPARSE_PER_TILE=300, BWD_DENSE_PER_TILE=480,
+                                   COMPACT_DENSITY_NUM=3, EXTRA_SLOTS=16)
+    # launch_blend_bwd's comparison, both tile rules: 5 n <= 1500 T, and 3 n <= 1500 T for the compacted lists
+    assert bwd_path(3600, 12, "opacity")["sparse"] and not bwd_path(3601, 12, "opacity")["sparse"]
+    assert bwd_path(6000, 12, "aabb")["sparse"] and not bwd_path(6001, 12, "aabb")["sparse"]
+    assert not bwd_path(5760, 12, "opacity")["dense"] and bwd_path(5761, 12, "aabb")["dense"]
+    assert [bwd_path(n, 12, tb)["SL"] for n, tb in ((1, "opacity"), (1, "aabb"), (9999, "opacity"), (9999, "aabb"))] == [152, 144, 160, 152]
+    assert bwd_path(1, 12, "aabb", binning="radix")["SL"] == 152           # the radix path's lists are not compacted
+
+
+@pytest.mark.parametrize("name,tile_bounds,sparse,dense", [("band_sparse", "opacity", True, False), ("band_sparse", "aabb", True, False),
+                                                            ("band_dense", "opacity", False, False), ("band_dense", "aabb", False, True)])
+def test_band_scenes_have_chunks_only_the_extras_split(name, tile_bounds, sparse, dense):
+    """A chunk whose fullest quadrant is reached by more than SL - 16 and at most SL staged splats runs in one pass in the default
+    kernel and in two halves with the extras (SL: the default instance's slots per wave copy).  At least 3 such chunks per scene, and
+    at least 3 of them two or more away from either end of the band (the host evaluates the reach rule in fp64, the forward in fp32).
+    Found (instances per tile; geometry; chunks: one pass / in the band / over SL also by default; the band's counts):
+      band_sparse opacity  273.0   240 / 168   9 /  7 /  2   155 155 155 159 161 166 166   of (152, 168]
+      band_sparse aabb     388.9   240 / 160   8 /  5 /  5   151 155 155 155 159           of (144, 160]
+      band_dense  opacity  376.4   224 / 176  19 /  4 /  6   168 169 171 172               of (160, 176]
+      band_dense  aabb     738.6   224 / 168  11 /  5 / 14   155 155 156 156 164           of (152, 168]
+    (the stock rule counts 3/5 of its list as record holders: sparse up to 500 per tile, so its dense-geometry scene is also past 480)"""
+    path, chunks, st, _ = _quadrant_counts(name, tile_bounds)
+    per_tile = st.point_list.numel() / (st.gx * st.gy)
+    assert path["sparse"] == sparse and path["dense"] == dense and path["compact"] == (tile_bounds == "aabb"), (per_tile, path)
+    assert (per_tile <= (500 if tile_bounds == "aabb" else 300)) == sparse and (per_tile > 480) == dense, per_tile
+    SL = path["SL_default"]
+    band = sorted(q for _, q in chunks if SL - 16 < q <= SL)
+    print(name, tile_bounds, per_tile, path, len(chunks), band)
+    assert len(band) >= 3 and sum(SL - 16 + 3 <= q <= SL - 2 for q in band) >= 3, band
+    assert any(q <= SL - 16 for _, q in chunks) and any(q > SL for _, q in chunks)      # and both neighbours of the band
+
+
+def test_the_1500_splat_family_has_band_chunks_too():
+    """make_case(1500, 128, 96, 1.0, 3), the one family of the older oracle comparisons of tests/test_depth_grad_gpu.py: sparse geometry
+    only (154 .. 156 instances per tile), yet 6 to 9 of its ~60 chunks lie in (152, 168] -- seed 11 (the sh3 case): 153 154 154 154 156
+    157 161 165 168; seed 14 (test_zero_extra_cotangents_leave_the_image_gradients, which cites the two-half branch): 153 155 155 157
+    159 159 163.  So that family does run the branch, in the 240 / 168 geometry alone; the scenes above add the 224 / 176 geometry, chunks
+    that split in every instance and the dense-scene mode."""
+    for seed, n_band in ((11, 9), (14, 7)):
+        scene, cam = make_case(1500, 128, 96, 1.0, 3, seed=seed)
+        path, chunks, st = scene_chunks(scene, cam, 3)
+        assert path["sparse"] and not path["dense"] and path["SL_default"] == 168
+        band = [q for per_tile in chunks.values() for _, q in per_tile if 152 < q <= 168]
+        assert abs(len(band) - n_band) <= 2 and len(band) >= 3, band        # (+-2: counts at an end of the band, fp64 here / fp32 there)
+
+
+@pytest.mark.parametrize("tile_bounds", ["opacity", "aabb"])
+def test_overflow_scene_splits_every_full_chunk(tile_bounds):
+    """Every chunk that stages a full CH splats is over SL (with and without the extras): 12 of 12 with either rule, at 377.5 (224 / 160,
+    opacity rule) and 420.0 (240 / 144: sparse for the stock rule) instances per tile; the 12 second chunks are shorter and 6 of them
+    land in the band."""
+    path, chunks, st, _ = _quadrant_counts("overflow", tile_bounds)
+    assert path["sparse"] == (tile_bounds == "aabb") and not path["dense"]
+    full = [q for n, q in chunks if n == path["CH"]]
+    assert len(full) >= 12 and all(q > path["SL_default"] for q in full), full
+
+
+def test_dense_mode_scene_is_past_the_threshold():
+    """525.5 instances per tile (> 480): live bytes, no zero records; 24 full chunks, all split."""
+    path, chunks, st, _ = _quadrant_counts("dense_mode", "opacity")
+    assert path["dense"] and not path["sparse"] and st.point_list.numel() > 480 * st.gx * st.gy
+    assert sum(n == 224 and q > 176 for n, q in chunks) >= 12
+
+
+def test_saturated_scene_stops_early():
+    """Opaque splats: the oracle's n_contrib is below the tile's list length on every pixel (1.000 of them; the bar is half)."""
+    scene, cam, deg = path_scene("saturated")
+    st = oracle_forward(scene, cam, deg)
+    lens = (st.ranges[:, 1] - st.ranges[:, 0]).view(st.gy, st.gx)
+    per_pixel = lens[torch.arange(cam.image_height)[:, None] // 16, torch.arange(cam.image_width)[None, :] // 16]
+    assert float((st.n_contrib < per_pixel).float().mean()) > 0.5
+    assert float(st.final_T.median()) < 1e-3                          # most pixels ran down to the T < 1e-4 stop ...
+    assert int((st.n_contrib > 0).sum()) == st.n_contrib.numel()      # ... and every pixel has a contributor
+
+
+@pytest.mark.parametrize("W,H", [(100, 70), (17, 33)])
+def test_ragged_scenes_overhang(W, H):
+    """The right column and the bottom row of tiles overhang the image and hold contributors (100 x 70: 7 x 5 tiles, 17 x 33: 2 x 3)."""
+    scene, cam = make_case(800, W, H, 2.0, 2, seed=W)
+    st = oracle_forward(scene, cam, 2)
+    assert W % 16 and H % 16 and (st.gx, st.gy) == ((W + 15) // 16, (H + 15) // 16)
+    assert int((st.n_contrib[:, (st.gx - 1) * 16:] > 0).sum()) > 0 and int((st.n_contrib[(st.gy - 1) * 16:, :] > 0).sum()) > 0
+
+
+def test_clamp_scene_has_clamped_gaussians_in_its_lists():
+    """settings[clamp_exact]: 1.3 x the field of view is crossed by Gaussians that reach the image (the two clamp semantics differ
+    only there)."""
+    import math
+    from scenes import camera_tensors
+    scene, cam = make_case(1500, 96, 64, 2.0, 1, seed=3, dist=2.5)
+    st = oracle_forward(scene, cam, 1, clamp_grad="exact")
+    t = torch.cat([scene["means3D"], torch.ones(1500, 1)], 1) @ camera_tensors(cam)["viewmatrix"]
+    clamped = ((t[:, 0] / t[:, 2]).abs() > 1.3 * math.tan(cam.FoVx / 2)) | ((t[:, 1] / t[:, 2]).abs() > 1.3 * math.tan(cam.FoVy / 2))
+    listed = torch.zeros(1500, dtype=torch.bool)
+    listed[st.point_list.long()] = True
+    print(int((clamped & listed).sum()))
+    assert int((clamped & listed).sum()) > 50

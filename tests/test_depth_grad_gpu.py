@@ -6,7 +6,7 @@ import math
 import pytest
 import torch
 
-from depth_oracle import compare_ex, cotangents, run_hip_ex
+from depth_oracle import compare_ex, cotangents, path_scene, run_hip_ex
 from parity import sample_tiles
 from scenes import make_case
 
@@ -173,6 +173,163 @@ def test_extras_with_the_split_and_accumulating_backwards():
     ref = run("plain")
     for mode in ("gate", "in_place", "factored"):
         _equal(run(mode), ref)
+
+
+# ---- every path of the EXTRA backward against the oracle.  tests/test_depth_grad_cpu.py proves from the oracle alone that each scene
+# takes the path it is named for (chunk geometry, dense-scene mode, chunks that only the extras split, ...).
+def _report(name, rep):
+    from parity import dump_report
+    dump_report(name, rep)
+
+
+def _path_case(name, tile_bounds, depth_only=False, **kw):
+    scene, cam, deg = path_scene(name, tile_bounds)
+    res = compare_ex(scene, cam, deg, seed=21, tile_bounds=tile_bounds, image=not depth_only, weights=not depth_only, **kw)
+    _report(f"extras_{name}[{tile_bounds}{',depth_only' if depth_only else ''}]", res[0] if kw.get("return_oracle") else res)
+    return res
+
+
+@pytest.mark.parametrize("cotangents_on", ["all", "depth_only"])
+@pytest.mark.parametrize("tile_bounds", ["opacity", "aabb"])
+@pytest.mark.parametrize("name", ["band_sparse", "band_dense", "overflow"])
+def test_extras_on_split_chunks(name, tile_bounds, cotangents_on):
+    """band_*: chunks whose fullest quadrant lies between SL - 16 and SL run in one pass in the default kernel and in two halves here (the
+    one branch the extras add to the control flow), in both chunk geometries (240 / 168 and 224 / 176) and from consecutive and from
+    compacted lists; overflow: every full chunk in two halves.  With the depth cotangent alone dL/dz (the twelfth sum of a slot)
+    carries the whole gradient."""
+    _assert_ex(_path_case(name, tile_bounds, cotangents_on == "depth_only"))
+
+
+def test_extras_in_the_dense_scene_mode(monkeypatch):
+    """525 instances per tile: the library's own threshold picks the dense-scene mode (live bytes; preprocess_bwd must not read the
+    dL/dz of a record nobody wrote).  The oracle's bars, and bit for bit what the zero-record mode gives."""
+    from bags_raster import rasterizer as R
+    scene, cam, deg = path_scene("dense_mode")
+    gi, gd, gw = cotangents(48, 64, 21)
+    monkeypatch.setattr(R, "DENSE_PER_TILE", 0)
+    _assert_ex(_path_case("dense_mode", "opacity"))
+    _, a = run_hip_ex(scene, cam, deg, gi, gd, gw)
+    monkeypatch.setattr(R, "DENSE_PER_TILE", -1)
+    _, b = run_hip_ex(scene, cam, deg, gi, gd, gw)
+    _equal(a, b)
+
+
+def test_extras_on_saturated_pixels():
+    """Opaque splats: every pixel stops at T < 1e-4 long before its list ends -- dL/dweights and dL/ddepth of the splats behind the cut
+    are exactly absent in the reference (they are not in its graph)."""
+    rep, o = _path_case("saturated", "opacity", return_oracle=True)
+    _assert_ex(rep)
+    lens = (o["ranges"][:, 1] - o["ranges"][:, 0]).reshape(6, 6)            # 96 x 96: 6 x 6 tiles
+    assert (o["n_contrib"] < lens.repeat(16, 0).repeat(16, 1)).mean() > 0.5  # the walk this run was compared on did end early
+
+
+@pytest.mark.parametrize("W,H", [(100, 70), (17, 33)])
+def test_extras_on_tiles_that_overhang_the_image(W, H):
+    scene, cam = make_case(800, W, H, 2.0, 2, seed=W)
+    rep = compare_ex(scene, cam, 2, seed=22)
+    _report(f"extras_ragged[{W}x{H}]", rep)
+    _assert_ex(rep)
+
+
+@pytest.mark.parametrize("case", ["tiny_scales", "huge_scales", "opaque_and_transparent", "near_plane", "off_screen", "needle"])
+def test_extras_on_extreme_inputs(case):
+    """The six inputs of test_extreme_inputs_match_oracle with all three cotangents, to that test's bars."""
+    scene, cam = make_case(600, 144, 112, 2.0, 1, seed=41)
+    g = torch.Generator().manual_seed(43)
+    if case == "tiny_scales":
+        scene["scales"] = scene["scales"] * 1e-4
+    elif case == "huge_scales":
+        scene["scales"] = scene["scales"] * 40.0
+        scene["opacities"] = scene["opacities"] * 0.3
+    elif case == "opaque_and_transparent":
+        op = torch.rand(600, 1, generator=g)
+        scene["opacities"] = torch.where(op < 0.3, torch.zeros_like(op), torch.where(op > 0.7, torch.full_like(op, 0.9999), op))
+    elif case == "near_plane":
+        scene["means3D"] = scene["means3D"] * torch.tensor([1.0, 1.0, 0.05]) + torch.tensor([0.0, 0.0, -3.8])   # z_view ~ 0.2
+    elif case == "off_screen":
+        scene["means3D"] = scene["means3D"] + torch.tensor([2.6, -1.9, 0.0])
+    elif case == "needle":
+        scene["scales"] = scene["scales"] * torch.tensor([30.0, 0.02, 0.02])
+    rep = compare_ex(scene, cam, 1, seed=23)
+    _report(f"extras_extreme[{case}]", rep)
+    if case == "needle":
+        print(rep)
+        # parity.assert_ill_conditioned's rule: fp32 itself is only good to ~1e-2 here; at most 3x as far from fp64 as the fp32 reference
+        for k, ref in rep["oracle32_vs_64"].items():
+            if k in rep["grad_rel_fp64"]:
+                assert rep["grad_rel_fp64"][k] <= 3.0 * ref + 1e-4, (k, rep["grad_rel_fp64"][k], ref)
+    else:
+        _assert_ex(rep, grad_tol=3e-4)
+
+
+@pytest.mark.parametrize("setting", ["scale_modifier", "clamp_exact", "conic_exact"])
+def test_extras_with_other_settings(setting):
+    if setting == "scale_modifier":
+        scene, cam = make_case(1500, 96, 64, 2.0, 3, seed=3)
+        rep = compare_ex(scene, cam, 3, seed=24, scale_modifier=0.7)
+    elif setting == "clamp_exact":        # camera close to the cloud: Gaussians beyond 1.3 x the field of view reach the image
+        scene, cam = make_case(1500, 96, 64, 2.0, 1, seed=3, dist=2.5)
+        rep = compare_ex(scene, cam, 1, seed=24, clamp_grad="exact")
+    else:                                 # small splats: det(cov2D) near its floor, where the stock regulariser weighs most
+        scene, cam = make_case(2000, 96, 64, 0.25, 1, seed=9)
+        rep = compare_ex(scene, cam, 1, seed=24, conic_grad="exact")
+    _report(f"extras_settings[{setting}]", rep)
+    _assert_ex(rep)
+
+
+def test_extras_with_no_one_and_no_visible_gaussian():
+    from bags_raster.synth import look_at_origin_camera
+    cam = look_at_origin_camera(64, 48)
+    gi, gd, gw = cotangents(48, 64, 25)
+    # P = 0: no error, every gradient of its tensor's shape and zero
+    empty = dict(means3D=torch.zeros(0, 3), scales=torch.zeros(0, 3), rotations=torch.zeros(0, 4), opacities=torch.zeros(0, 1),
+                 shs=torch.zeros(0, 4, 3))
+    outs, grads = run_hip_ex(empty, cam, 1, gi, gd, gw)
+    assert float(outs[2].abs().max()) == 0.0 and float(outs[3].abs().max()) == 0.0
+    for k, v in grads.items():
+        assert v is None or float(v.abs().sum()) == 0.0, k
+        if v is not None and k in empty:
+            assert v.shape == empty[k].shape, k
+    # everything behind the camera: no instance, zero gradients
+    scene, _ = make_case(50, 64, 48, 1.0, 1, seed=1)
+    scene["means3D"] = scene["means3D"] + torch.tensor([0.0, 0.0, -10.0])
+    outs, grads = run_hip_ex(scene, cam, 1, gi, gd, gw)
+    assert int(outs[1].max()) == 0 and float(outs[3].abs().max()) == 0.0
+    assert all(v is None or float(v.abs().max()) == 0.0 for v in grads.values())
+    # a single Gaussian on the optical axis
+    one = dict(means3D=torch.zeros(1, 3), scales=torch.full((1, 3), 0.2), rotations=torch.tensor([[1.0, 0, 0, 0]]),
+               opacities=torch.tensor([[0.8]]), shs=torch.randn(1, 16, 3, generator=torch.Generator().manual_seed(2)) * 0.3)
+    rep = compare_ex(one, cam, 3, seed=25)
+    _report("extras_single", rep)
+    _assert_ex(rep)
+
+
+def test_background_does_not_reach_the_extra_gradients():
+    """depth and weights composite over background 0 whatever the image's background is: with the image out of the loss the
+    gradients with bg = (0.3, 0.7, 0.1) are those with bg = 0, bit for bit (tile_begin forms bg . dL/dimage from zeros)."""
+    scene, cam = make_case(1500, 96, 64, 2.0, 3, seed=3)
+    _, gd, gw = cotangents(64, 96, 26)
+    a = run_hip_ex(scene, cam, 3, None, gd, gw)[1]
+    b = run_hip_ex(scene, cam, 3, None, gd, gw, bg=torch.tensor([0.3, 0.7, 0.1]))[1]
+    assert float(a["means3D"].abs().sum()) > 0
+    _equal(a, b)
+
+
+def test_zero_extra_cotangents_on_a_band_scene():
+    """test_zero_extra_cotangents_leave_the_image_gradients on band_sparse: 7 of its 18 chunks run in one pass in the default kernel and in
+    two halves with the extras, so the image gradients agree to 1e-6 -- and NOT to the bit: the two-half branch, that test's reason for
+    its bar, did run."""
+    from scenes import rel_err
+    scene, cam, deg = path_scene("band_sparse")
+    gi, gd, gw = cotangents(48, 64, 27)
+    a = run_hip_ex(scene, cam, deg, gi, None, None, depth_weights_grad=False)[1]
+    b = run_hip_ex(scene, cam, deg, gi, torch.zeros_like(gd), torch.zeros_like(gw))[1]
+    same = True
+    for k in a:
+        if a[k] is not None:
+            assert rel_err(b[k], a[k]) <= 1e-6, (k, rel_err(b[k], a[k]))
+            same = same and torch.equal(a[k], b[k])
+    assert not same
 
 
 def test_depth_loss_alone_pulls_a_perturbed_pose_back():

@@ -971,7 +971,7 @@ def test_wide_chunks_that_overflow_a_wave_copy(tile_bounds):
     import numpy as np
     from oracle import raster_oracle as O
     from scenes import oracle_settings
-    from analysis_geometries import sub_masks, quadrant_groups
+    from parity import chunk_quadrant_counts
     scene, cam = make_case(420, 64, 48, 8.0, 1, seed=21)
     scene["opacities"] = scene["opacities"] * 0.2
     rep = compare(scene, cam, 1, tile_bounds=tile_bounds)
@@ -992,17 +992,11 @@ def test_wide_chunks_that_overflow_a_wave_copy(tile_bounds):
         pre = O.preprocess(scene["means3D"], torch.zeros(P, 3), torch.zeros(3), scene["shs"], None, scene["opacities"], scene["scales"],
                            scene["rotations"], None, s, torch.float32, None)
     xy, conic, op = pre.xy.numpy().astype(np.float64), pre.conic.numpy().astype(np.float64), pre.opacity.numpy().astype(np.float64)
-    pl, ranges, nc = v["point_list"].numpy().astype(np.int64), v["ranges"].numpy().astype(np.int64), v["n_contrib"].numpy()
-    overflowing = two_chunks = 0
-    for t in range(T):
-        ty, tx = divmod(t, 4)
-        hi0 = int(nc[ty * 16:ty * 16 + 16, tx * 16:tx * 16 + 16].max())          # the tile's deepest contributor: where its chunks start
-        two_chunks += hi0 > 240
-        ids = pl[ranges[t, 0] + max(0, hi0 - 224):ranges[t, 0] + hi0]            # (at least) the first, deepest chunk of either geometry
-        n = ids.size
-        m = sub_masks(xy[ids, 0], xy[ids, 1], conic[ids, 0], conic[ids, 1], conic[ids, 2], op[ids], np.full(n, tx * 16.0), np.full(n, ty * 16.0), 4, 4)
-        overflowing += max(int(m[:, q].any(1).sum()) for q in quadrant_groups(4, 4)) > 176
-    assert overflowing >= 6 and two_chunks >= 3, (overflowing, two_chunks)
+    # (at least) the first, deepest chunk of either geometry: 224 consecutive list positions from the tile's deepest contributor
+    chunks = chunk_quadrant_counts(v["point_list"].numpy(), v["ranges"].numpy(), v["n_contrib"].numpy(), xy, conic, op, 4, 224)
+    overflowing = sum(bool(c) and c[0][1] > 176 for c in chunks.values())
+    two_chunks = sum(sum(n for n, _ in c) > 240 for c in chunks.values())
+    assert len(chunks) == T and overflowing >= 6 and two_chunks >= 3, (overflowing, two_chunks)
 
 
 def test_conic_backward_semantic():
