@@ -15,6 +15,7 @@ from .bilagrid import BilateralGridBank, apply_bilagrid, bilagrid_torch, bilagri
 from .depth_prior import DepthPriorBank, depth_prior_loss, depth_prior_loss_torch
 from .normal_prior import normal_prior_loss, normal_prior_loss_torch, depth_to_normal, depth_to_normal_torch, pinhole_of
 from .correspondence import correspondence_loss, correspondence_loss_torch, reproject_pixels, reproject_pixels_torch
+from .warp import warp_image, warp_image_torch, warp_loss, warp_loss_torch
 from .io import save_ply, load_ply, save_checkpoint, load_checkpoint, save_exposure_json, load_exposure_json
 from .optim import GaussianAdam
 from .pose_bank import PoseBank, PoseAdam
@@ -32,4 +33,5 @@ __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gau
            "filter_3D", "filter_3D_torch", "filtered_activations_torch",
            "DepthPriorBank", "depth_prior_loss", "depth_prior_loss_torch",
            "normal_prior_loss", "normal_prior_loss_torch", "depth_to_normal", "depth_to_normal_torch", "pinhole_of",
-           "correspondence_loss", "correspondence_loss_torch", "reproject_pixels", "reproject_pixels_torch"]
+           "correspondence_loss", "correspondence_loss_torch", "reproject_pixels", "reproject_pixels_torch",
+           "warp_loss", "warp_loss_torch", "warp_image", "warp_image_torch"]

@@ -239,6 +239,15 @@ class BagsCorrespondence(C.Structure):      # the source maps, matches, view mat
                 ("conf", c_fp * MAX_POSE_ROWS), ("view_src", c_fp * MAX_POSE_ROWS), ("view_dst", c_fp * MAX_POSE_ROWS)]
 
 
+class BagsWarp(C.Structure):                # the source maps, colours, target images and maps, view matrices and pinholes of one call's ordered pairs (csrc/warp.hip); None = NULL
+    _fields_ = [("H", C.c_int32), ("W", C.c_int32), ("n_rows", C.c_int32), ("min_weight", C.c_float), ("min_depth", C.c_double),
+                ("C", C.c_int32), ("H_dst", C.c_int32), ("W_dst", C.c_int32), ("reserved", C.c_int32), ("eps", C.c_double),
+                ("occlusion", C.c_double), ("pinhole_src", (C.c_double * 4) * MAX_POSE_ROWS), ("pinhole_dst", (C.c_double * 4) * MAX_POSE_ROWS),
+                ("depth", c_fp * MAX_POSE_ROWS), ("weights", c_fp * MAX_POSE_ROWS), ("conf", c_fp * MAX_POSE_ROWS),
+                ("view_src", c_fp * MAX_POSE_ROWS), ("view_dst", c_fp * MAX_POSE_ROWS), ("color_src", c_fp * MAX_POSE_ROWS),
+                ("image_dst", c_fp * MAX_POSE_ROWS), ("depth_dst", c_fp * MAX_POSE_ROWS), ("weights_dst", c_fp * MAX_POSE_ROWS)]
+
+
 SYMBOLS = {    "bags_abi_version": (C.c_int, []),
     "bags_build_info": (C.c_char_p, []),
     "bags_last_error": (C.c_char_p, []),
@@ -339,6 +348,11 @@ SYMBOLS = {    "bags_abi_version": (C.c_int, []),
     "bags_correspondence_backward": (C.c_int, [C.POINTER(BagsCorrespondence), c_fp, c_fp, C.c_void_p, C.c_size_t, C.POINTER(c_fp), C.POINTER(c_fp),
                                                C.POINTER(c_fp), C.POINTER(c_fp), C.c_void_p]),
     "bags_reproject_pixels": (C.c_int, [C.POINTER(BagsCorrespondence), C.c_int32, C.c_int32, c_fp, C.c_void_p, C.c_void_p]),
+    "bags_warp_workspace_size": (C.c_size_t, [C.c_int32] * 3),
+    "bags_warp_forward": (C.c_int, [C.POINTER(BagsWarp), C.c_void_p, C.c_size_t, c_fp, c_fp, c_fp, C.c_void_p]),
+    "bags_warp_backward": (C.c_int, [C.POINTER(BagsWarp), c_fp, c_fp, C.c_void_p, C.c_size_t, C.POINTER(c_fp), C.POINTER(c_fp), C.POINTER(c_fp),
+                                     C.POINTER(c_fp), C.c_void_p]),
+    "bags_warp_image": (C.c_int, [C.POINTER(BagsWarp), c_fp, C.c_void_p, C.c_void_p]),
     "bags_filter3d_workspace_size": (C.c_size_t, [C.c_int32]),
     "bags_filter3d_compute": (C.c_int, [c_fp, C.c_int32, c_fp, c_fp, c_fp, C.c_int32, C.c_float, C.c_void_p, C.c_size_t, c_fp, C.c_void_p]),
     "bags_activations_filtered_forward": (C.c_int, [C.POINTER(BagsRawGaussians), c_fp] + [C.c_void_p] * 5),

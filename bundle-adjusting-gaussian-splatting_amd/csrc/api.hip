@@ -1778,4 +1778,92 @@ int bags_reproject_pixels(const BagsCorrespondence* a, int32_t H_dst, int32_t W_
     return BAGS_OK;
 }
 
+// ---- warp.hip: the rows of correspondence.hip, per pair and chunk of the SOURCE image, carved by carve_correspondence
+size_t bags_warp_workspace_size(int32_t n_rows, int32_t H, int32_t W)
+{
+    if (n_rows < 1 || n_rows > BAGS_MAX_POSE_ROWS || !correspondence_image_ok(H, W)) return 0;
+    return carve_correspondence(nullptr, n_rows, H, W, nullptr);
+}
+
+static int check_warp(const char* op, const BagsWarp* a, bool colors)
+{
+    if (!a) return fail(BAGS_ERR_ARG, "%s: null struct", op);
+    if (a->n_rows < 1 || a->n_rows > BAGS_MAX_POSE_ROWS) return fail(BAGS_ERR_ARG, "%s: n_rows %d not in 1..%d", op, a->n_rows, BAGS_MAX_POSE_ROWS);
+    if (a->H < 1 || a->W < 1) return fail(BAGS_ERR_ARG, "%s: empty image %dx%d", op, a->W, a->H);
+    if (!correspondence_image_ok(a->H, a->W)) return fail(BAGS_ERR_ARG, "%s: image %dx%d has 2^31 pixels or more", op, a->W, a->H);
+    if (a->H_dst < 1 || a->W_dst < 1) return fail(BAGS_ERR_ARG, "%s: empty target image %dx%d", op, a->W_dst, a->H_dst);
+    if (!correspondence_image_ok(a->H_dst, a->W_dst))
+        return fail(BAGS_ERR_ARG, "%s: target image %dx%d has 2^31 pixels or more", op, a->W_dst, a->H_dst);
+    if (a->C != 1 && a->C != 3) return fail(BAGS_ERR_ARG, "%s: C = %d channels, must be 1 or 3", op, a->C);
+    if (!(a->min_weight > 0.0f) || std::isinf(a->min_weight)) return fail(BAGS_ERR_ARG, "%s: min_weight must be a positive number", op);
+    if (!(a->min_depth > 0.0) || std::isinf(a->min_depth)) return fail(BAGS_ERR_ARG, "%s: min_depth must be a positive number", op);
+    if (!(a->eps > 0.0) || std::isinf(a->eps)) return fail(BAGS_ERR_ARG, "%s: eps must be a positive number", op);
+    if (!(a->occlusion > 0.0) || std::isinf(a->occlusion)) return fail(BAGS_ERR_ARG, "%s: occlusion must be a positive number", op);
+    for (int k = 0; k < a->n_rows; ++k) {
+        if (const int rc = check_pinhole(op, k, a->pinhole_src[k])) return rc;
+        if (const int rc = check_pinhole(op, k, a->pinhole_dst[k])) return rc;
+        if (!a->depth[k]) return fail(BAGS_ERR_ARG, "%s: null depth[%d]", op, k);
+        if (!a->weights[k]) return fail(BAGS_ERR_ARG, "%s: null weights[%d]", op, k);
+        if (!a->view_src[k] || !a->view_dst[k]) return fail(BAGS_ERR_ARG, "%s: null view_src[%d] / view_dst[%d]", op, k, k);
+        if (colors && !a->color_src[k]) return fail(BAGS_ERR_ARG, "%s: null color_src[%d]", op, k);
+        if (!a->image_dst[k]) return fail(BAGS_ERR_ARG, "%s: null image_dst[%d]", op, k);
+        if (!a->depth_dst[k] != !a->weights_dst[k])
+            return fail(BAGS_ERR_ARG, "%s: depth_dst[%d] and weights_dst[%d] must be given together or not at all", op, k, k);
+    }
+    return BAGS_OK;
+}
+
+static int check_warp_workspace(const char* op, const BagsWarp* a, void* workspace, size_t workspace_bytes)
+{
+    const size_t need = bags_warp_workspace_size(a->n_rows, a->H, a->W);
+    if (!workspace || workspace_bytes < need)
+        return fail(BAGS_ERR_ARG, "%s: needs a workspace of %zu bytes (got %zu)", op, need, workspace ? workspace_bytes : (size_t)0);
+    if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return fail(BAGS_ERR_ARG, "%s: the workspace is not 16-byte aligned", op);
+    return BAGS_OK;
+}
+
+int bags_warp_forward(const BagsWarp* a, void* workspace, size_t workspace_bytes, float* loss, float* count, double* stats, void* stream)
+{
+    if (const int rc = check_warp("warp_forward", a, true)) return rc;
+    if (!loss || !count || !stats) return fail(BAGS_ERR_ARG, "warp_forward: null loss / count / stats");
+    if (const int rc = check_warp_workspace("warp_forward", a, workspace, workspace_bytes)) return rc;
+    if (reinterpret_cast<uintptr_t>(stats) % 8 != 0) return fail(BAGS_ERR_ARG, "warp_forward: stats is not 8-byte aligned");
+    double* partials = nullptr;
+    carve_correspondence(workspace, a->n_rows, a->H, a->W, &partials);
+    HIP_TRY(launch_warp_fwd(*a, partials, loss, count, stats, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
+int bags_warp_backward(const BagsWarp* a, const double* stats, const float* g_loss, void* workspace, size_t workspace_bytes,
+                       float* const g_depth[BAGS_MAX_POSE_ROWS], float* const g_weights[BAGS_MAX_POSE_ROWS],
+                       float* const g_view_src[BAGS_MAX_POSE_ROWS], float* const g_view_dst[BAGS_MAX_POSE_ROWS], void* stream)
+{
+    if (const int rc = check_warp("warp_backward", a, true)) return rc;
+    if (!stats) return fail(BAGS_ERR_ARG, "warp_backward: null stats");
+    if (reinterpret_cast<uintptr_t>(stats) % 8 != 0) return fail(BAGS_ERR_ARG, "warp_backward: stats is not 8-byte aligned");
+    if (!g_loss) return fail(BAGS_ERR_ARG, "warp_backward: null g_loss");
+    bool any_map = false, any_view = false;
+    for (int k = 0; k < a->n_rows; ++k) {
+        any_map |= (g_depth && g_depth[k]) || (g_weights && g_weights[k]);
+        any_view |= (g_view_src && g_view_src[k]) || (g_view_dst && g_view_dst[k]);
+    }
+    if (!any_map && !any_view) return BAGS_OK;
+    double* sums = nullptr;
+    if (any_view) {
+        if (const int rc = check_warp_workspace("warp_backward", a, workspace, workspace_bytes)) return rc;
+        carve_correspondence(workspace, a->n_rows, a->H, a->W, &sums);
+    }
+    HIP_TRY(launch_warp_bwd(*a, stats, g_loss, sums, g_depth, g_weights, g_view_src, g_view_dst, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
+int bags_warp_image(const BagsWarp* a, float* out, uint8_t* valid, void* stream)
+{
+    if (const int rc = check_warp("warp_image", a, false)) return rc;
+    if (a->n_rows != 1) return fail(BAGS_ERR_ARG, "warp_image: one pair per call (n_rows = %d)", a->n_rows);
+    if (!out || !valid) return fail(BAGS_ERR_ARG, "warp_image: null out / valid");
+    HIP_TRY(launch_warp_image(*a, out, valid, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
 }  // extern "C"

@@ -365,6 +365,12 @@ hipError_t launch_correspondence_fwd(const BagsCorrespondence& a, double* partia
 hipError_t launch_correspondence_bwd(const BagsCorrespondence& a, const double* stats, const float* g_loss, double* sums, float* const* g_depth,
                                      float* const* g_weights, float* const* g_view_src, float* const* g_view_dst, hipStream_t st);
 hipError_t launch_reproject_pixels(const BagsCorrespondence& a, int H_dst, int W_dst, float* proj, uint8_t* valid, hipStream_t st);
+// warp.hip: the photometric reprojection of a view's pixels into another view's image on the ordered pairs of a step; partials and
+// stats as correspondence.hip's, with the same correspondence_chunks(H, W) rows per pair (carve_correspondence in api.hip)
+hipError_t launch_warp_fwd(const BagsWarp& a, double* partials, float* loss, float* count, double* stats, hipStream_t st);
+hipError_t launch_warp_bwd(const BagsWarp& a, const double* stats, const float* g_loss, double* sums, float* const* g_depth, float* const* g_weights,
+                           float* const* g_view_src, float* const* g_view_dst, hipStream_t st);
+hipError_t launch_warp_image(const BagsWarp& a, float* out, uint8_t* valid, hipStream_t st);
 hipError_t launch_appearance_fwd(const BagsAppearance& a, hipStream_t st);
 hipError_t launch_appearance_bwd(const BagsAppearance& a, const float* const* g_out, double* partials, float* const* g_image, float* g_table,
                                  hipStream_t st);

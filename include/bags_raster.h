@@ -962,6 +962,65 @@ int    bags_correspondence_backward(const BagsCorrespondence* args, const double
 int    bags_reproject_pixels(const BagsCorrespondence* args, int32_t H_dst, int32_t W_dst, float* proj /* (2,H,W) */,
                              uint8_t* valid /* (H,W) */, void* stream);
 
+/* The photometric reprojection (warping) loss on the rasterizer's maps (csrc/warp.hip): a pixel of the source view is un-projected
+ * with the rendered depth, carried into the target view with the two view matrices, the target view's image is sampled there,
+ * bilinearly, and the sampled colour is held to the colour of the pixel (CF-3DGS, Nope-NeRF, the self-supervised-depth family).
+ * Conventions, solid, z, M, c, x_i, x_j and proj are the correspondence loss's above, word for word.  Per ordered pair: source maps
+ * D, A (H,W) float32, view matrices Vi, Vj (4,4) ON THE DEVICE, color_src (C,H,W) = the colour each source pixel is held to,
+ * image_dst (C,H_dst,W_dst) = the image of view j that is sampled, an optional confidence conf >= 0 (H,W) (NULL: 1), optional target
+ * maps depth_dst, weights_dst (H_dst,W_dst) for the occlusion test (both or neither), host pinholes of both sides.  C is 1 or 3.
+ *     inside  = 0 <= proj.x <= W_dst - 1 and 0 <= proj.y <= H_dst - 1            (all four taps exist; pixel centres at whole numbers)
+ *     x0 = floor(proj.x)  y0 = floor(proj.y)  ax = proj.x - x0  ay = proj.y - y0  x1 = min(x0 + 1, W_dst - 1)  y1 = min(y0 + 1, H_dst - 1)
+ *     S_c = (1-ay) ((1-ax) T_c[y0,x0] + ax T_c[y0,x1]) + ay ((1-ax) T_c[y1,x0] + ax T_c[y1,x1])       T = image_dst, in float64
+ *     dS_c/dproj = ((1-ay)(T_c[y0,x1]-T_c[y0,x0]) + ay (T_c[y1,x1]-T_c[y1,x0]),  (1-ax)(T_c[y1,x0]-T_c[y0,x0]) + ax (T_c[y1,x1]-T_c[y0,x1]))
+ *     visible = no target maps given, or at the nearest target pixel (floor(proj + 0.5)), with z_t = D_t / A_t (one float32 division):
+ *               A_t >= min_weight and D_t > 0 and |x_j.z - z_t| <= occlusion * z_t
+ *     valid   = solid and det(Ai) usable and x_j.z >= min_depth and conf > 0 and inside and visible and every S_c, color_src_c finite
+ *     r_c = S_c - color_src_c ;  rho = (1/C) sum_c (sqrt(r_c^2 + eps^2) - eps)                       (Charbonnier: L1 as eps -> 0)
+ *     w = conf on valid pixels ;  cnt = sum w ;  L_k = sum w rho / cnt
+ *     dL/dproj = s_k (w / cnt) (1/C) sum_c r_c / sqrt(r_c^2 + eps^2) * dS_c/dproj                    (s_k the cotangent)
+ * From dL/dproj on, the backward is the correspondence loss's.  cnt <= 0, or det(Ai) zero or not finite: L_k = 0 and every gradient an
+ * exact zero, never NaN.  Validity is a decision, not differentiated through (the bilinear cell and the occlusion test included);
+ * invalid pixels get exact-zero gradients.  NO gradient to image_dst, color_src, the target maps, conf or the pinholes: a gradient to
+ * the sampled image is a scatter, and this library writes no gradient with atomics.
+ * forward / backward: launches, workspace rows (BAGS_CORRESPONDENCE_CHUNK pixels per workgroup), stats (n_rows,2), the NULL rules of
+ *           the four gradient tables and the bitwise guarantees are those of bags_correspondence_forward / _backward.
+ * bags_warp_image: one launch, the first pair of the struct alone (n_rows == 1; conf and color_src are not read): out (C,H,W) float32
+ *           = S_c where the pixel is solid, x_j.z >= min_depth, inside, visible and every S_c finite, zeros elsewhere; valid (H,W)
+ *           uint8 marks those pixels.
+ * workspace: bags_warp_workspace_size bytes (0 for invalid arguments), 16-byte aligned, no initialisation; one size serves the forward
+ *           and the backward.
+ * min_weight and min_depth must be positive and finite, eps and occlusion too.  H * W and H_dst * W_dst must be below 2^31. */
+typedef struct BagsWarp {
+    int32_t H, W;
+    int32_t n_rows;                          /* pairs of the call, 1..BAGS_MAX_POSE_ROWS */
+    float min_weight;
+    double min_depth;
+    int32_t C;                               /* channels of color_src and image_dst: 1 or 3 */
+    int32_t H_dst, W_dst;                    /* one target size per call; may differ from H, W */
+    int32_t reserved;                        /* 0 */
+    double eps;
+    double occlusion;
+    double pinhole_src[BAGS_MAX_POSE_ROWS][4];   /* (fx, fy, cx, cy) in pixels per pair; fx, fy non-zero and finite */
+    double pinhole_dst[BAGS_MAX_POSE_ROWS][4];
+    const float* depth[BAGS_MAX_POSE_ROWS];  /* (H,W) each, the first n_rows given: the SOURCE view's maps */
+    const float* weights[BAGS_MAX_POSE_ROWS];
+    const float* conf[BAGS_MAX_POSE_ROWS];   /* any of them NULL: every pixel weighs 1 */
+    const float* view_src[BAGS_MAX_POSE_ROWS];   /* (4,4) each, on the device */
+    const float* view_dst[BAGS_MAX_POSE_ROWS];
+    const float* color_src[BAGS_MAX_POSE_ROWS];  /* (C,H,W) each */
+    const float* image_dst[BAGS_MAX_POSE_ROWS];  /* (C,H_dst,W_dst) each */
+    const float* depth_dst[BAGS_MAX_POSE_ROWS];  /* (H_dst,W_dst) each; NULL per pair, together with weights_dst: no occlusion test */
+    const float* weights_dst[BAGS_MAX_POSE_ROWS];
+} BagsWarp;
+size_t bags_warp_workspace_size(int32_t n_rows, int32_t H, int32_t W);
+int    bags_warp_forward(const BagsWarp* args, void* workspace, size_t workspace_bytes, float* loss /* (n_rows) */,
+                         float* count /* (n_rows) */, double* stats /* (n_rows,2) */, void* stream);
+int    bags_warp_backward(const BagsWarp* args, const double* stats, const float* g_loss /* (n_rows) */, void* workspace,
+                          size_t workspace_bytes, float* const g_depth[BAGS_MAX_POSE_ROWS], float* const g_weights[BAGS_MAX_POSE_ROWS],
+                          float* const g_view_src[BAGS_MAX_POSE_ROWS], float* const g_view_dst[BAGS_MAX_POSE_ROWS], void* stream);
+int    bags_warp_image(const BagsWarp* args, float* out /* (C,H,W) */, uint8_t* valid /* (H,W) */, void* stream);
+
 /* Per-image bilateral-grid colour (csrc/bilagrid.hip): gsplat's lib_bilagrid slice-and-apply on the rendered image, behind the
  * appearance step and in front of the loss, and the total variation of the grids.  The grids of all N training images are one
  * (N,12,L,Gy,Gx) device tensor in gsplat's layout: coefficient k = 4*c + j of a vertex is entry [c][j] of a 3x4 affine matrix; the
