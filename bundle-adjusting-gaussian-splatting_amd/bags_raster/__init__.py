@@ -5,7 +5,7 @@ Mirrors the operator API of the reference's ``diff_gaussian_rasterization`` pack
 """
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, rasterize_gaussians, debug_views
 
-from .render import render, render_views, PipelineParams
+from .render import render, render_views, render_normals, PipelineParams
 from .gaussians import GaussianBag, eval_sh, sh_colors, sh_colors_views
 from .mcmc import compute_relocation, compute_relocation_torch, relocation_binoms
 from .antialias import antialias_opacity, antialias_opacity_torch
@@ -16,6 +16,8 @@ from .depth_prior import DepthPriorBank, depth_prior_loss, depth_prior_loss_torc
 from .normal_prior import normal_prior_loss, normal_prior_loss_torch, depth_to_normal, depth_to_normal_torch, pinhole_of
 from .correspondence import correspondence_loss, correspondence_loss_torch, reproject_pixels, reproject_pixels_torch
 from .warp import warp_image, warp_image_torch, warp_loss, warp_loss_torch
+from .gaussian_normals import gaussian_normals, gaussian_normals_views, gaussian_normals_torch, gaussian_normals_views_torch
+from .normal_map import normal_map_loss, normal_map_loss_torch
 from .io import save_ply, load_ply, save_checkpoint, load_checkpoint, save_exposure_json, load_exposure_json
 from .optim import GaussianAdam
 from .pose_bank import PoseBank, PoseAdam
@@ -34,4 +36,6 @@ __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gau
            "DepthPriorBank", "depth_prior_loss", "depth_prior_loss_torch",
            "normal_prior_loss", "normal_prior_loss_torch", "depth_to_normal", "depth_to_normal_torch", "pinhole_of",
            "correspondence_loss", "correspondence_loss_torch", "reproject_pixels", "reproject_pixels_torch",
-           "warp_loss", "warp_loss_torch", "warp_image", "warp_image_torch"]
+           "warp_loss", "warp_loss_torch", "warp_image", "warp_image_torch",
+           "gaussian_normals", "gaussian_normals_views", "gaussian_normals_torch", "gaussian_normals_views_torch", "render_normals",
+           "normal_map_loss", "normal_map_loss_torch"]

@@ -248,6 +248,20 @@ class BagsWarp(C.Structure):                # the source maps, colours, target i
                 ("image_dst", c_fp * MAX_POSE_ROWS), ("depth_dst", c_fp * MAX_POSE_ROWS), ("weights_dst", c_fp * MAX_POSE_ROWS)]
 
 
+class BagsGaussianNormals(C.Structure):    # the Gaussians and the V <= MAX_SH_VIEWS view matrices of one call (csrc/gaussian_normals.hip)
+    _fields_ = [("P", C.c_int32), ("V", C.c_int32), ("rotations", c_fp), ("scales", c_fp), ("means3D", c_fp),
+                ("viewmatrix", c_fp * MAX_SH_VIEWS)]
+
+
+NORMAL_MAP_STATS = 2                        # include/bags_raster.h: BAGS_NORMAL_MAP_STATS
+
+
+class BagsNormalMap(C.Structure):           # the normal / weights / target / mask maps of one step's views (csrc/normal_map.hip); None = NULL
+    _fields_ = [("mode", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("n_rows", C.c_int32), ("min_weight", C.c_float),
+                ("min_norm", C.c_float), ("normal", c_fp * MAX_POSE_ROWS), ("weights", c_fp * MAX_POSE_ROWS),
+                ("prior", c_fp * MAX_POSE_ROWS), ("mask", c_fp * MAX_POSE_ROWS)]
+
+
 SYMBOLS = {    "bags_abi_version": (C.c_int, []),
     "bags_build_info": (C.c_char_p, []),
     "bags_last_error": (C.c_char_p, []),
@@ -353,6 +367,13 @@ SYMBOLS = {    "bags_abi_version": (C.c_int, []),
     "bags_warp_backward": (C.c_int, [C.POINTER(BagsWarp), c_fp, c_fp, C.c_void_p, C.c_size_t, C.POINTER(c_fp), C.POINTER(c_fp), C.POINTER(c_fp),
                                      C.POINTER(c_fp), C.c_void_p]),
     "bags_warp_image": (C.c_int, [C.POINTER(BagsWarp), c_fp, C.c_void_p, C.c_void_p]),
+    "bags_gaussian_normals_forward": (C.c_int, [C.POINTER(BagsGaussianNormals), C.POINTER(c_fp), C.c_void_p]),
+    "bags_gaussian_normals_workspace_size": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "bags_gaussian_normals_backward": (C.c_int, [C.POINTER(BagsGaussianNormals), C.POINTER(c_fp), C.c_void_p, C.c_size_t, c_fp, C.POINTER(c_fp),
+                                                 C.c_void_p]),
+    "bags_normal_map_workspace_size": (C.c_size_t, [C.c_int32] * 3),
+    "bags_normal_map_forward": (C.c_int, [C.POINTER(BagsNormalMap), C.c_void_p, C.c_size_t, c_fp, c_fp, c_fp, C.c_void_p]),
+    "bags_normal_map_backward": (C.c_int, [C.POINTER(BagsNormalMap), c_fp, c_fp, C.POINTER(c_fp), C.c_void_p]),
     "bags_filter3d_workspace_size": (C.c_size_t, [C.c_int32]),
     "bags_filter3d_compute": (C.c_int, [c_fp, C.c_int32, c_fp, c_fp, c_fp, C.c_int32, C.c_float, C.c_void_p, C.c_size_t, c_fp, C.c_void_p]),
     "bags_activations_filtered_forward": (C.c_int, [C.POINTER(BagsRawGaussians), c_fp] + [C.c_void_p] * 5),

@@ -16,6 +16,9 @@ arguments, same choice of covariance path (``pipe.compute_cov3D_python``) and co
 ``render_views()`` is ``render()`` for the V cameras of one step: the same dictionaries, the activations once, on the fused
 colour path one ``bags_raster.sh_colors_views`` call for the colours of all the cameras, and for the cameras of a
 ``bags_raster.PoseBank`` one chain launch each way for all of them.
+
+``render_normals()`` is the second pass of the normal-supervision recipes: the normal of every Gaussian
+(``bags_raster.gaussian_normals_views``) splatted through the ``override_color`` path over a zero background.
 """
 from __future__ import annotations
 
@@ -26,6 +29,7 @@ from typing import Optional
 import torch
 
 from ._lib import MAX_POSE_ROWS, MAX_SH_VIEWS
+from .gaussian_normals import gaussian_normals_views
 from .gaussians import eval_sh, sh_colors, sh_colors_views
 from .pose_bank import PoseBankCamera
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer
@@ -63,8 +67,9 @@ def _python_colors(pc, xyz, feats, campos: torch.Tensor, mlp_color) -> torch.Ten
     return rgb + mlp_color
 
 
-def _activate(pc, pipe, hybrid: bool, override_color) -> SimpleNamespace:
-    """What a call needs from the Gaussian set, whichever camera it is for: the colour path and the activated parameters."""
+def _activate(pc, pipe, hybrid: bool, override_color, features: bool = True) -> SimpleNamespace:
+    """What a call needs from the Gaussian set, whichever camera it is for: the colour path and the activated parameters.
+    ``features=False`` (``render_normals``): no colour is evaluated, so the feature tensor is not formed."""
     # activations: one fused launch when the container offers it (GaussianBag on a GPU), else the reference's properties
     # rasterizer-side SH colours and, on a GPU, the Python-side ones (bags_raster.sh_colors): the two feature parameters go to the
     # kernel as they are stored (shs = features_dc, shs_rest = features_rest), without get_features' torch.cat; every other colour
@@ -78,10 +83,10 @@ def _activate(pc, pipe, hybrid: bool, override_color) -> SimpleNamespace:
     split = ((raster_sh or fused_colors) and torch.is_tensor(rest) and torch.is_tensor(getattr(pc, "_features_dc", None))
              and rest.dim() == 3 and rest.shape[1] >= 1 and rest.is_cuda)
     if hasattr(pc, "activated"):                               # GaussianBag: one fused launch each way
-        xyz, features, opacity, scaling, rotation = pc.activated(features=not split)
+        xyz, features, opacity, scaling, rotation = pc.activated(features=features and not split)
     else:                                                      # any container with the reference's properties (GaussianModel)
         xyz, opacity, scaling, rotation = pc.get_xyz, pc.get_opacity, pc.get_scaling, pc.get_rotation
-        features = None if split else pc.get_features
+        features = None if (split or not features) else pc.get_features
     return SimpleNamespace(fused_colors=fused_colors, split=split, xyz=xyz, features=features, opacity=opacity, scaling=scaling,
                            rotation=rotation)
 
@@ -99,15 +104,16 @@ def _camera_chain(viewpoint_camera, global_alignment):
 
 
 def _rasterize_view(viewpoint_camera, pc, pipe, bg_color, mlp_color, shift_factors, hybrid, scaling_modifier, override_color, iteration,
-                    depth_key, depth_weights_grad, act, matrices, fused_rgb):
+                    depth_key, depth_weights_grad, act, matrices, fused_rgb, sinks=True):
     """One camera's rasterizer call and the returned dictionary.  ``act``: ``_activate``'s result; ``matrices``: ``_camera_chain``'s;
-    ``fused_rgb``: this view's ``sh_colors`` / ``sh_colors_views`` output where ``act.fused_colors``, else None."""
+    ``fused_rgb``: this view's ``sh_colors`` / ``sh_colors_views`` output where ``act.fused_colors``, else None.  ``sinks=False``
+    (``render_normals``): no screen-space gradient sinks are made, and the two entries are None."""
     xyz = act.xyz
     # zero tensors whose .grad receives the screen-space gradients (:37-44)
     # (leaves: `.grad` is populated as with the reference's `zeros + 0` / retain_grad() pair, without the two adds and the two
     # 6 MB gradient copies that pair costs per call)
-    screenspace_points = torch.zeros_like(xyz, requires_grad=True)
-    screenspace_points_densify = torch.zeros_like(xyz, requires_grad=True)
+    screenspace_points = torch.zeros_like(xyz, requires_grad=True) if sinks else None
+    screenspace_points_densify = torch.zeros_like(xyz, requires_grad=True) if sinks else None
     viewmatrix, projmatrix, intrinsic, campos = matrices
 
     raster_settings = GaussianRasterizationSettings(
@@ -234,3 +240,39 @@ def render_views(cameras, pc, pipe, bg_color: torch.Tensor, mlp_color, shift_fac
             fused_rgb = [sh_colors(pc.active_sh_degree, shs, act.xyz, m[3], shs_rest=rest) for m in matrices]
     return [_rasterize_view(cam, pc, pipe, bg_color, mlp_color, shift_factors, hybrid, scaling_modifier, override_color, iteration,
                             depth_key, depth_weights_grad, act, m, rgb) for cam, m, rgb in zip(cameras, matrices, fused_rgb)]
+
+
+def render_normals(cameras, pc, pipe, shift_factors, scaling_modifier: float = 1.0, global_alignment=None, depth_key: str = "z",
+                   depth_weights_grad: bool = False):
+    """The rendered normal map of one camera (a dictionary) or of a list of cameras (a list of dictionaries): what ``render()`` gives
+    with ``override_color = gaussian_normals(...)`` and a zero background.  ``"normal"`` is ``(3,H,W)``, ``sum_i w_i n_i`` in the
+    camera frame of the operator's view space (x right, y down, z forward; a wall seen head-on has ``n_z < 0``, the convention of
+    ``normal_prior_loss``); ``"weights"``, ``"depth"`` and ``"radii"`` are the operator's, the bits a ``render()`` call on the same
+    inputs gives.  There are no densification sinks in it: those belong to the colour pass.  A precomputed colour reaches the blend
+    unclamped, so the negative components arrive as they are.
+
+    The activations are evaluated once and the camera chain as ``render_views`` does (the cameras of one ``PoseBank``: one chain
+    launch each way per 16); the normals of up to 16 cameras come from one ``gaussian_normals_views`` call.  The decision input of
+    ``gaussian_normals`` -- which axis is the shortest -- is ``pc._scaling`` as stored where the container has it (any monotone
+    function of the scales serves), else the activated scaling: under a 3D filter much larger than a scale, ``sqrt(s^2 + f^2)`` can
+    round to a tie in float32.  The gradient reaches the rotations (through the normals and through the operator), the positions,
+    opacities and scales (through the operator) and the pose (both ways).  The pass costs one operator call per camera."""
+    single = not isinstance(cameras, (list, tuple))
+    cams = [cameras] if single else list(cameras)
+    act = _activate(pc, pipe, hybrid=True, override_color="normals", features=False)      # (an override colour: no SH path, no feature tensor)
+    matrices = _camera_chains(cams, global_alignment)
+    order = getattr(pc, "_scaling", None)
+    if not (torch.is_tensor(order) and tuple(order.shape) == tuple(act.scaling.shape)):
+        order = act.scaling
+    dev = act.xyz.device
+    zero3 = _ZERO3.get(dev)
+    if zero3 is None:
+        zero3 = _ZERO3[dev] = torch.zeros(3, device=dev)
+    out = []
+    for b in range(0, len(cams), MAX_SH_VIEWS):
+        normals = gaussian_normals_views(act.rotation, order.detach(), act.xyz.detach(), [m[0] for m in matrices[b:b + MAX_SH_VIEWS]])
+        for cam, m, n in zip(cams[b:b + MAX_SH_VIEWS], matrices[b:b + MAX_SH_VIEWS], normals):
+            r = _rasterize_view(cam, pc, pipe, zero3, 0, shift_factors, True, scaling_modifier, n, None, depth_key, depth_weights_grad, act,
+                                m, None, sinks=False)
+            out.append({"normal": r["render"], "weights": r["weights"], "depth": r["depth"], "radii": r["radii"]})
+    return out[0] if single else out

@@ -1866,4 +1866,126 @@ int bags_warp_image(const BagsWarp* a, float* out, uint8_t* valid, void* stream)
     return BAGS_OK;
 }
 
+// ---- gaussian_normals.hip: one row of 9 V view-matrix sums per workgroup
+static size_t carve_gaussian_normals(void* base, int P, int V, float** slab)
+{
+    Carver c(base);
+    float* s = c.take<float>((size_t)gaussian_normals_blocks(P) * GN_SLAB_PER_VIEW * V);
+    if (slab) *slab = s;
+    return c.used();
+}
+
+size_t bags_gaussian_normals_workspace_size(int32_t P, int32_t V)
+{
+    if (P < 0 || V < 1 || V > BAGS_MAX_SH_VIEWS) return 0;
+    return carve_gaussian_normals(nullptr, P, V, nullptr) + BASE_SLACK;
+}
+
+static int check_gaussian_normals(const char* op, const BagsGaussianNormals* a)
+{
+    if (!a) return fail(BAGS_ERR_ARG, "%s: null struct", op);
+    if (a->P < 0) return fail(BAGS_ERR_ARG, "%s: P < 0 (got %d)", op, a->P);
+    if (a->V < 1 || a->V > BAGS_MAX_SH_VIEWS)
+        return fail(BAGS_ERR_ARG, "%s: V %d not in 1..%d (more views: one call per chunk)", op, a->V, BAGS_MAX_SH_VIEWS);
+    if (a->P == 0) return BAGS_OK;                 // an empty set has no rows to point to: the pointers are not looked at
+    if (!a->rotations || !a->scales || !a->means3D) return fail(BAGS_ERR_ARG, "%s: NULL rotations / scales / means3D", op);
+    for (int v = 0; v < a->V; ++v)
+        if (!a->viewmatrix[v]) return fail(BAGS_ERR_ARG, "%s: viewmatrix[%d] is NULL (V = %d)", op, v, a->V);
+    return BAGS_OK;
+}
+
+int bags_gaussian_normals_forward(const BagsGaussianNormals* a, float* const out[], void* stream)
+{
+    if (const int rc = check_gaussian_normals("gaussian_normals_forward", a)) return rc;
+    if (a->P == 0) return BAGS_OK;
+    if (!out) return fail(BAGS_ERR_ARG, "gaussian_normals_forward: null out table");
+    for (int v = 0; v < a->V; ++v)
+        if (!out[v]) return fail(BAGS_ERR_ARG, "gaussian_normals_forward: out[%d] is NULL (V = %d)", v, a->V);
+    HIP_TRY(launch_gaussian_normals_fwd(*a, out, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
+int bags_gaussian_normals_backward(const BagsGaussianNormals* a, const float* const grad_out[], void* workspace, size_t workspace_bytes,
+                                   float* g_rotations, float* const g_viewmatrix[], void* stream)
+{
+    if (const int rc = check_gaussian_normals("gaussian_normals_backward", a)) return rc;
+    if (a->P == 0) return BAGS_OK;
+    if (!grad_out) return fail(BAGS_ERR_ARG, "gaussian_normals_backward: null grad_out table (its entries may be NULL, the table not)");
+    bool any_view = false;
+    for (int v = 0; v < a->V; ++v) any_view |= g_viewmatrix && g_viewmatrix[v];
+    float* slab = nullptr;
+    if (any_view) {
+        const size_t need = bags_gaussian_normals_workspace_size(a->P, a->V);
+        if (!workspace || workspace_bytes < need)
+            return fail(BAGS_ERR_SIZE, "gaussian_normals_backward: the view-matrix gradients need a workspace of %zu bytes (got %zu)", need,
+                        workspace ? workspace_bytes : (size_t)0);
+        carve_gaussian_normals(workspace, a->P, a->V, &slab);
+    }
+    if (!g_rotations && !slab) return BAGS_OK;
+    HIP_TRY(launch_gaussian_normals_bwd(*a, grad_out, slab, g_rotations, g_viewmatrix, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
+// ---- normal_map.hip: one row of 2 doubles per workgroup of the sums kernel, view-major; the slots are depth_prior.hip's
+static size_t carve_normal_map(void* base, int n_rows, int H, int W, double** partials)
+{
+    Carver c(base, false);                       // the base as given: a misaligned one is refused, not rounded
+    double* p = c.take<double>((size_t)n_rows * depth_prior_slots(H, W) * BAGS_NORMAL_MAP_STATS);
+    if (partials) *partials = p;
+    return c.used();
+}
+
+size_t bags_normal_map_workspace_size(int32_t n_rows, int32_t H, int32_t W)
+{
+    if (n_rows < 1 || n_rows > BAGS_MAX_POSE_ROWS || !depth_prior_image_ok(H, W)) return 0;
+    return carve_normal_map(nullptr, n_rows, H, W, nullptr);
+}
+
+static int check_normal_map(const char* op, const BagsNormalMap* a)
+{
+    if (!a) return fail(BAGS_ERR_ARG, "%s: null struct", op);
+    if (a->mode != BAGS_NORMAL_PRIOR_COS && a->mode != BAGS_NORMAL_PRIOR_L1) return fail(BAGS_ERR_ARG, "%s: unknown mode %d", op, a->mode);
+    if (a->n_rows < 1 || a->n_rows > BAGS_MAX_POSE_ROWS) return fail(BAGS_ERR_ARG, "%s: n_rows %d not in 1..%d", op, a->n_rows, BAGS_MAX_POSE_ROWS);
+    if (a->H < 1 || a->W < 1) return fail(BAGS_ERR_ARG, "%s: empty image %dx%d", op, a->W, a->H);
+    if (!depth_prior_image_ok(a->H, a->W)) return fail(BAGS_ERR_ARG, "%s: image %dx%d has 2^31 pixels or more", op, a->W, a->H);
+    if (!(a->min_weight == a->min_weight)) return fail(BAGS_ERR_ARG, "%s: min_weight is NaN", op);
+    if (!(a->min_norm >= 0.0f)) return fail(BAGS_ERR_ARG, "%s: min_norm must be a non-negative number", op);
+    for (int v = 0; v < a->n_rows; ++v) {
+        if (!a->normal[v]) return fail(BAGS_ERR_ARG, "%s: null normal[%d]", op, v);
+        if (!a->weights[v]) return fail(BAGS_ERR_ARG, "%s: null weights[%d]", op, v);
+        if (!a->prior[v]) return fail(BAGS_ERR_ARG, "%s: null prior[%d]", op, v);
+    }
+    return BAGS_OK;
+}
+
+int bags_normal_map_forward(const BagsNormalMap* a, void* workspace, size_t workspace_bytes, float* loss, float* count, double* stats,
+                            void* stream)
+{
+    if (const int rc = check_normal_map("normal_map_forward", a)) return rc;
+    if (!loss || !count || !stats) return fail(BAGS_ERR_ARG, "normal_map_forward: null loss / count / stats");
+    const size_t need = bags_normal_map_workspace_size(a->n_rows, a->H, a->W);
+    if (!workspace || workspace_bytes < need)
+        return fail(BAGS_ERR_ARG, "normal_map_forward: needs a workspace of %zu bytes (got %zu)", need, workspace ? workspace_bytes : (size_t)0);
+    if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return fail(BAGS_ERR_ARG, "normal_map_forward: the workspace is not 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(stats) % 8 != 0) return fail(BAGS_ERR_ARG, "normal_map_forward: stats is not 8-byte aligned");
+    double* partials = nullptr;
+    carve_normal_map(workspace, a->n_rows, a->H, a->W, &partials);
+    HIP_TRY(launch_normal_map_fwd(*a, partials, loss, count, stats, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
+int bags_normal_map_backward(const BagsNormalMap* a, const double* stats, const float* g_loss, float* const g_normal[BAGS_MAX_POSE_ROWS],
+                             void* stream)
+{
+    if (const int rc = check_normal_map("normal_map_backward", a)) return rc;
+    if (!stats) return fail(BAGS_ERR_ARG, "normal_map_backward: null stats");
+    if (reinterpret_cast<uintptr_t>(stats) % 8 != 0) return fail(BAGS_ERR_ARG, "normal_map_backward: stats is not 8-byte aligned");
+    if (!g_loss) return fail(BAGS_ERR_ARG, "normal_map_backward: null g_loss");
+    bool any_map = false;
+    for (int v = 0; v < a->n_rows; ++v) any_map |= g_normal && g_normal[v];
+    if (!any_map) return BAGS_OK;
+    HIP_TRY(launch_normal_map_bwd(*a, stats, g_loss, g_normal, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
 }  // extern "C"

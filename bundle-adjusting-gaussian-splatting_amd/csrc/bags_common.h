@@ -371,6 +371,18 @@ hipError_t launch_warp_fwd(const BagsWarp& a, double* partials, float* loss, flo
 hipError_t launch_warp_bwd(const BagsWarp& a, const double* stats, const float* g_loss, double* sums, float* const* g_depth, float* const* g_weights,
                            float* const* g_view_src, float* const* g_view_dst, hipStream_t st);
 hipError_t launch_warp_image(const BagsWarp& a, float* out, uint8_t* valid, hipStream_t st);
+// gaussian_normals.hip: the shortest axis of every Gaussian in the camera frame of V views, and its adjoint; slab:
+// gaussian_normals_blocks(P) rows of GN_SLAB_PER_VIEW * V floats, or nullptr when no view-matrix gradient is wanted
+// (carve_gaussian_normals in api.hip)
+#define GN_SLAB_PER_VIEW 9
+int gaussian_normals_blocks(int P);
+hipError_t launch_gaussian_normals_fwd(const BagsGaussianNormals& a, float* const* out, hipStream_t st);
+hipError_t launch_gaussian_normals_bwd(const BagsGaussianNormals& a, const float* const* grad_out, float* slab, float* g_rot,
+                                       float* const* g_view, hipStream_t st);
+// normal_map.hip: a rendered normal map held to a target on the V views of a step; partials: n_rows * depth_prior_slots(H, W) rows of
+// 2 doubles (carve_normal_map in api.hip); stats (n_rows,2) goes from the forward to the backward
+hipError_t launch_normal_map_fwd(const BagsNormalMap& a, double* partials, float* loss, float* count, double* stats, hipStream_t st);
+hipError_t launch_normal_map_bwd(const BagsNormalMap& a, const double* stats, const float* g_loss, float* const* g_normal, hipStream_t st);
 hipError_t launch_appearance_fwd(const BagsAppearance& a, hipStream_t st);
 hipError_t launch_appearance_bwd(const BagsAppearance& a, const float* const* g_out, double* partials, float* const* g_image, float* g_table,
                                  hipStream_t st);

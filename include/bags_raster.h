@@ -1084,6 +1084,61 @@ int    bags_bilagrid_tv_forward(const float* grids, int32_t N, int32_t Gx, int32
 int    bags_bilagrid_tv_backward(const float* grids, int32_t N, int32_t Gx, int32_t Gy, int32_t L, const float* g_loss /* (1) */,
                                  float* g_grids, void* stream);
 
+/* Per-Gaussian normals (csrc/gaussian_normals.hip): the shortest axis of every Gaussian in the camera frame of the V views of a
+ * step (1 <= V <= BAGS_MAX_SH_VIEWS; more views: one call per chunk), turned towards the camera.  Its output is the operator's
+ * colors_precomp of a second pass, which splats it into a normal map.  Per Gaussian and view, q = (w,x,y,z) as given:
+ *     k     = first minimum of the three scales (a decision; only their order is read, so log-scales serve)
+ *     c     = column k of Q(q) = |q|^2 R(q/|q|), formed without a division
+ *     m_j   = sum_i c_i V[i,j] ;  t = mean @ V[:3,:3] + V[3,:3]               (row-vector convention, V (16) on the device)
+ *     sigma = -1 if m . t > 0 else +1 ;  l2 = |m|^2 ;  live = l2 finite and > 0
+ *     out   = sigma m / sqrt(l2) where live, (0,0,0) elsewhere
+ * forward:  ONE launch whatever V is; a row is read once, 12 bytes are written per Gaussian and view.
+ * backward: recomputes the forward.  grad_out[v] may be NULL: a view no loss uses, a zero cotangent.  g_rotations (P,4) or NULL: the gradient of the quaternion as given, summed over the V views,
+ *           written once.  g_viewmatrix: NULL, or V pointers of which any may be NULL; a wanted one is a full (16) output whose
+ *           fourth row and column are written as zeros.  There is no gradient to the scales or the means (k and sigma are
+ *           decisions).  A dead row contributes exactly nothing.  The view-matrix outputs are per-workgroup sums in the workspace
+ *           added in double in workgroup order by a second launch: no atomics, two runs give the same bits, and a view's result does
+ *           not depend on the others of the call.  The workspace (bags_gaussian_normals_workspace_size bytes, no initialisation)
+ *           is needed only when a view-matrix output is wanted.  A wanted output's bits do not depend on which others are wanted.
+ * P == 0 is a successful no-op (nothing is written). */
+typedef struct BagsGaussianNormals {
+    int32_t P, V;
+    const float *rotations, *scales, *means3D;           /* (P,4), (P,3), (P,3) */
+    const float* viewmatrix[BAGS_MAX_SH_VIEWS];          /* (16) each, device, the first V given */
+} BagsGaussianNormals;
+int    bags_gaussian_normals_forward(const BagsGaussianNormals* args, float* const out[] /* V x (P,3) */, void* stream);
+size_t bags_gaussian_normals_workspace_size(int32_t P, int32_t V);
+int    bags_gaussian_normals_backward(const BagsGaussianNormals* args, const float* const grad_out[] /* V x (P,3) */, void* workspace,
+                                      size_t workspace_bytes, float* g_rotations, float* const g_viewmatrix[], void* stream);
+
+/* A rendered normal map held to a target normal map (csrc/normal_map.hip).  Per view: normal N (3,H,W), the weights map A (H,W), a
+ * target p (3,H,W), an optional pixel weight m (H,W).
+ *     valid = A >= min_weight and |N|^2 finite and > min_norm^2 and m > 0 and |p|^2 finite and > 0.25
+ *     nh = N/|N| ; ph = p/|p| ; w = m on valid pixels ; cnt = sum w
+ *     BAGS_NORMAL_PRIOR_COS: l = 1 - nh . ph     BAGS_NORMAL_PRIOR_L1: l = |nh - ph|_1, sign(0) = 0
+ *     L = sum w l / cnt ;  cnt <= 0: L = 0 and all gradients zero
+ * forward:  two launches for the n_rows <= BAGS_MAX_POSE_ROWS views of a step (pointers by value, nothing stacked): a pixels kernel
+ *           whose workgroups each leave one row of 2 doubles in the workspace, and a finalize kernel that adds a view's rows in a
+ *           fixed order and writes loss, count and the stats row (n_rows, BAGS_NORMAL_MAP_STATS) the backward reads.
+ * backward: one launch; g_normal[v] (3,H,W) or NULL.  Invalid pixels get exact zeros.  No gradient to A, p or m.
+ * No atomics, no memset: two runs give the same bits and a view's result does not depend on the others of the call.
+ * workspace: bags_normal_map_workspace_size bytes (0 for invalid arguments), 16-byte aligned, no initialisation (forward only). */
+#define BAGS_NORMAL_MAP_STATS 2              /* doubles per stats row (and per partial row of the workspace) */
+typedef struct BagsNormalMap {
+    int32_t mode, H, W;                      /* mode: BAGS_NORMAL_PRIOR_COS / BAGS_NORMAL_PRIOR_L1 */
+    int32_t n_rows;                          /* views of the call, 1..BAGS_MAX_POSE_ROWS */
+    float min_weight, min_norm;              /* min_norm >= 0 */
+    const float* normal[BAGS_MAX_POSE_ROWS]; /* (3,H,W) each, the first n_rows given */
+    const float* weights[BAGS_MAX_POSE_ROWS];/* (H,W) each */
+    const float* prior[BAGS_MAX_POSE_ROWS];  /* (3,H,W) each */
+    const float* mask[BAGS_MAX_POSE_ROWS];   /* any of them NULL: every pixel weighs 1 */
+} BagsNormalMap;
+size_t bags_normal_map_workspace_size(int32_t n_rows, int32_t H, int32_t W);
+int    bags_normal_map_forward(const BagsNormalMap* args, void* workspace, size_t workspace_bytes, float* loss /* (n_rows) */,
+                               float* count /* (n_rows) */, double* stats, void* stream);
+int    bags_normal_map_backward(const BagsNormalMap* args, const double* stats, const float* g_loss /* (n_rows) */,
+                                float* const g_normal[BAGS_MAX_POSE_ROWS], void* stream);
+
 #ifdef __cplusplus
 }
 #endif
