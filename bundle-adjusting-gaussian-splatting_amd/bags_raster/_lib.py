@@ -262,6 +262,19 @@ class BagsNormalMap(C.Structure):           # the normal / weights / target / ma
                 ("prior", c_fp * MAX_POSE_ROWS), ("mask", c_fp * MAX_POSE_ROWS)]
 
 
+SMOOTH_TILE_W, SMOOTH_TILE_H, SMOOTH_PARTIALS, SMOOTH_STATS, SMOOTH_MEAN_SLOTS = 32, 8, 6, 8, 512      # include/bags_raster.h: BAGS_SMOOTH_*
+SMOOTH_DEPTH, SMOOTH_NORMAL = 0, 1
+SMOOTH_L1, SMOOTH_L2 = 0, 1
+
+
+class BagsSmooth(C.Structure):              # the field / weights / guide / mask maps of one step's views (csrc/smooth.hip); None = NULL
+    _fields_ = [("kind", C.c_int32), ("space", C.c_int32), ("order", C.c_int32), ("penalty", C.c_int32), ("normalize", C.c_int32),
+                ("H", C.c_int32), ("W", C.c_int32), ("n_rows", C.c_int32), ("guide_channels", C.c_int32), ("reserved", C.c_int32),
+                ("min_weight", C.c_float), ("min_norm", C.c_float), ("eps", C.c_double), ("gamma", C.c_double),
+                ("field", c_fp * MAX_POSE_ROWS), ("weights", c_fp * MAX_POSE_ROWS), ("guide", c_fp * MAX_POSE_ROWS),
+                ("mask", c_fp * MAX_POSE_ROWS)]
+
+
 SYMBOLS = {    "bags_abi_version": (C.c_int, []),
     "bags_build_info": (C.c_char_p, []),
     "bags_last_error": (C.c_char_p, []),
@@ -374,6 +387,9 @@ SYMBOLS = {    "bags_abi_version": (C.c_int, []),
     "bags_normal_map_workspace_size": (C.c_size_t, [C.c_int32] * 3),
     "bags_normal_map_forward": (C.c_int, [C.POINTER(BagsNormalMap), C.c_void_p, C.c_size_t, c_fp, c_fp, c_fp, C.c_void_p]),
     "bags_normal_map_backward": (C.c_int, [C.POINTER(BagsNormalMap), c_fp, c_fp, C.POINTER(c_fp), C.c_void_p]),
+    "bags_smooth_workspace_size": (C.c_size_t, [C.c_int32] * 3),
+    "bags_smooth_forward": (C.c_int, [C.POINTER(BagsSmooth), C.c_void_p, C.c_size_t, c_fp, c_fp, c_fp, C.c_void_p]),
+    "bags_smooth_backward": (C.c_int, [C.POINTER(BagsSmooth), c_fp, c_fp, C.POINTER(c_fp), C.POINTER(c_fp), C.c_void_p]),
     "bags_filter3d_workspace_size": (C.c_size_t, [C.c_int32]),
     "bags_filter3d_compute": (C.c_int, [c_fp, C.c_int32, c_fp, c_fp, c_fp, C.c_int32, C.c_float, C.c_void_p, C.c_size_t, c_fp, C.c_void_p]),
     "bags_activations_filtered_forward": (C.c_int, [C.POINTER(BagsRawGaussians), c_fp] + [C.c_void_p] * 5),

@@ -1988,4 +1988,80 @@ int bags_normal_map_backward(const BagsNormalMap* a, const double* stats, const 
     return BAGS_OK;
 }
 
+// ---- smooth.hip: one row of 6 doubles per tile of the sums kernel, then one row of 2 doubles per workgroup of the mean kernel,
+// both view-major
+static size_t carve_smooth(void* base, int n_rows, int H, int W, double** partials, double** mean_rows)
+{
+    Carver c(base, false);                       // the base as given: a misaligned one is refused, not rounded
+    double* p = c.take<double>((size_t)n_rows * (size_t)smooth_tiles(H, W) * BAGS_SMOOTH_PARTIALS);
+    double* m = c.take<double>((size_t)n_rows * (size_t)smooth_mean_slots(H, W) * 2);
+    if (partials) *partials = p;
+    if (mean_rows) *mean_rows = m;
+    return c.used();
+}
+
+size_t bags_smooth_workspace_size(int32_t n_rows, int32_t H, int32_t W)
+{
+    if (n_rows < 1 || n_rows > BAGS_MAX_POSE_ROWS || !depth_prior_image_ok(H, W)) return 0;
+    return carve_smooth(nullptr, n_rows, H, W, nullptr, nullptr);
+}
+
+static int check_smooth(const char* op, const BagsSmooth* a)
+{
+    if (!a) return fail(BAGS_ERR_ARG, "%s: null struct", op);
+    if (a->kind != BAGS_SMOOTH_DEPTH && a->kind != BAGS_SMOOTH_NORMAL) return fail(BAGS_ERR_ARG, "%s: unknown kind %d", op, a->kind);
+    if (a->kind == BAGS_SMOOTH_DEPTH && a->space != BAGS_DEPTH_PRIOR_DEPTH && a->space != BAGS_DEPTH_PRIOR_INVERSE)
+        return fail(BAGS_ERR_ARG, "%s: unknown space %d", op, a->space);
+    if (a->order != 1 && a->order != 2) return fail(BAGS_ERR_ARG, "%s: order must be 1 or 2 (got %d)", op, a->order);
+    if (a->penalty != BAGS_SMOOTH_L1 && a->penalty != BAGS_SMOOTH_L2) return fail(BAGS_ERR_ARG, "%s: unknown penalty %d", op, a->penalty);
+    if (a->normalize != 0 && a->normalize != 1) return fail(BAGS_ERR_ARG, "%s: normalize must be 0 or 1 (got %d)", op, a->normalize);
+    if (a->kind == BAGS_SMOOTH_NORMAL && a->normalize) return fail(BAGS_ERR_ARG, "%s: normalize with the normal kind (unit normals have no scale)", op);
+    if (a->n_rows < 1 || a->n_rows > BAGS_MAX_POSE_ROWS) return fail(BAGS_ERR_ARG, "%s: n_rows %d not in 1..%d", op, a->n_rows, BAGS_MAX_POSE_ROWS);
+    if (a->H < 1 || a->W < 1) return fail(BAGS_ERR_ARG, "%s: empty image %dx%d", op, a->W, a->H);
+    if (!depth_prior_image_ok(a->H, a->W)) return fail(BAGS_ERR_ARG, "%s: image %dx%d has 2^31 pixels or more", op, a->W, a->H);
+    if (a->guide_channels != 0 && a->guide_channels != 1 && a->guide_channels != 3)
+        return fail(BAGS_ERR_ARG, "%s: guide_channels must be 0, 1 or 3 (got %d)", op, a->guide_channels);
+    if (!(a->min_weight == a->min_weight)) return fail(BAGS_ERR_ARG, "%s: min_weight is NaN", op);
+    if (a->kind == BAGS_SMOOTH_NORMAL && !(a->min_norm >= 0.0f)) return fail(BAGS_ERR_ARG, "%s: min_norm must be a non-negative number", op);
+    if (!(a->eps >= 0.0 && a->eps < (double)INFINITY)) return fail(BAGS_ERR_ARG, "%s: eps must be a non-negative number", op);
+    if (a->penalty == BAGS_SMOOTH_L2 && a->eps != 0.0) return fail(BAGS_ERR_ARG, "%s: eps must be 0 with the l2 penalty", op);
+    if (!(a->gamma >= 0.0 && a->gamma < (double)INFINITY)) return fail(BAGS_ERR_ARG, "%s: gamma must be a non-negative number", op);
+    for (int v = 0; v < a->n_rows; ++v) {
+        if (!a->field[v]) return fail(BAGS_ERR_ARG, "%s: null field[%d]", op, v);
+        if (!a->weights[v]) return fail(BAGS_ERR_ARG, "%s: null weights[%d]", op, v);
+        if (a->guide_channels && !a->guide[v]) return fail(BAGS_ERR_ARG, "%s: null guide[%d]", op, v);
+    }
+    return BAGS_OK;
+}
+
+int bags_smooth_forward(const BagsSmooth* a, void* workspace, size_t workspace_bytes, float* loss, float* count, double* stats, void* stream)
+{
+    if (const int rc = check_smooth("smooth_forward", a)) return rc;
+    if (!loss || !count || !stats) return fail(BAGS_ERR_ARG, "smooth_forward: null loss / count / stats");
+    const size_t need = bags_smooth_workspace_size(a->n_rows, a->H, a->W);
+    if (!workspace || workspace_bytes < need)
+        return fail(BAGS_ERR_ARG, "smooth_forward: needs a workspace of %zu bytes (got %zu)", need, workspace ? workspace_bytes : (size_t)0);
+    if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return fail(BAGS_ERR_ARG, "smooth_forward: the workspace is not 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(stats) % 8 != 0) return fail(BAGS_ERR_ARG, "smooth_forward: stats is not 8-byte aligned");
+    double *partials = nullptr, *mean_rows = nullptr;
+    carve_smooth(workspace, a->n_rows, a->H, a->W, &partials, &mean_rows);
+    HIP_TRY(launch_smooth_fwd(*a, partials, mean_rows, loss, count, stats, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
+int bags_smooth_backward(const BagsSmooth* a, const double* stats, const float* g_loss, float* const g_field[BAGS_MAX_POSE_ROWS],
+                         float* const g_weights[BAGS_MAX_POSE_ROWS], void* stream)
+{
+    if (const int rc = check_smooth("smooth_backward", a)) return rc;
+    if (!stats) return fail(BAGS_ERR_ARG, "smooth_backward: null stats");
+    if (reinterpret_cast<uintptr_t>(stats) % 8 != 0) return fail(BAGS_ERR_ARG, "smooth_backward: stats is not 8-byte aligned");
+    if (!g_loss) return fail(BAGS_ERR_ARG, "smooth_backward: null g_loss");
+    bool any_map = false;
+    for (int v = 0; v < a->n_rows; ++v)
+        any_map |= (g_field && g_field[v]) || (a->kind == BAGS_SMOOTH_DEPTH && g_weights && g_weights[v]);
+    if (!any_map) return BAGS_OK;
+    HIP_TRY(launch_smooth_bwd(*a, stats, g_loss, g_field, g_weights, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
 }  // extern "C"

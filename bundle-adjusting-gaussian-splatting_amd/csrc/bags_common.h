@@ -383,6 +383,14 @@ hipError_t launch_gaussian_normals_bwd(const BagsGaussianNormals& a, const float
 // 2 doubles (carve_normal_map in api.hip); stats (n_rows,2) goes from the forward to the backward
 hipError_t launch_normal_map_fwd(const BagsNormalMap& a, double* partials, float* loss, float* count, double* stats, hipStream_t st);
 hipError_t launch_normal_map_bwd(const BagsNormalMap& a, const double* stats, const float* g_loss, float* const* g_normal, hipStream_t st);
+// smooth.hip: the edge-aware smoothness of the depth / weights maps or of a normal map on the V views of a step; partials: n_rows *
+// smooth_tiles(H, W) rows of 6 doubles, mean_rows: n_rows * smooth_mean_slots(H, W) rows of 2 doubles (carve_smooth in api.hip);
+// stats (n_rows,8) goes from the forward to the backward
+long long smooth_tiles(int H, int W);
+int smooth_mean_slots(int H, int W);
+hipError_t launch_smooth_fwd(const BagsSmooth& a, double* partials, double* mean_rows, float* loss, float* count, double* stats, hipStream_t st);
+hipError_t launch_smooth_bwd(const BagsSmooth& a, const double* stats, const float* g_loss, float* const* g_field, float* const* g_weights,
+                             hipStream_t st);
 hipError_t launch_appearance_fwd(const BagsAppearance& a, hipStream_t st);
 hipError_t launch_appearance_bwd(const BagsAppearance& a, const float* const* g_out, double* partials, float* const* g_image, float* g_table,
                                  hipStream_t st);

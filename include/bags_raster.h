@@ -1139,6 +1139,63 @@ int    bags_normal_map_forward(const BagsNormalMap* args, void* workspace, size_
 int    bags_normal_map_backward(const BagsNormalMap* args, const double* stats, const float* g_loss /* (n_rows) */,
                                 float* const g_normal[BAGS_MAX_POSE_ROWS], void* stream);
 
+/* Edge-aware smoothness of the depth / weights maps and of a splatted normal map (csrc/smooth.hip): the regulariser beside the data
+ * terms above (Monodepth2's get_smooth_loss, DN-Splatter's EdgeAwareTV and TVLoss, and their second-order variants).  Per view: a
+ * field map, the weights map A (H,W), an optional guide image I (guide_channels,H,W) (guide_channels = 0: none), an optional pixel
+ * weight m (H,W).
+ *     BAGS_SMOOTH_DEPTH:  field = D (H,W) ; usable = A >= min_weight and D > 0 and m > 0 and x finite ; x = A / D
+ *                         (BAGS_DEPTH_PRIOR_INVERSE) or D / A (BAGS_DEPTH_PRIOR_DEPTH), one division in float32 ;
+ *                         normalize: mu = sum_usable x / n, F = x / mu ; else F = x
+ *     BAGS_SMOOTH_NORMAL: field = N (3,H,W) ; usable = A >= min_weight and |N|^2 finite and > min_norm^2 and m > 0 ; F = N / |N|
+ *     order 1: d = F(u+1,v) - F(u,v), g = mean_c |I(u+1,v) - I(u,v)| ;  order 2: d = F(u-1,v) - 2 F(u,v) + F(u+1,v),
+ *              g = mean_c |I(u+1,v) - I(u-1,v)| / 2 ;  the same along v
+ *     a stencil is valid when its members are inside the image and usable and g is finite ; e = exp(-gamma g) ; w = min of m over
+ *     the members ; rho = mean over the channels of BAGS_SMOOTH_L1: sqrt(t^2 + eps^2) - eps (eps = 0: |t|, sign(0) = 0) or
+ *     BAGS_SMOOTH_L2: t^2 (eps must be 0)
+ *     L = S_x / cnt_x + S_y / cnt_y, S_dir = sum w e rho(d), cnt_dir = sum w (cnt_dir <= 0: that direction counts 0) ;
+ *     count = cnt_x + cnt_y ;  a view with no valid stencil: L = 0 and all gradients zero
+ * forward:  two launches for the n_rows <= BAGS_MAX_POSE_ROWS views of a step (pointers by value, nothing stacked), three where the
+ *           depth kind is normalised: [the mean: bags_smooth_mean_slots rows of (sum x, n) per view;] a tile kernel whose workgroups
+ *           each leave one row of BAGS_SMOOTH_PARTIALS doubles; a finalize kernel that adds a view's rows in a fixed order and writes
+ *           loss, count and the stats row (n_rows, BAGS_SMOOTH_STATS): 1/cnt_x, 1/cnt_y, 1/mu, n, T, cnt_x, cnt_y, mu.
+ * backward: one launch; g_field[v] ((H,W) or (3,H,W)) and, for the depth kind, g_weights[v] (H,W), each or NULL.  The normalised
+ *           depth field also sends -T / (mu n) to every usable pixel.  Pixels that are not usable get exact zeros.  No gradient to
+ *           the guide or the mask, and none to A of the normal kind (g_weights is not looked at there).
+ * No atomics, no memset: two runs give the same bits, a view's result does not depend on the others of the call, and what is stored
+ * is the same bits whichever outputs are wanted.
+ * workspace: bags_smooth_workspace_size bytes (0 for invalid arguments), 16-byte aligned, no initialisation (forward only). */
+#define BAGS_SMOOTH_TILE_W 32                /* a workgroup of 256 threads takes a tile of 32 x 8 pixels */
+#define BAGS_SMOOTH_TILE_H 8
+#define BAGS_SMOOTH_PARTIALS 6               /* doubles per partial row of the workspace */
+#define BAGS_SMOOTH_STATS 8                  /* doubles per stats row */
+#define BAGS_SMOOTH_MEAN_SLOTS 512           /* the mean has min(ceil(H W / 256), 512) workgroups per view */
+#define BAGS_SMOOTH_DEPTH 0                  /* kind */
+#define BAGS_SMOOTH_NORMAL 1
+#define BAGS_SMOOTH_L1 0                     /* penalty */
+#define BAGS_SMOOTH_L2 1
+typedef struct BagsSmooth {
+    int32_t kind;                            /* BAGS_SMOOTH_DEPTH / BAGS_SMOOTH_NORMAL */
+    int32_t space;                           /* depth kind: BAGS_DEPTH_PRIOR_DEPTH / BAGS_DEPTH_PRIOR_INVERSE */
+    int32_t order;                           /* 1 or 2 */
+    int32_t penalty;                         /* BAGS_SMOOTH_L1 / BAGS_SMOOTH_L2 */
+    int32_t normalize;                       /* depth kind: 0 or 1; the normal kind takes 0 */
+    int32_t H, W;
+    int32_t n_rows;                          /* views of the call, 1..BAGS_MAX_POSE_ROWS */
+    int32_t guide_channels;                  /* 0 (no guide), 1 or 3 */
+    int32_t reserved;                        /* 0 */
+    float min_weight, min_norm;              /* min_norm >= 0 (normal kind) */
+    double eps, gamma;                       /* both >= 0; eps == 0 with BAGS_SMOOTH_L2 */
+    const float* field[BAGS_MAX_POSE_ROWS];  /* (H,W) or (3,H,W) each, the first n_rows given */
+    const float* weights[BAGS_MAX_POSE_ROWS];/* (H,W) each */
+    const float* guide[BAGS_MAX_POSE_ROWS];  /* (guide_channels,H,W) each; not looked at where guide_channels == 0 */
+    const float* mask[BAGS_MAX_POSE_ROWS];   /* any of them NULL: every pixel weighs 1 */
+} BagsSmooth;
+size_t bags_smooth_workspace_size(int32_t n_rows, int32_t H, int32_t W);
+int    bags_smooth_forward(const BagsSmooth* args, void* workspace, size_t workspace_bytes, float* loss /* (n_rows) */,
+                           float* count /* (n_rows) */, double* stats, void* stream);
+int    bags_smooth_backward(const BagsSmooth* args, const double* stats, const float* g_loss /* (n_rows) */,
+                            float* const g_field[BAGS_MAX_POSE_ROWS], float* const g_weights[BAGS_MAX_POSE_ROWS], void* stream);
+
 #ifdef __cplusplus
 }
 #endif
