@@ -310,9 +310,13 @@ loss_bwd_kernel(const float* __restrict__ img, const float* __restrict__ gt, int
 }
 
 static LossWindow make_window()
-{   // utils/loss_utils.py:35-37: exp(-(x-5)^2 / (2 sigma^2)) evaluated in double, stored as float, normalised in float
-    LossWindow w; float s = 0.f;
-    for (int i = 0; i < 11; ++i) { w.w[i] = (float)exp(-(double)((i - 5) * (i - 5)) / (2.0 * 1.5 * 1.5)); s += w.w[i]; }
+{   // utils/loss_utils.py:35-37: exp(-(x-5)^2 / (2 sigma^2)) evaluated in double, stored as float, divided in float by their
+    // float sum.  That sum is the correctly rounded one, as torch's gauss.sum() gives it: added up in float from left to right it
+    // comes out one ulp low, every weight 6e-8 too large, and SSIM's sigma^2 = E[a^2] - mu^2 magnifies a common scale of the window
+    // sums by mu^2 / sigma^2, a few hundred: 2e-5 of the gradient, all of one sign
+    LossWindow w; double sum = 0.0;
+    for (int i = 0; i < 11; ++i) { w.w[i] = (float)exp(-(double)((i - 5) * (i - 5)) / (2.0 * 1.5 * 1.5)); sum += (double)w.w[i]; }
+    const float s = (float)sum;
     for (int i = 0; i < 11; ++i) w.w[i] /= s;
     return w;
 }
