@@ -275,6 +275,14 @@ class BagsSmooth(C.Structure):              # the field / weights / guide / mask
                 ("mask", c_fp * MAX_POSE_ROWS)]
 
 
+GAUSSIAN_REG_BLOCK, GAUSSIAN_REG_ROWS, GAUSSIAN_REG_STATS, GAUSSIAN_REG_TERMS = 256, 1024, 8, 6      # include/bags_raster.h: BAGS_GAUSSIAN_REG_*
+
+
+class BagsGaussianReg(C.Structure):         # the raw leaves, the 3D filter and the row mask of one call (csrc/gaussian_reg.hip); None = NULL
+    _fields_ = [("P", C.c_int32), ("terms", C.c_uint32), ("max_ratio", C.c_float), ("max_scale", C.c_float), ("opacity_raw", c_fp),
+                ("scaling_raw", c_fp), ("filter", c_fp), ("select", c_fp)]
+
+
 SYMBOLS = {    "bags_abi_version": (C.c_int, []),
     "bags_build_info": (C.c_char_p, []),
     "bags_last_error": (C.c_char_p, []),
@@ -390,6 +398,9 @@ SYMBOLS = {    "bags_abi_version": (C.c_int, []),
     "bags_smooth_workspace_size": (C.c_size_t, [C.c_int32] * 3),
     "bags_smooth_forward": (C.c_int, [C.POINTER(BagsSmooth), C.c_void_p, C.c_size_t, c_fp, c_fp, c_fp, C.c_void_p]),
     "bags_smooth_backward": (C.c_int, [C.POINTER(BagsSmooth), c_fp, c_fp, C.POINTER(c_fp), C.POINTER(c_fp), C.c_void_p]),
+    "bags_gaussian_reg_workspace_size": (C.c_size_t, [C.c_int32]),
+    "bags_gaussian_reg_forward": (C.c_int, [C.POINTER(BagsGaussianReg), C.c_void_p, C.c_size_t, c_fp, c_fp, c_fp, C.c_void_p]),
+    "bags_gaussian_reg_backward": (C.c_int, [C.POINTER(BagsGaussianReg), c_fp, c_fp, c_fp, c_fp, C.c_void_p]),
     "bags_filter3d_workspace_size": (C.c_size_t, [C.c_int32]),
     "bags_filter3d_compute": (C.c_int, [c_fp, C.c_int32, c_fp, c_fp, c_fp, C.c_int32, C.c_float, C.c_void_p, C.c_size_t, c_fp, C.c_void_p]),
     "bags_activations_filtered_forward": (C.c_int, [C.POINTER(BagsRawGaussians), c_fp] + [C.c_void_p] * 5),

@@ -26,6 +26,7 @@ import torch
 
 from . import _lib as L
 from .filter3d import filter_3D, filter_3D_torch, filtered_activations_torch
+from .gaussian_reg import REG_TERMS, gaussian_reg_loss, gaussian_reg_loss_torch
 from .mcmc import N_MAX, relocation_binoms
 
 SH_C0 = 0.28209479177387814
@@ -242,6 +243,15 @@ class GaussianBag:
             op, sc = filtered_activations_torch(self._opacity, self._scaling, f)
             return self.get_xyz, (self.get_features if features else None), op, sc, self.get_rotation
         return self.get_xyz, (self.get_features if features else None), self.get_opacity, self.get_scaling, self.get_rotation
+
+    def regularizers(self, select=None, terms=REG_TERMS, max_ratio: float = 10.0, max_scale: float = 0.05):
+        """``(terms (6,), count ())``: the regularisers on the Gaussians themselves (bags_raster.gaussian_reg_loss: opacity, scale,
+        flat, aniso, big, entropy) of ``_opacity`` and ``_scaling``, over the rows ``select (P,)`` bool keeps (None: all).  With
+        ``filter_3D`` set they are taken on the filtered opacity and scales, exactly where ``activated()`` uses the filter.  Two HIP
+        launches forward and one backward on a GPU, ``gaussian_reg_loss_torch`` on the host."""
+        f = None if self.filter_3D is None else self._checked_filter("GaussianBag.regularizers")
+        fn = gaussian_reg_loss if self._xyz.is_cuda else gaussian_reg_loss_torch
+        return fn(self._opacity, self._scaling, f, select, terms, max_ratio, max_scale)
 
     def oneupSHdegree(self):
         if self.active_sh_degree < self.max_sh_degree:

@@ -2064,4 +2064,57 @@ int bags_smooth_backward(const BagsSmooth* a, const double* stats, const float* 
     return BAGS_OK;
 }
 
+// ---- gaussian_reg.hip: one record of 8 doubles per workgroup of the sums kernel
+static size_t carve_gaussian_reg(void* base, int P, double** records)
+{
+    Carver c(base, false);                       // the base as given: a misaligned one is refused, not rounded
+    double* r = c.take<double>((size_t)gaussian_reg_records(P) * BAGS_GAUSSIAN_REG_STATS);
+    if (records) *records = r;
+    return c.used();
+}
+
+size_t bags_gaussian_reg_workspace_size(int32_t P) { return carve_gaussian_reg(nullptr, P, nullptr); }
+
+static int check_gaussian_reg(const char* op, const BagsGaussianReg* a)
+{
+    if (!a) return fail(BAGS_ERR_ARG, "%s: null struct", op);
+    if (a->P < 0) return fail(BAGS_ERR_ARG, "%s: P < 0 (got %d)", op, a->P);
+    if (a->terms >> BAGS_GAUSSIAN_REG_TERMS) return fail(BAGS_ERR_ARG, "%s: unknown bits in terms 0x%x", op, a->terms);
+    if (!(a->max_ratio >= 1.0f)) return fail(BAGS_ERR_ARG, "%s: max_ratio must be >= 1", op);
+    if (!(a->max_scale >= 0.0f)) return fail(BAGS_ERR_ARG, "%s: max_scale must be >= 0", op);
+    if (a->P > 0 && (!a->opacity_raw || !a->scaling_raw)) return fail(BAGS_ERR_ARG, "%s: null opacity_raw / scaling_raw", op);
+    return BAGS_OK;
+}
+
+int bags_gaussian_reg_forward(const BagsGaussianReg* a, void* workspace, size_t workspace_bytes, float* terms, float* count, double* stats,
+                              void* stream)
+{
+    if (const int rc = check_gaussian_reg("gaussian_reg_forward", a)) return rc;
+    if (!terms || !count || !stats) return fail(BAGS_ERR_ARG, "gaussian_reg_forward: null terms / count / stats");
+    if (reinterpret_cast<uintptr_t>(stats) % 8 != 0) return fail(BAGS_ERR_ARG, "gaussian_reg_forward: stats is not 8-byte aligned");
+    const size_t need = bags_gaussian_reg_workspace_size(a->P);
+    if (need > 0 && (!workspace || workspace_bytes < need))
+        return fail(BAGS_ERR_SIZE, "gaussian_reg_forward: needs a workspace of %zu bytes (got %zu)", need, workspace ? workspace_bytes : (size_t)0);
+    if (need > 0 && reinterpret_cast<uintptr_t>(workspace) % 16 != 0)
+        return fail(BAGS_ERR_ARG, "gaussian_reg_forward: the workspace is not 16-byte aligned");
+    double* records = nullptr;
+    if (need > 0) carve_gaussian_reg(workspace, a->P, &records);
+    HIP_TRY(launch_gaussian_reg_fwd(*a, records, terms, count, stats, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
+int bags_gaussian_reg_backward(const BagsGaussianReg* a, const double* stats, const float* g_terms, float* g_opacity, float* g_scaling,
+                               void* stream)
+{
+    if (const int rc = check_gaussian_reg("gaussian_reg_backward", a)) return rc;
+    if (!stats) return fail(BAGS_ERR_ARG, "gaussian_reg_backward: null stats");
+    if (reinterpret_cast<uintptr_t>(stats) % 8 != 0) return fail(BAGS_ERR_ARG, "gaussian_reg_backward: stats is not 8-byte aligned");
+    if (!g_terms) return fail(BAGS_ERR_ARG, "gaussian_reg_backward: null g_terms");
+    if ((g_opacity && g_opacity == a->opacity_raw) || (g_scaling && g_scaling == a->scaling_raw))
+        return fail(BAGS_ERR_ARG, "gaussian_reg_backward: a gradient must not be its leaf");
+    if (a->P == 0 || (!g_opacity && !g_scaling)) return BAGS_OK;
+    HIP_TRY(launch_gaussian_reg_bwd(*a, stats, g_terms, g_opacity, g_scaling, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
 }  // extern "C"

@@ -391,6 +391,12 @@ int smooth_mean_slots(int H, int W);
 hipError_t launch_smooth_fwd(const BagsSmooth& a, double* partials, double* mean_rows, float* loss, float* count, double* stats, hipStream_t st);
 hipError_t launch_smooth_bwd(const BagsSmooth& a, const double* stats, const float* g_loss, float* const* g_field, float* const* g_weights,
                              hipStream_t st);
+// gaussian_reg.hip: the six regularisers on the raw _opacity / _scaling leaves; records: gaussian_reg_records(P) records of 8 doubles
+// (carve_gaussian_reg in api.hip); stats (8) goes from the forward to the backward
+int gaussian_reg_records(int P);
+hipError_t launch_gaussian_reg_fwd(const BagsGaussianReg& a, double* records, float* terms, float* count, double* stats, hipStream_t st);
+hipError_t launch_gaussian_reg_bwd(const BagsGaussianReg& a, const double* stats, const float* g_terms, float* g_opacity, float* g_scaling,
+                                   hipStream_t st);
 hipError_t launch_appearance_fwd(const BagsAppearance& a, hipStream_t st);
 hipError_t launch_appearance_bwd(const BagsAppearance& a, const float* const* g_out, double* partials, float* const* g_image, float* g_table,
                                  hipStream_t st);

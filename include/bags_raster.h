@@ -1196,6 +1196,44 @@ int    bags_smooth_forward(const BagsSmooth* args, void* workspace, size_t works
 int    bags_smooth_backward(const BagsSmooth* args, const double* stats, const float* g_loss /* (n_rows) */,
                             float* const g_field[BAGS_MAX_POSE_ROWS], float* const g_weights[BAGS_MAX_POSE_ROWS], void* stream);
 
+/* The regularisers on the Gaussians themselves (csrc/gaussian_reg.hip), over all P rows of the raw leaves: 3DGS-MCMC's opacity_reg and
+ * scale_reg means, the minimum-scale (flatness) loss of PGSR / 2DGS-style recipes, PhysGaussian's anisotropy-ratio hinge, a hinge on
+ * large scales and the opacity entropy of pruning recipes.  x = opacity_raw (P), r = scaling_raw (P,3), f = filter (P) or NULL,
+ * select (P bytes, 0 / 1) or NULL: every row.
+ *     no filter:  o = 1 / (1 + exp(-x)), s_a = exp(r_a) ;  filter:  s_a = sqrt(exp(r_a)^2 + f^2), o = sigmoid * prod_a exp(r_a) / s_a
+ *     n = the selected rows ;  kmin / kmax: the first minimum / maximum of a row's raw r
+ *     terms[0] opacity  sum o / n                                   terms[1] scale    sum sum_a s_a / (3 n)
+ *     terms[2] flat     sum s_kmin / n                              terms[3] aniso    sum max(s_kmax / s_kmin - max_ratio, 0) / n
+ *     terms[4] big      sum sum_a max(s_a - max_scale, 0) / (3 n)   terms[5] entropy  sum -(o log o + (1 - o) log(1 - o)) / n
+ * The sums run over the selected rows.  Both hinges are strict; a row with o <= 0 or o >= 1 in float32 has no entropy.  A term whose
+ * bit (1 << index) is not set in `terms` is an exact 0 and sends no gradient.  n == 0 (also P == 0): six zeros, zero gradients.
+ * forward:  two launches: workgroups of BAGS_GAUSSIAN_REG_BLOCK threads each take BAGS_GAUSSIAN_REG_ROWS rows and leave one record of
+ *           BAGS_GAUSSIAN_REG_STATS doubles; one workgroup adds the records in index order and writes terms (6), count (1) and the
+ *           stats record (BAGS_GAUSSIAN_REG_STATS doubles: the six raw sums, n, 0).
+ * backward: one launch; g_terms (6) and stats are read on the device.  g_opacity (P) and g_scaling (P,3), each or NULL, are written
+ *           completely (rows that are not selected: zeros).  With a filter the opacity-based terms reach g_scaling through c.
+ * No atomics, no memset: two runs give the same bits, and what is stored is the same bits whichever output is wanted.
+ * workspace: bags_gaussian_reg_workspace_size bytes (0 for P <= 0: NULL is accepted), 16-byte aligned, no initialisation. */
+#define BAGS_GAUSSIAN_REG_BLOCK 256          /* threads per workgroup */
+#define BAGS_GAUSSIAN_REG_ROWS 1024          /* rows per workgroup of the sums kernel (and per workspace record) */
+#define BAGS_GAUSSIAN_REG_STATS 8            /* doubles per workspace record and in the stats record */
+#define BAGS_GAUSSIAN_REG_TERMS 6
+typedef struct BagsGaussianReg {
+    int32_t P;
+    uint32_t terms;                          /* bit k: terms[k] is wanted; bits above BAGS_GAUSSIAN_REG_TERMS are refused */
+    float max_ratio;                         /* >= 1 */
+    float max_scale;                         /* >= 0 */
+    const float* opacity_raw;                /* (P,1) */
+    const float* scaling_raw;                /* (P,3) */
+    const float* filter;                     /* (P,1) or NULL: unfiltered */
+    const void* select;                      /* (P) bytes, non-zero: the row counts; NULL: every row */
+} BagsGaussianReg;
+size_t bags_gaussian_reg_workspace_size(int32_t P);
+int    bags_gaussian_reg_forward(const BagsGaussianReg* args, void* workspace, size_t workspace_bytes, float* terms /* (6) */,
+                                 float* count /* (1) */, double* stats, void* stream);
+int    bags_gaussian_reg_backward(const BagsGaussianReg* args, const double* stats, const float* g_terms /* (6) */,
+                                  float* g_opacity /* (P,1) or NULL */, float* g_scaling /* (P,3) or NULL */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
