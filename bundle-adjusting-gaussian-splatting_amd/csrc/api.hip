@@ -589,6 +589,7 @@ int bags_loss_forward(const float* image, const float* gt, int32_t C, int32_t H,
     if (!image || !gt || !workspace || !out_terms) return fail(BAGS_ERR_ARG, "loss_forward: null pointer");
     if (workspace_bytes < loss_workspace_bytes(C, H, W))
         return fail(BAGS_ERR_SIZE, "loss_forward: workspace %zu bytes < %zu", workspace_bytes, loss_workspace_bytes(C, H, W));
+    if (reinterpret_cast<uintptr_t>(workspace) % 4 != 0) return fail(BAGS_ERR_ARG, "loss_forward: the workspace is not 4-byte aligned");
     HIP_TRY(launch_loss_fwd(image, gt, C, H, W, workspace, out_terms, (hipStream_t)stream));
     return BAGS_OK;
 }
@@ -600,6 +601,7 @@ int bags_loss_backward(const float* image, const float* gt, int32_t C, int32_t H
     if (!image || !gt || !workspace || !grad_terms || !grad_image) return fail(BAGS_ERR_ARG, "loss_backward: null pointer");
     if (workspace_bytes < loss_workspace_bytes(C, H, W))
         return fail(BAGS_ERR_SIZE, "loss_backward: workspace %zu bytes < %zu", workspace_bytes, loss_workspace_bytes(C, H, W));
+    if (reinterpret_cast<uintptr_t>(workspace) % 4 != 0) return fail(BAGS_ERR_ARG, "loss_backward: the workspace is not 4-byte aligned");
     HIP_TRY(launch_loss_bwd(image, gt, C, H, W, workspace, grad_terms, grad_image, (hipStream_t)stream));
     return BAGS_OK;
 }
@@ -612,6 +614,7 @@ int bags_photometric_loss_forward(const float* image, const float* gt, int32_t C
     if (!(lambda_dssim >= 0.f && lambda_dssim <= 1.f)) return fail(BAGS_ERR_ARG, "photometric_loss_forward: lambda_dssim %g outside [0, 1]", (double)lambda_dssim);
     if (workspace_bytes < loss_workspace_bytes(C, H, W))
         return fail(BAGS_ERR_SIZE, "photometric_loss_forward: workspace %zu bytes < %zu", workspace_bytes, loss_workspace_bytes(C, H, W));
+    if (reinterpret_cast<uintptr_t>(workspace) % 4 != 0) return fail(BAGS_ERR_ARG, "photometric_loss_forward: the workspace is not 4-byte aligned");
     HIP_TRY(launch_loss_fwd(image, gt, C, H, W, workspace, out_loss_terms, (hipStream_t)stream, true, lambda_dssim));
     return BAGS_OK;
 }
@@ -624,6 +627,7 @@ int bags_photometric_loss_backward(const float* image, const float* gt, int32_t 
     if (!(lambda_dssim >= 0.f && lambda_dssim <= 1.f)) return fail(BAGS_ERR_ARG, "photometric_loss_backward: lambda_dssim %g outside [0, 1]", (double)lambda_dssim);
     if (workspace_bytes < loss_workspace_bytes(C, H, W))
         return fail(BAGS_ERR_SIZE, "photometric_loss_backward: workspace %zu bytes < %zu", workspace_bytes, loss_workspace_bytes(C, H, W));
+    if (reinterpret_cast<uintptr_t>(workspace) % 4 != 0) return fail(BAGS_ERR_ARG, "photometric_loss_backward: the workspace is not 4-byte aligned");
     HIP_TRY(launch_loss_bwd(image, gt, C, H, W, workspace, grad_loss, grad_image, (hipStream_t)stream, true, lambda_dssim));
     return BAGS_OK;
 }

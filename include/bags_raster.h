@@ -102,6 +102,16 @@ typedef struct BagsInputs {
     const float* shs_rest;
 } BagsInputs;
 
+/* Caller-owned memory.  Every buffer the library works in is the caller's: the three state buffers below, the backward's workspace
+ * and the workspace of every other entry point, each sized by its bags_*_size function.  None needs initialisation (it may hold
+ * anything), nothing outside its `bytes` is read or written, and a buffer one byte short of its size function is refused before
+ * anything is launched.  Two rules for the base pointer, by buffer (tests/test_memory_contract_gpu.py holds each entry point to its):
+ *   rounded   the library rounds the base up to 256 itself and the size carries the slack for it: ANY base is accepted.  The state
+ *             buffers (geom, binning, image), the backward workspace, and the workspaces of resample, resample_faces, sh_colors,
+ *             sh_colors_views, densify, lens_field, knn, mcmc, antialias, filter3d and gaussian_normals.
+ *   as given  the base is used as it is and must be aligned as the entry point says; another base is refused, not rounded, before
+ *             anything is launched.  16 bytes: appearance, bilagrid_tv, depth_prior, normal_prior, correspondence, warp, normal_map,
+ *             smooth, gaussian_reg.  4 bytes: the photometric loss.  (bags_bilagrid_workspace_size is 0: nothing is taken.) */
 /* caller-owned state that survives from forward to backward */
 typedef struct BagsState {
     void* geom;    size_t geom_bytes;     /* >= bags_geom_size(P)            */
@@ -276,8 +286,11 @@ int bags_profile_read(int max_stages, const char** names, double* total_ms, int6
  * (utils/loss_utils.py:18-19 and :48-76: five dense 11x11 depthwise conv2d calls and their autograd backward; call
  * site train.py:311-313, combined at train.py:325 as (1-lambda) L1 + lambda (1-SSIM)).
  *   image, gt     device, fp32, contiguous (C,H,W)
- *   workspace     caller-owned, bags_loss_workspace_size(C,H,W) bytes, kept from forward to backward
- *   out_terms     device float[2]: { mean |image-gt| , mean SSIM }
+ *   workspace     caller-owned, bags_loss_workspace_size(C,H,W) bytes, kept from forward to backward.  The base is used as given
+ *                 (the size has no slack for rounding it up): it holds float planes, so it is 4-byte aligned -- another base is
+ *                 refused before anything is launched -- and a 16-byte aligned one (with W % 4 == 0) takes the backward's vector
+ *                 path, with the same bits either way.  No initialisation.
+ *   out_terms    device float[2]: { mean |image-gt| , mean SSIM }
  *   grad_terms    device float[2]: upstream dL/d{L1 mean, SSIM mean} (read on the device: no host round trip)
  *   grad_image    device (C,H,W): dL/dimage
  * Stream-ordered on `stream`; sums are taken in a fixed order (bitwise reproducible). */

@@ -97,6 +97,23 @@ def test_backward_phase_is_validated(lib):
     assert rc == -1 and b"phase" in lib.bags_last_error(), (rc, lib.bags_last_error())
 
 
+def test_loss_workspace_is_taken_as_given_and_refused_off_four_bytes(lib):
+    """The loss workspace holds float planes and its base is not rounded (include/bags_raster.h): a base off 4 bytes, and a buffer one
+    byte short, are argument errors of all four entry points, reported before anything is enqueued (no GPU touched)."""
+    buf = (C.c_char * 4096)()
+    addr = (C.addressof(buf) + 15) // 16 * 16
+    need = lib.bags_loss_workspace_size(3, 5, 4)
+    calls = {"loss_forward": lambda ws, n: lib.bags_loss_forward(addr, addr, 3, 5, 4, ws, n, addr, None),
+             "loss_backward": lambda ws, n: lib.bags_loss_backward(addr, addr, 3, 5, 4, ws, n, addr, addr, None),
+             "photometric_loss_forward": lambda ws, n: lib.bags_photometric_loss_forward(addr, addr, 3, 5, 4, ws, n, 0.2, addr, None),
+             "photometric_loss_backward": lambda ws, n: lib.bags_photometric_loss_backward(addr, addr, 3, 5, 4, ws, n, 0.2, addr, addr, None)}
+    for op, call in calls.items():
+        for off in (1, 2, 3, 5):
+            assert call(addr + off, need) != 0
+            assert lib.bags_last_error() == (op + ": the workspace is not 4-byte aligned").encode(), (op, off, lib.bags_last_error())
+        assert call(addr, need - 1) != 0 and lib.bags_last_error().startswith((op + ": workspace").encode()), (op, lib.bags_last_error())
+
+
 def test_factored_sh_gradient_arguments_are_validated(lib):
     """ABI 10: bags_sh_gradient_from_views / BagsBackwardArgs.grad_dldc argument errors (reported before anything is enqueued)."""
     buf = (C.c_char * 4096)()
