@@ -20,6 +20,7 @@ from .gaussian_normals import gaussian_normals, gaussian_normals_views, gaussian
 from .normal_map import normal_map_loss, normal_map_loss_torch
 from .smooth import depth_smooth_loss, depth_smooth_loss_torch, normal_smooth_loss, normal_smooth_loss_torch
 from .gaussian_reg import REG_TERMS, gaussian_reg_loss, gaussian_reg_loss_torch
+from .alpha import alpha_loss, alpha_loss_torch
 from .io import save_ply, load_ply, save_checkpoint, load_checkpoint, save_exposure_json, load_exposure_json
 from .optim import GaussianAdam
 from .pose_bank import PoseBank, PoseAdam
@@ -42,4 +43,5 @@ __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gau
            "gaussian_normals", "gaussian_normals_views", "gaussian_normals_torch", "gaussian_normals_views_torch", "render_normals",
            "normal_map_loss", "normal_map_loss_torch",
            "depth_smooth_loss", "depth_smooth_loss_torch", "normal_smooth_loss", "normal_smooth_loss_torch",
-           "REG_TERMS", "gaussian_reg_loss", "gaussian_reg_loss_torch"]
+           "REG_TERMS", "gaussian_reg_loss", "gaussian_reg_loss_torch",
+           "alpha_loss", "alpha_loss_torch"]

@@ -283,6 +283,16 @@ class BagsGaussianReg(C.Structure):         # the raw leaves, the 3D filter and 
                 ("scaling_raw", c_fp), ("filter", c_fp), ("select", c_fp)]
 
 
+ALPHA_BCE, ALPHA_L1, ALPHA_L2, ALPHA_ENTROPY = 0, 1, 2, 3                          # include/bags_raster.h: BAGS_ALPHA_*
+ALPHA_STATS, ALPHA_GROUPS = 2, 256
+ALPHA_WORKSPACE_BYTES = MAX_POSE_ROWS * ALPHA_GROUPS * ALPHA_STATS * 8            # a constant: this family has no size function
+
+
+class BagsAlpha(C.Structure):               # the weights / target / mask maps of one step's views (csrc/alpha.hip); None = NULL
+    _fields_ = [("mode", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("n_rows", C.c_int32), ("lo", C.c_float), ("hi", C.c_float),
+                ("weights", c_fp * MAX_POSE_ROWS), ("target", c_fp * MAX_POSE_ROWS), ("mask", c_fp * MAX_POSE_ROWS)]
+
+
 SYMBOLS = {    "bags_abi_version": (C.c_int, []),
     "bags_build_info": (C.c_char_p, []),
     "bags_last_error": (C.c_char_p, []),
@@ -401,6 +411,8 @@ SYMBOLS = {    "bags_abi_version": (C.c_int, []),
     "bags_gaussian_reg_workspace_size": (C.c_size_t, [C.c_int32]),
     "bags_gaussian_reg_forward": (C.c_int, [C.POINTER(BagsGaussianReg), C.c_void_p, C.c_size_t, c_fp, c_fp, c_fp, C.c_void_p]),
     "bags_gaussian_reg_backward": (C.c_int, [C.POINTER(BagsGaussianReg), c_fp, c_fp, c_fp, c_fp, C.c_void_p]),
+    "bags_alpha_forward": (C.c_int, [C.POINTER(BagsAlpha), C.c_void_p, C.c_size_t, c_fp, c_fp, c_fp, C.c_void_p]),
+    "bags_alpha_backward": (C.c_int, [C.POINTER(BagsAlpha), c_fp, c_fp, C.POINTER(c_fp), C.c_void_p]),
     "bags_filter3d_workspace_size": (C.c_size_t, [C.c_int32]),
     "bags_filter3d_compute": (C.c_int, [c_fp, C.c_int32, c_fp, c_fp, c_fp, C.c_int32, C.c_float, C.c_void_p, C.c_size_t, c_fp, C.c_void_p]),
     "bags_activations_filtered_forward": (C.c_int, [C.POINTER(BagsRawGaussians), c_fp] + [C.c_void_p] * 5),

@@ -2121,4 +2121,59 @@ int bags_gaussian_reg_backward(const BagsGaussianReg* a, const double* stats, co
     return BAGS_OK;
 }
 
+// ---- alpha.hip: one row of 2 doubles per workgroup of the sums kernel, view-major.  The grid is fixed, so the layout is the same for
+// every call and its size is the header's constant: there is no size function
+static size_t carve_alpha(void* base, double** partials)
+{
+    Carver c(base, false);                       // the base as given: a misaligned one is refused, not rounded
+    double* p = c.take<double>((size_t)BAGS_MAX_POSE_ROWS * BAGS_ALPHA_GROUPS * BAGS_ALPHA_STATS);
+    if (partials) *partials = p;
+    return c.used();
+}
+static_assert(BAGS_ALPHA_WORKSPACE_BYTES % 256 == 0, "what the carving helper hands out is the constant of the header");
+
+static int check_alpha(const char* op, const BagsAlpha* a)
+{
+    if (!a) return fail(BAGS_ERR_ARG, "%s: null struct", op);
+    if (a->mode != BAGS_ALPHA_BCE && a->mode != BAGS_ALPHA_L1 && a->mode != BAGS_ALPHA_L2 && a->mode != BAGS_ALPHA_ENTROPY)
+        return fail(BAGS_ERR_ARG, "%s: unknown mode %d", op, a->mode);
+    if (a->n_rows < 1 || a->n_rows > BAGS_MAX_POSE_ROWS) return fail(BAGS_ERR_ARG, "%s: n_rows %d not in 1..%d", op, a->n_rows, BAGS_MAX_POSE_ROWS);
+    if (a->H < 1 || a->W < 1) return fail(BAGS_ERR_ARG, "%s: empty image %dx%d", op, a->W, a->H);
+    if (!depth_prior_image_ok(a->H, a->W)) return fail(BAGS_ERR_ARG, "%s: image %dx%d has 2^31 pixels or more", op, a->W, a->H);
+    if (!(a->lo > 0.0f && a->lo < a->hi && a->hi < 1.0f)) return fail(BAGS_ERR_ARG, "%s: the clamp must be 0 < lo < hi < 1", op);
+    for (int v = 0; v < a->n_rows; ++v) {
+        if (!a->weights[v]) return fail(BAGS_ERR_ARG, "%s: null weights[%d]", op, v);
+        if (a->mode != BAGS_ALPHA_ENTROPY && !a->target[v]) return fail(BAGS_ERR_ARG, "%s: null target[%d]", op, v);
+    }
+    return BAGS_OK;
+}
+
+int bags_alpha_forward(const BagsAlpha* a, void* workspace, size_t workspace_bytes, float* loss, float* count, double* stats, void* stream)
+{
+    if (const int rc = check_alpha("alpha_forward", a)) return rc;
+    if (!loss || !count || !stats) return fail(BAGS_ERR_ARG, "alpha_forward: null loss / count / stats");
+    const size_t need = carve_alpha(nullptr, nullptr);                    // == BAGS_ALPHA_WORKSPACE_BYTES
+    if (!workspace || workspace_bytes < need)
+        return fail(BAGS_ERR_ARG, "alpha_forward: needs a workspace of %zu bytes (got %zu)", need, workspace ? workspace_bytes : (size_t)0);
+    if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return fail(BAGS_ERR_ARG, "alpha_forward: the workspace is not 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(stats) % 8 != 0) return fail(BAGS_ERR_ARG, "alpha_forward: stats is not 8-byte aligned");
+    double* partials = nullptr;
+    carve_alpha(workspace, &partials);
+    HIP_TRY(launch_alpha_fwd(*a, partials, loss, count, stats, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
+int bags_alpha_backward(const BagsAlpha* a, const double* stats, const float* g_loss, float* const g_weights[BAGS_MAX_POSE_ROWS], void* stream)
+{
+    if (const int rc = check_alpha("alpha_backward", a)) return rc;
+    if (!stats) return fail(BAGS_ERR_ARG, "alpha_backward: null stats");
+    if (reinterpret_cast<uintptr_t>(stats) % 8 != 0) return fail(BAGS_ERR_ARG, "alpha_backward: stats is not 8-byte aligned");
+    if (!g_loss) return fail(BAGS_ERR_ARG, "alpha_backward: null g_loss");
+    bool any_map = false;
+    for (int v = 0; v < a->n_rows; ++v) any_map |= g_weights && g_weights[v];
+    if (!any_map) return BAGS_OK;
+    HIP_TRY(launch_alpha_bwd(*a, stats, g_loss, g_weights, (hipStream_t)stream));
+    return BAGS_OK;
+}
+
 }  // extern "C"

@@ -383,6 +383,11 @@ hipError_t launch_gaussian_normals_bwd(const BagsGaussianNormals& a, const float
 // 2 doubles (carve_normal_map in api.hip); stats (n_rows,2) goes from the forward to the backward
 hipError_t launch_normal_map_fwd(const BagsNormalMap& a, double* partials, float* loss, float* count, double* stats, hipStream_t st);
 hipError_t launch_normal_map_bwd(const BagsNormalMap& a, const double* stats, const float* g_loss, float* const* g_normal, hipStream_t st);
+// alpha.hip: the weights map held to a target, or its entropy, on the V views of a step; partials: BAGS_MAX_POSE_ROWS *
+// BAGS_ALPHA_GROUPS rows of 2 doubles, a constant (api.hip checks BAGS_ALPHA_WORKSPACE_BYTES); stats (n_rows,2) goes from the
+// forward to the backward
+hipError_t launch_alpha_fwd(const BagsAlpha& a, double* partials, float* loss, float* count, double* stats, hipStream_t st);
+hipError_t launch_alpha_bwd(const BagsAlpha& a, const double* stats, const float* g_loss, float* const* g_weights, hipStream_t st);
 // smooth.hip: the edge-aware smoothness of the depth / weights maps or of a normal map on the V views of a step; partials: n_rows *
 // smooth_tiles(H, W) rows of 6 doubles, mean_rows: n_rows * smooth_mean_slots(H, W) rows of 2 doubles (carve_smooth in api.hip);
 // stats (n_rows,8) goes from the forward to the backward

@@ -111,7 +111,8 @@ typedef struct BagsInputs {
  *             sh_colors_views, densify, lens_field, knn, mcmc, antialias, filter3d and gaussian_normals.
  *   as given  the base is used as it is and must be aligned as the entry point says; another base is refused, not rounded, before
  *             anything is launched.  16 bytes: appearance, bilagrid_tv, depth_prior, normal_prior, correspondence, warp, normal_map,
- *             smooth, gaussian_reg.  4 bytes: the photometric loss.  (bags_bilagrid_workspace_size is 0: nothing is taken.) */
+ *             smooth, gaussian_reg, alpha (whose size is the constant BAGS_ALPHA_WORKSPACE_BYTES, not a function).  4 bytes: the
+ *             photometric loss.  (bags_bilagrid_workspace_size is 0: nothing is taken.) */
 /* caller-owned state that survives from forward to backward */
 typedef struct BagsState {
     void* geom;    size_t geom_bytes;     /* >= bags_geom_size(P)            */
@@ -1246,6 +1247,51 @@ int    bags_gaussian_reg_forward(const BagsGaussianReg* args, void* workspace, s
                                  float* count /* (1) */, double* stats, void* stream);
 int    bags_gaussian_reg_backward(const BagsGaussianReg* args, const double* stats, const float* g_terms /* (6) */,
                                   float* g_opacity /* (P,1) or NULL */, float* g_scaling /* (P,3) or NULL */, void* stream);
+
+/* The weights map itself held to a target, or to solid-or-empty (csrc/alpha.hip): the silhouette / mask loss of object-centric
+ * captures, the sky loss of the urban recipes (target 1 - sky) and the alpha entropy.  Per view: the weights map A (H,W), an optional
+ * target t (H,W) (constant data), an optional pixel weight m (H,W).
+ *     usable = A finite and m > 0 and (BAGS_ALPHA_ENTROPY: always | the target modes: t finite; BAGS_ALPHA_BCE also 0 <= t <= 1)
+ *     w = m on usable pixels ; cnt = sum w
+ *     inside = lo < A < hi, compared in float32 (the caller rounds lo = eps and hi = 1 - eps once) ;
+ *     a = A inside, lo where A <= lo, hi where A >= hi
+ *     BAGS_ALPHA_BCE:     l = -(t log a + (1 - t) log(1 - a))     dl/dA = (a - t) / (a (1 - a)) inside, 0 outside
+ *     BAGS_ALPHA_ENTROPY: l = -(a log a + (1 - a) log(1 - a))     dl/dA = log((1 - a) / a) inside, 0 outside ; target is not looked at
+ *     BAGS_ALPHA_L1:      l = |A - t|, sign(0) = 0                BAGS_ALPHA_L2: l = (A - t)^2
+ *     L = sum w l / cnt ;  cnt <= 0: L = 0 and the gradient all zeros
+ * forward:  two launches for the n_rows <= BAGS_MAX_POSE_ROWS views of a step (pointers by value, nothing stacked): a sums kernel of
+ *           BAGS_ALPHA_GROUPS workgroups per view, whatever the size of the maps, each of which walks its own contiguous span of the
+ *           view's pixels and leaves one row of BAGS_ALPHA_STATS doubles (cnt, sum w l; a zero row for an empty span), and a finalize
+ *           kernel that adds a view's rows in index order and writes loss, count and the stats row (n_rows, BAGS_ALPHA_STATS) the
+ *           backward reads.
+ * backward: one launch; g_weights[v] (H,W) or NULL, written completely (pixels that are not usable: exact zeros); g_loss is read on
+ *           the device.  No gradient to t or m; the clamp and the validity are decisions.
+ * No atomics, no memset: two runs give the same bits and a view's result does not depend on the others of the call.
+ * workspace: the grid is fixed, so the scratch is a constant and this family has no size function: BAGS_ALPHA_WORKSPACE_BYTES bytes
+ *           whatever n_rows, H and W, 16-byte aligned, as given (another base is refused, not rounded), no initialisation (forward
+ *           only).  Argument errors -- a base off 16 bytes, a buffer one byte short, an unknown mode, n_rows outside
+ *           1..BAGS_MAX_POSE_ROWS, H W >= 2^31, a NULL among the first n_rows weights -- are reported before anything is enqueued. */
+#define BAGS_ALPHA_BCE 0                     /* mode */
+#define BAGS_ALPHA_L1 1
+#define BAGS_ALPHA_L2 2
+#define BAGS_ALPHA_ENTROPY 3
+#define BAGS_ALPHA_STATS 2                   /* doubles per stats row (and per partial row of the workspace) */
+#ifndef BAGS_ALPHA_GROUPS
+#define BAGS_ALPHA_GROUPS 256                /* workgroups per view of the sums kernel: a power of two <= 256 (profiles/alpha/NOTES.md) */
+#endif
+#define BAGS_ALPHA_WORKSPACE_BYTES (BAGS_MAX_POSE_ROWS * BAGS_ALPHA_GROUPS * BAGS_ALPHA_STATS * 8)
+typedef struct BagsAlpha {
+    int32_t mode, H, W;                      /* mode: BAGS_ALPHA_BCE / _L1 / _L2 / _ENTROPY */
+    int32_t n_rows;                          /* views of the call, 1..BAGS_MAX_POSE_ROWS */
+    float lo, hi;                            /* 0 < lo < hi < 1: eps and 1 - eps, each rounded once to float32 */
+    const float* weights[BAGS_MAX_POSE_ROWS];/* (H,W) each, the first n_rows given */
+    const float* target[BAGS_MAX_POSE_ROWS]; /* (H,W) each; not looked at with BAGS_ALPHA_ENTROPY */
+    const float* mask[BAGS_MAX_POSE_ROWS];   /* any of them NULL: every pixel weighs 1 */
+} BagsAlpha;
+int    bags_alpha_forward(const BagsAlpha* args, void* workspace, size_t workspace_bytes, float* loss /* (n_rows) */,
+                          float* count /* (n_rows) */, double* stats, void* stream);
+int    bags_alpha_backward(const BagsAlpha* args, const double* stats, const float* g_loss /* (n_rows) */,
+                           float* const g_weights[BAGS_MAX_POSE_ROWS], void* stream);
 
 #ifdef __cplusplus
 }
