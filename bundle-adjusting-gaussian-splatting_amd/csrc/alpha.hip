@@ -14,13 +14,13 @@
 // A map is a flat run of H W floats (no stencil: rows do not matter), taken as quads of four consecutive pixels.  A view has
 // BAGS_ALPHA_GROUPS workgroups whatever its size and whatever the number of views (grid dimension y); workgroup g walks the
 // contiguous span of quads [g span, (g + 1) span), thread t the quads t, t + ALPHA_BLOCK, ... of it, and leaves one row of 2
-// doubles (cnt, sum w l): the lanes of a wave added by a shuffle butterfly, the waves in wave order through LDS.  A workgroup whose
-// span is empty leaves a zero row, so the workspace is never assumed clean.  The finalize kernel adds a view's rows in index order.
+// doubles (cnt, sum w l), its lanes added as ordered_sum.h says (eight waves).  A workgroup whose span is empty leaves a zero row,
+// so the workspace is never assumed clean.  The finalize kernel adds a view's rows in index order, one after the other.
 // A whole quad is one float4 per map where every map of the call is 16-byte aligned, four floats otherwise, instantiated from one
 // body (and -ffp-contract=off: the same bits); the last quad of a map whose size is no multiple of four is taken element by
 // element in both.  No atomics, no memset: two runs give the same bits, and a view's loss, count and gradient are the same bits in
 // a 16-view call and in a call of its own.  The mode is a template parameter: l1 and l2 carry no logarithm.
-#include "bags_common.h"
+#include "ordered_sum.h"
 
 #ifndef ALPHA_BLOCK
 #define ALPHA_BLOCK 512                              // threads of a sums workgroup (profiles/alpha/NOTES.md: the alternatives timed)
@@ -40,38 +40,15 @@ struct AlphaDev {
     float* g_weights[BAGS_MAX_POSE_ROWS];            // backward: any of them NULL
 };
 
-// n elements (1..4) from p; the rest of d is 0.  A whole quad of the vector instance is one float4
-template <bool VEC> __device__ __forceinline__ void alpha_load4(const float* __restrict__ p, const int n, float (&d)[4])
-{
-    if (VEC && n == 4) {
-        const float4 t = *reinterpret_cast<const float4*>(p);
-        d[0] = t.x; d[1] = t.y; d[2] = t.z; d[3] = t.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) d[j] = (j < n) ? p[j] : 0.0f;
-    }
-}
-template <bool VEC> __device__ __forceinline__ void alpha_store4(float* __restrict__ p, const int n, const float (&d)[4])
-{
-    if (VEC && n == 4) {
-        *reinterpret_cast<float4*>(p) = make_float4(d[0], d[1], d[2], d[3]);
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) if (j < n) p[j] = d[j];
-    }
-}
-
-__device__ __forceinline__ bool alpha_finite(const float x) { return x - x == 0.0f; }
-
 // the maps of a quad; a lane past the end of the last quad has m = 0: not usable
 template <bool VEC, int MODE> struct AlphaQuad {
     float A[4], t[4], m[4];
     __device__ __forceinline__ void load(const AlphaDev& a, const int v, const size_t at, const int n)
     {
-        alpha_load4<VEC>(a.weights[v] + at, n, A);
-        if (MODE != BAGS_ALPHA_ENTROPY) alpha_load4<VEC>(a.target[v] + at, n, t);
+        osum::load4<VEC>(a.weights[v] + at, n, A);
+        if (MODE != BAGS_ALPHA_ENTROPY) osum::load4<VEC>(a.target[v] + at, n, t);
         const float* __restrict__ mk = a.mask[v];
-        if (mk) alpha_load4<VEC>(mk + at, n, m);                                             // uniform
+        if (mk) osum::load4<VEC>(mk + at, n, m);                                             // uniform
         else {
 #pragma unroll
             for (int j = 0; j < 4; ++j) m[j] = (j < n) ? 1.0f : 0.0f;
@@ -79,8 +56,8 @@ template <bool VEC, int MODE> struct AlphaQuad {
     }
     __device__ __forceinline__ bool usable(const int j) const
     {
-        bool ok = alpha_finite(A[j]) && m[j] > 0.0f;
-        if (MODE != BAGS_ALPHA_ENTROPY) ok = ok && alpha_finite(t[j]);
+        bool ok = osum::finite(A[j]) && m[j] > 0.0f;
+        if (MODE != BAGS_ALPHA_ENTROPY) ok = ok && osum::finite(t[j]);
         if (MODE == BAGS_ALPHA_BCE) ok = ok && t[j] >= 0.0f && t[j] <= 1.0f;
         return ok;
     }
@@ -105,7 +82,7 @@ template <bool VEC, int MODE> struct AlphaQuad {
     // dl/dA of a usable pixel
     __device__ __forceinline__ double slope(const AlphaDev& a, const int j) const
     {
-        if (MODE == BAGS_ALPHA_L1) { const double r = (double)A[j] - (double)t[j]; return (double)((r > 0.0) - (r < 0.0)); }
+        if (MODE == BAGS_ALPHA_L1) return osum::sign((double)A[j] - (double)t[j]);
         if (MODE == BAGS_ALPHA_L2) return 2.0 * ((double)A[j] - (double)t[j]);
         bool inside;
         const double x = clamped(a, j, inside);
@@ -119,7 +96,7 @@ template <bool VEC, int MODE> struct AlphaQuad {
 template <bool VEC, int MODE>
 __global__ void __launch_bounds__(ALPHA_BLOCK) alpha_sums_kernel(const AlphaDev a, double* __restrict__ partials)
 {
-    __shared__ double wsum[ALPHA_BLOCK / 64][ALPHA_ROW];
+    __shared__ double sh[ALPHA_BLOCK / 64 * ALPHA_ROW];
     const int v = blockIdx.y;
     double acc[ALPHA_ROW] = {0.0, 0.0};
 
@@ -136,26 +113,14 @@ __global__ void __launch_bounds__(ALPHA_BLOCK) alpha_sums_kernel(const AlphaDev 
             acc[0] += w; acc[1] += w * Qd.value(a, j);
         }
     }
-    // every lane is here: lanes -> wave (the butterfly leaves the same total in every lane), waves -> workgroup in wave order
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int t = 0; t < ALPHA_ROW; ++t) {
-        double s = acc[t];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d);
-        if (lane == 0) wsum[wave][t] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < ALPHA_ROW) {
-        double s = wsum[0][threadIdx.x];
-#pragma unroll
-        for (int k = 1; k < ALPHA_BLOCK / 64; ++k) s += wsum[k][threadIdx.x];
-        partials[((size_t)v * BAGS_ALPHA_GROUPS + blockIdx.x) * ALPHA_ROW + threadIdx.x] = s;
-    }
+    osum::block_sum<ALPHA_ROW, ALPHA_BLOCK / 64>(acc, sh);                                   // every lane is here
+    if (threadIdx.x < ALPHA_ROW)
+        partials[((size_t)v * BAGS_ALPHA_GROUPS + blockIdx.x) * ALPHA_ROW + threadIdx.x] = osum::block_total<ALPHA_ROW, ALPHA_BLOCK / 64>(sh, threadIdx.x);
 }
 
 // One workgroup per view: its BAGS_ALPHA_GROUPS partial rows, fetched by as many threads, added in index order by one thread per
-// column; then loss, count and the stats row.
+// column; then loss, count and the stats row.  NOT ordered_sum.h's ordered_rows_sum: one serial chain over the rows, whose bits the
+// operator has promised since it was added; a tree over the same rows rounds differently.
 __global__ void __launch_bounds__(BAGS_ALPHA_GROUPS) alpha_finalize_kernel(const double* __restrict__ partials, float* __restrict__ loss,
                                                                            float* __restrict__ count, double* __restrict__ stats)
 {
@@ -205,7 +170,7 @@ __global__ void __launch_bounds__(ALPHA_BWD_BLOCK) alpha_bwd_kernel(const AlphaD
         if (!(inv > 0.0) || !Qd.usable(j)) continue;
         d[j] = (float)((g * ((double)Qd.m[j] * inv)) * Qd.slope(a, j));
     }
-    alpha_store4<VEC>(gA + at, n, d);
+    osum::store4<VEC>(gA + at, n, d);
 }
 
 static AlphaDev alpha_dev(const BagsAlpha& a, float* const* g_weights)

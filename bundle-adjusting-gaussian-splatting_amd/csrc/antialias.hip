@@ -10,9 +10,9 @@
 // the forward from the inputs (nothing is saved, as K9) and states the backward of the covariance chain a SECOND time -- K9's
 // lines in K9's order (preprocess_bwd.hip step 3 and the shift polynomial), to be folded later (DESIGN.md open items).  The 17
 // non-zero pose terms (viewmatrix 4x3, k[0], k[5], shift_factors) are reduced wave -> workgroup -> one slab row per workgroup;
-// a second small launch adds the rows in double in a fixed order (bags_common.h: slab_column_sum).  No atomics: two runs give
+// a second small launch adds the rows in double in a fixed order (ordered_sum.h: slab_column_sum).  No atomics: two runs give
 // the same bits.
-#include "bags_common.h"
+#include "ordered_sum.h"
 #include "projection.h"
 
 #define AA_BLOCK 256

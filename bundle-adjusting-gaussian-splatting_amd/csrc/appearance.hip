@@ -13,11 +13,11 @@
 // operations and the file is compiled with -ffp-contract=off, so they give the same bits.  The views of a call are grid
 // dimension y; their pointers and table rows arrive by value, and a view's row is read through wave-uniform addresses.
 //
-// The 15 sums of a view: a lane adds its terms in double; after its last tile the lanes of a wave are added by a shuffle
-// butterfly, the four waves in wave order in LDS, and the workgroup leaves one row of 16 doubles.  A view has appearance_slots(H, W)
-// workgroups whatever the number of views, so its rows -- and the table kernel's fixed-order sum of them -- are the same in a
-// 16-view call and in a call of its own.  No atomics, no memset.
-#include "bags_common.h"
+// The 15 sums of a view: a lane adds its terms in double; after its last tile the workgroup adds its lanes (ordered_sum.h) and
+// leaves one row of 16 doubles, the 16th a zero it writes.  A view has appearance_slots(H, W) workgroups whatever the number of
+// views, so its rows -- and the table kernel's sum of them in row order (ordered_sum.h) -- are the same in a 16-view call and in a
+// call of its own.  No atomics, no memset.
+#include "ordered_sum.h"
 
 #define APP_BLOCK BAGS_APPEARANCE_BLOCK
 #define APP_VALS 15                                  // sums per view; the 16th column of a row is unused
@@ -46,27 +46,6 @@ __device__ __forceinline__ AppRow app_row(const float* __restrict__ t)
     return r;
 }
 
-// n elements (1..4) from p; the rest of d is 0
-template <bool VEC> __device__ __forceinline__ void app_load4(const float* __restrict__ p, const int n, float (&d)[4])
-{
-    if (VEC) {
-        const float4 t = *reinterpret_cast<const float4*>(p);
-        d[0] = t.x; d[1] = t.y; d[2] = t.z; d[3] = t.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) d[j] = (j < n) ? p[j] : 0.0f;
-    }
-}
-template <bool VEC> __device__ __forceinline__ void app_store4(float* __restrict__ p, const int n, const float (&d)[4])
-{
-    if (VEC) {
-        *reinterpret_cast<float4*>(p) = make_float4(d[0], d[1], d[2], d[3]);
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) if (j < n) p[j] = d[j];
-    }
-}
-
 __device__ __forceinline__ float app_r2(const AppDev& a, const int x, const int y)
 {
     const float dx = ((float)x + 0.5f) - a.cx, dy = ((float)y + 0.5f) - a.cy;
@@ -82,13 +61,13 @@ __global__ void __launch_bounds__(APP_BLOCK) appearance_fwd_kernel(const AppDev 
     const unsigned q = blockIdx.x * APP_BLOCK + threadIdx.x;
     if (q >= a.nquads) return;
     const int y = (int)(q / (unsigned)a.Q), x0 = 4 * (int)(q - (unsigned)y * (unsigned)a.Q);
-    const int n = min(4, a.W - x0);
+    const int n = VEC ? 4 : min(4, a.W - x0);                                                // (VEC: W % 4 == 0)
     const size_t plane = (size_t)a.H * a.W, at = (size_t)y * a.W + x0;
     const float* __restrict__ img = a.image[v];
     float* __restrict__ out = a.out[v];
     float p[3][4], o[3][4];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) app_load4<VEC>(img + k * plane + at, n, p[k]);
+    for (int k = 0; k < 3; ++k) osum::load4<VEC>(img + k * plane + at, n, p[k]);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const float f = app_falloff(R, app_r2(a, x0 + j, y));
@@ -97,7 +76,7 @@ __global__ void __launch_bounds__(APP_BLOCK) appearance_fwd_kernel(const AppDev 
         for (int c = 0; c < 3; ++c) o[c][j] = q0 * R.e[0][c] + q1 * R.e[1][c] + q2 * R.e[2][c] + R.e[c][3];
     }
 #pragma unroll
-    for (int c = 0; c < 3; ++c) app_store4<VEC>(out + c * plane + at, n, o[c]);
+    for (int c = 0; c < 3; ++c) osum::store4<VEC>(out + c * plane + at, n, o[c]);
 }
 
 // Workgroup `slot` of view v walks the tiles slot, slot + nslots, ...  SUMS == false: the table gradient is not wanted, the image
@@ -107,7 +86,7 @@ __global__ void __launch_bounds__(APP_BLOCK) appearance_fwd_kernel(const AppDev 
 template <bool VEC, bool SUMS>
 __global__ void __launch_bounds__(APP_BLOCK) appearance_bwd_kernel(const AppDev a, double* __restrict__ partials)
 {
-    __shared__ double wsum[APP_BLOCK / 64][16];
+    __shared__ double sh[APP_BLOCK / 64 * 16];
     const int v = blockIdx.y;
     const AppRow R = app_row(a.table + (size_t)a.rows[v] * 16);
     const size_t plane = (size_t)a.H * a.W;
@@ -122,13 +101,13 @@ __global__ void __launch_bounds__(APP_BLOCK) appearance_bwd_kernel(const AppDev 
         const unsigned q = tile * APP_BLOCK + threadIdx.x;
         if (q >= a.nquads) continue;
         const int y = (int)(q / (unsigned)a.Q), x0 = 4 * (int)(q - (unsigned)y * (unsigned)a.Q);
-        const int n = min(4, a.W - x0);
+        const int n = VEC ? 4 : min(4, a.W - x0);
         const size_t at = (size_t)y * a.W + x0;
         float p[3][4], g[3][4], d[3][4];
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            app_load4<VEC>(gout + k * plane + at, n, g[k]);
-            if (SUMS) app_load4<VEC>(img + k * plane + at, n, p[k]);
+            osum::load4<VEC>(gout + k * plane + at, n, g[k]);
+            if (SUMS) osum::load4<VEC>(img + k * plane + at, n, p[k]);
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -156,45 +135,28 @@ __global__ void __launch_bounds__(APP_BLOCK) appearance_bwd_kernel(const AppDev 
         }
         if (gimg) {                                                                        // uniform
 #pragma unroll
-            for (int k = 0; k < 3; ++k) app_store4<VEC>(gimg + k * plane + at, n, d[k]);
+            for (int k = 0; k < 3; ++k) osum::store4<VEC>(gimg + k * plane + at, n, d[k]);
         }
     }
     if (!SUMS) return;
-    // every lane is here: lanes -> wave (the butterfly leaves the same total in every lane), waves -> workgroup in wave order
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int t = 0; t < APP_VALS; ++t) {
-        double x = acc[t];
-#pragma unroll
-        for (int s = 32; s >= 1; s >>= 1) x += __shfl_xor(x, s);
-        if (lane == 0) wsum[wave][t] = x;
-    }
-    __syncthreads();
+    osum::block_sum<APP_VALS>(acc, sh);                                                    // every lane is here
     if (threadIdx.x < 16)
-        partials[((size_t)v * gridDim.x + blockIdx.x) * 16 + threadIdx.x] =
-            (threadIdx.x < APP_VALS) ? ((wsum[0][threadIdx.x] + wsum[1][threadIdx.x]) + wsum[2][threadIdx.x]) + wsum[3][threadIdx.x] : 0.0;
+        partials[((size_t)v * gridDim.x + blockIdx.x) * 16 + threadIdx.x] = (threadIdx.x < APP_VALS) ? osum::block_total<APP_VALS>(sh, threadIdx.x) : 0.0;
 }
 
 // The (N,16) gradient, every element.  Workgroup (c, v) of the first n_rows * 16: column c of listed row rows[v], the view's
-// nslots partial rows added in slot order -- thread i takes slots i, i + 256, ..., a fixed shuffle tree, the waves in wave
-// order -- and rounded once (column 15: zero).  The workgroups after them: zeros into every row that is not listed.
+// nslots partial rows added in slot order (ordered_sum.h) and rounded once (column 15: no rows, zero).  The workgroups after them:
+// zeros into every row that is not listed.
 __global__ void __launch_bounds__(256) appearance_table_kernel(const AppDev a, const double* __restrict__ partials, const int nslots,
                                                                float* __restrict__ g_table)
 {
     const int sums = a.n_rows * 16;
     if ((int)blockIdx.x < sums) {                                                          // uniform
-        __shared__ double wsum[4];
+        __shared__ double sh[4];
         const int v = blockIdx.x >> 4, c = blockIdx.x & 15;
-        double acc = 0.0;
-        if (c < APP_VALS) {
-            const double* __restrict__ col = partials + (size_t)v * nslots * 16 + c;
-            for (int s = threadIdx.x; s < nslots; s += 256) acc += col[(size_t)s * 16];
-        }
-#pragma unroll
-        for (int s = 32; s >= 1; s >>= 1) acc += __shfl_xor(acc, s);
-        if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-        __syncthreads();
-        if (threadIdx.x == 0) g_table[(size_t)a.rows[v] * 16 + c] = (float)(((wsum[0] + wsum[1]) + wsum[2]) + wsum[3]);
+        double S[1];
+        osum::ordered_rows_sum<1>(partials + (size_t)v * nslots * 16 + c, c < APP_VALS ? nslots : 0, 16, sh, S);
+        if (threadIdx.x == 0) g_table[(size_t)a.rows[v] * 16 + c] = (float)S[0];
         return;
     }
     const size_t e = (size_t)(blockIdx.x - sums) * 256 + threadIdx.x;

@@ -54,40 +54,7 @@ __device__ __forceinline__ float det_atan2_pos(float rho, float tz)
     return (rho > tz) ? 1.57079637f - a : a;
 }
 
-// sum over the 64 lanes on DPP (row_shr 1/2/4/8 inside the 16-lane rows, row_bcast:15 / row_bcast:31 across them: six
-// v_add_f32_dpp); the total is valid in lane 63.  Every lane must be active.
-__device__ __forceinline__ float wave_total_f(float x)
-{
-#define DPP_ADD(ctrl, rmask) x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), ctrl, rmask, 0xf, false))
-    DPP_ADD(0x111, 0xf); DPP_ADD(0x112, 0xf); DPP_ADD(0x114, 0xf); DPP_ADD(0x118, 0xf); DPP_ADD(0x142, 0xa); DPP_ADD(0x143, 0xc);
-#undef DPP_ADD
-    return x;
-}
-
-// Column t of a slab of nblocks rows (one per workgroup of the kernel that wrote it, `stride` floats apart) summed in fp64 by one
-// 256-thread workgroup: thread i adds rows i, i + 256, ... in row order, the 64 partial sums of a wave are added by a fixed shuffle
-// tree, the four wave sums in wave order, so the result is deterministic.  The sum is returned in thread 0 (the others' is the same
-// and not meant to be used).  Every thread has its 8 loads of a trip in flight at once; rows past the end INSIDE the batch are read
-// at a clamped index and dropped afterwards: a remainder loop of single loads -- 1954 rows are 7.6 per thread, so most threads took
-// it -- was seven dependent round trips, 6.5 us of a kernel that needs one.  No `in range ? load : 0`: the compiler makes that a
-// branch per load with a wait behind each.
-__device__ __forceinline__ double slab_column_sum(const float* __restrict__ slab, const int nblocks, const int stride, const int t)
-{
-    __shared__ double wsum[4];
-    double acc = 0.0;
-    for (int b = threadIdx.x; b < nblocks; b += 8 * 256) {
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = slab[(size_t)min(b + u * 256, nblocks - 1) * stride + t];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) acc += (b + u * 256 < nblocks) ? (double)v[u] : 0.0;
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    return ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
-}
+// (the ordered sums -- wave_total_f, slab_column_sum and the double sums of the losses -- are in ordered_sum.h)
 
 // ---- tile masks of small rectangles (GeomView::keep) ------------------------------------------------------
 // A rectangle of at most 8 x 8 tiles carries a 64-bit mask of the tiles it emits, bit ry * 8 + rx; a larger one emits all.

@@ -18,14 +18,14 @@
 //
 // dL/dgrid: one workgroup per (xy-vertex, output channel c, view).  It walks the vertex's support rectangle (about 2W/(Gx-1) x
 // 2H/(Gy-1) pixels; the rectangle is a conservative bound, membership is decided per pixel by the forward's own x0, x1, y0, y1), a
-// lane adds a pixel's terms into L x 4 double accumulators with predicated adds for its two live z-bins; lanes are added by a
-// shuffle butterfly, the four waves in wave order, and every one of the vertex's L x 4 elements is rounded once and written -- zeros
-// where no pixel reaches.  The workgroups behind them write zeros into the rows that are not listed.  No atomics, no memset, no
-// workspace; a view's gradient is its own workgroups' alone.
+// lane adds a pixel's terms into L x 4 double accumulators with predicated adds for its two live z-bins; the workgroup adds its
+// lanes (ordered_sum.h), and every one of the vertex's L x 4 elements is rounded once and written -- zeros where no pixel reaches.
+// The workgroups behind them write zeros into the rows that are not listed.  No atomics, no memset, no workspace; a view's gradient
+// is its own workgroups' alone.
 //
 // Total variation: a partials kernel with a workgroup count decided by the element count alone and a one-workgroup finalize; the
 // backward is a gather.
-#include "bags_common.h"
+#include "ordered_sum.h"
 
 #define BG_TILE_W BAGS_BILAGRID_TILE_W
 #define BG_TILE_H BAGS_BILAGRID_TILE_H
@@ -33,7 +33,7 @@
 #define BG_STAGE_VERTS BAGS_BILAGRID_STAGE_VERTS
 #define BG_MAX_L BAGS_BILAGRID_MAX_L
 #define BG_TV_BLOCK BAGS_BILAGRID_TV_BLOCK
-static_assert(BG_BLOCK == 256, "the reductions below are written for four waves");
+static_assert(BG_BLOCK == 256 && BG_TV_BLOCK == 256, "four waves: block_sum's default, and ordered_rows_sum's 256 threads");
 
 struct BgDev {
     const float* grids;                              // (N,12,L,Gy,Gx)
@@ -187,7 +187,7 @@ __global__ void __launch_bounds__(BG_BLOCK) bilagrid_grid_bwd_kernel(const BgDev
         if (!listed) g_grids[e] = 0.0f;
         return;
     }
-    __shared__ double wsum[BG_BLOCK / 64][LMAX * 4];
+    __shared__ double sh[BG_BLOCK / 64 * LMAX * 4];
     const int v = (int)(blockIdx.x / per_view), rest = (int)(blockIdx.x - (unsigned)v * per_view);
     const int c = rest % 3, vert = rest / 3, vy = vert / Gx, vx = vert - vy * Gx;
     // a bound of the pixels with x0 == vx or x1 == vx: u in [vx-1, vx+1), widened by two pixels against the rounding of u
@@ -205,11 +205,9 @@ __global__ void __launch_bounds__(BG_BLOCK) bilagrid_grid_bwd_kernel(const BgDev
     const size_t plane = (size_t)a.H * a.W;
     const float* __restrict__ img = a.image[v];
     const float* __restrict__ gc = a.g[v] + (size_t)c * plane;
-    double acc[LMAX][4];
+    double acc[LMAX * 4];                                                                  // [z][j]
 #pragma unroll
-    for (int z = 0; z < LMAX; ++z)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[z][j] = 0.0;
+    for (int t = 0; t < LMAX * 4; ++t) acc[t] = 0.0;
 
     for (unsigned i = threadIdx.x; i < npix; i += BG_BLOCK) {
         const int yy = (int)(i / (unsigned)rw), y = ylo + yy, x = xlo + (int)(i - (unsigned)yy * (unsigned)rw);
@@ -232,24 +230,12 @@ __global__ void __launch_bounds__(BG_BLOCK) bilagrid_grid_bwd_kernel(const BgDev
         for (int z = 0; z < LMAX; ++z)
 #pragma unroll
             for (int j = 0; j < 4; ++j)                                                    // (z1 == z0 only where tz == 0: t1 is zero there)
-                acc[z][j] += (double)((z == q.z0) ? t0[j] : ((z == q.z1) ? t1[j] : 0.0f));
+                acc[z * 4 + j] += (double)((z == q.z0) ? t0[j] : ((z == q.z1) ? t1[j] : 0.0f));
     }
-    // every lane is here: lanes -> wave (the butterfly leaves the same total in every lane), waves -> workgroup in wave order
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int z = 0; z < LMAX; ++z)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            double s = acc[z][j];
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m);
-            if (lane == 0) wsum[wave][z * 4 + j] = s;
-        }
-    __syncthreads();
+    osum::block_sum<LMAX * 4>(acc, sh);                                                    // every lane is here
     if ((int)threadIdx.x < L * 4) {
-        const int z = threadIdx.x >> 2, j = threadIdx.x & 3, t = threadIdx.x;
-        g_grids[(size_t)a.rows[v] * row_elems + (((size_t)(4 * c + j) * L + z) * Gy + vy) * Gx + vx] =
-            (float)(((wsum[0][t] + wsum[1][t]) + wsum[2][t]) + wsum[3][t]);
+        const int z = threadIdx.x >> 2, j = threadIdx.x & 3;
+        g_grids[(size_t)a.rows[v] * row_elems + (((size_t)(4 * c + j) * L + z) * Gy + vy) * Gx + vx] = (float)osum::block_total<LMAX * 4>(sh, threadIdx.x);
     }
 }
 
@@ -258,7 +244,7 @@ __global__ void __launch_bounds__(BG_BLOCK) bilagrid_grid_bwd_kernel(const BgDev
 __global__ void __launch_bounds__(BG_TV_BLOCK) bilagrid_tv_partials_kernel(const float* __restrict__ X, const size_t E, const int Gx, const int Gy,
                                                                            const int L, double* __restrict__ partials)
 {
-    __shared__ double wsum[BG_TV_BLOCK / 64][3];
+    __shared__ double sh[BG_TV_BLOCK / 64 * 3];
     double acc[3] = {0.0, 0.0, 0.0};
     const size_t sy = (size_t)Gx, sz = (size_t)Gx * Gy;
     for (size_t e = (size_t)blockIdx.x * BG_TV_BLOCK + threadIdx.x; e < E; e += (size_t)gridDim.x * BG_TV_BLOCK) {
@@ -268,18 +254,8 @@ __global__ void __launch_bounds__(BG_TV_BLOCK) bilagrid_tv_partials_kernel(const
         if (iy + 1 < Gy) { const double d = (double)(X[e + sy] - x); acc[1] += d * d; }
         if (iz + 1 < L) { const double d = (double)(X[e + sz] - x); acc[2] += d * d; }
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int t = 0; t < 3; ++t) {
-        double s = acc[t];
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m);
-        if (lane == 0) wsum[wave][t] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < 4)
-        partials[(size_t)blockIdx.x * 4 + threadIdx.x] =
-            threadIdx.x < 3 ? ((wsum[0][threadIdx.x] + wsum[1][threadIdx.x]) + wsum[2][threadIdx.x]) + wsum[3][threadIdx.x] : 0.0;
+    osum::block_sum<3>(acc, sh);
+    if (threadIdx.x < 4) partials[(size_t)blockIdx.x * 4 + threadIdx.x] = threadIdx.x < 3 ? osum::block_total<3>(sh, threadIdx.x) : 0.0;
 }
 
 // 1 / (12 * (n_d - 1) * the other two sizes), 0 for an axis of one vertex
@@ -288,28 +264,14 @@ __host__ __device__ static inline double bg_tv_scale(const int n, const int o1, 
     return n >= 2 ? 1.0 / (12.0 * (double)(n - 1) * (double)o1 * (double)o2) : 0.0;
 }
 
-// one workgroup: thread i takes rows i, i + 256, ...; a fixed shuffle tree, the waves in wave order; then the one scalar
+// one workgroup: the nblk rows added in row order (ordered_sum.h), then the one scalar
 __global__ void __launch_bounds__(BG_TV_BLOCK) bilagrid_tv_finalize_kernel(const double* __restrict__ partials, const int nblk, const int N, const int Gx,
                                                                            const int Gy, const int L, float* __restrict__ loss)
 {
-    __shared__ double wsum[BG_TV_BLOCK / 64][3];
-    double acc[3] = {0.0, 0.0, 0.0};
-    for (int b = threadIdx.x; b < nblk; b += BG_TV_BLOCK)
-#pragma unroll
-        for (int t = 0; t < 3; ++t) acc[t] += partials[(size_t)b * 4 + t];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int t = 0; t < 3; ++t) {
-        double s = acc[t];
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m);
-        if (lane == 0) wsum[wave][t] = s;
-    }
-    __syncthreads();
+    __shared__ double sh[BG_TV_BLOCK / 64 * 3];
+    double tot[3];
+    osum::ordered_rows_sum<3>(partials, nblk, 4, sh, tot);
     if (threadIdx.x == 0) {
-        double tot[3];
-#pragma unroll
-        for (int t = 0; t < 3; ++t) tot[t] = ((wsum[0][t] + wsum[1][t]) + wsum[2][t]) + wsum[3][t];
         const double sum = (tot[0] * bg_tv_scale(Gx, Gy, L) + tot[1] * bg_tv_scale(Gy, Gx, L)) + tot[2] * bg_tv_scale(L, Gx, Gy);
         loss[0] = (float)(sum / (double)N);
     }

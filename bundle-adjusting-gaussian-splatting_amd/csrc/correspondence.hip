@@ -23,9 +23,9 @@
 //
 // A thread is a pixel (in row-major order), a workgroup the CO_CHUNK = 256 consecutive pixels of a chunk, the grid (chunk, pair).
 // Lane 0 of a workgroup forms M and c in double from the 24 device floats (about 100 flops) and leaves them in LDS; the host never
-// reads the matrices.  The sums: a lane adds its one pixel in double; the lanes of a wave are added by a shuffle butterfly, the four
-// waves in wave order in LDS, and the workgroup leaves its partial sums in the workspace.  A pair has ceil(H W / 256) workgroups
-// whatever the number of pairs, and the finishing kernels add its partials in a fixed order: a pair's results are the same bits in a
+// reads the matrices.  The sums: a lane holds its one pixel in double, the workgroup adds its lanes (ordered_sum.h) and leaves its
+// partial sums in the workspace.  A pair has ceil(H W / 256) workgroups whatever the number of pairs, and the finishing kernels add
+// its partials in chunk order (ordered_sum.h): a pair's results are the same bits in a
 // 16-pair launch and in a launch of its own.  No atomics, no memset.  Compiled with -ffp-contract=off: only the operations spelled.
 #include "reproject.h"
 
@@ -81,7 +81,7 @@ __global__ void __launch_bounds__(CO_CHUNK) correspondence_sums_kernel(const CoD
 {
     __shared__ double Mc[12];
     __shared__ int ok;
-    __shared__ double wsum[CO_CHUNK / 64][CO_ROW];
+    __shared__ double sh[CO_CHUNK / 64 * CO_ROW];
     const int pair = blockIdx.y;
     rp_stage_transform(a, pair, Mc, &ok);
     const long long npix = (long long)a.H * a.W;
@@ -96,18 +96,16 @@ __global__ void __launch_bounds__(CO_CHUNK) correspondence_sums_kernel(const CoD
             acc[0] = rs.w * rho; acc[1] = rs.w;
         }
     }
-    rp_block_sum<CO_ROW>(acc, wsum);
-    if (threadIdx.x < CO_ROW)
-        partials[((size_t)pair * gridDim.x + blockIdx.x) * CO_ROW + threadIdx.x] =
-            ((wsum[0][threadIdx.x] + wsum[1][threadIdx.x]) + wsum[2][threadIdx.x]) + wsum[3][threadIdx.x];
+    osum::block_sum<CO_ROW>(acc, sh);
+    if (threadIdx.x < CO_ROW) partials[((size_t)pair * gridDim.x + blockIdx.x) * CO_ROW + threadIdx.x] = osum::block_total<CO_ROW>(sh, threadIdx.x);
 }
 
 // One workgroup per pair: its nchunks partial rows added in chunk order, then loss, count and the stats row.
 __global__ void __launch_bounds__(256) correspondence_finalize_kernel(const int nchunks, const double* __restrict__ partials, float* __restrict__ loss,
                                                                       float* __restrict__ count, double* __restrict__ stats)
 {
-    __shared__ double wsum[CO_ROW][4];
-    rp_finalize(blockIdx.x, nchunks, partials, loss, count, stats, wsum);
+    __shared__ double sh[4 * CO_ROW];
+    rp_finalize(blockIdx.x, nchunks, partials, loss, count, stats, sh);
 }
 
 // dL/dD and dL/dA of every pixel of the chunk (zeros where the pixel is not valid), each rounded once from double, and -- SUMS --
@@ -119,7 +117,7 @@ __global__ void __launch_bounds__(CO_CHUNK) correspondence_bwd_kernel(const CoDe
 {
     __shared__ double Mc[12];
     __shared__ int ok;
-    __shared__ double wsum[CO_CHUNK / 64][CO_SUMS];
+    __shared__ double sh[CO_CHUNK / 64 * CO_SUMS];
     const int pair = blockIdx.y;
     rp_stage_transform(a, pair, Mc, &ok);
     const long long npix = (long long)a.H * a.W;
@@ -146,7 +144,7 @@ __global__ void __launch_bounds__(CO_CHUNK) correspondence_bwd_kernel(const CoDe
         if (gA) gA[p] = dA;
     }
     if (!SUMS) return;
-    rp_store_sums(acc, wsum, pair, sums);
+    rp_store_sums(acc, sh, pair, sums);
 }
 
 // One workgroup per pair: the twelve sums of its chunks added in a fixed order, then the chain to the two (4,4) gradients in double,
@@ -154,9 +152,9 @@ __global__ void __launch_bounds__(CO_CHUNK) correspondence_bwd_kernel(const CoDe
 // not wanted.
 __global__ void __launch_bounds__(256) correspondence_views_kernel(const CoDev a, const RpViewGrads g, const int nchunks, const double* __restrict__ sums)
 {
-    __shared__ double wsum[4];
+    __shared__ double sh[4];
     const int pair = blockIdx.x;
-    rp_views_chain(a.view_src[pair], a.view_dst[pair], pair, nchunks, sums, g.src[pair], g.dst[pair], wsum);
+    rp_views_chain(a.view_src[pair], a.view_dst[pair], pair, nchunks, sums, g.src[pair], g.dst[pair], sh);
 }
 
 // proj (2,H,W) and valid (H,W) of one pair: the projection where the pixel is solid and x_j.z >= min_depth, zeros elsewhere; valid

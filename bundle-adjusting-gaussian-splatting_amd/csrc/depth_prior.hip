@@ -19,11 +19,11 @@
 // the file is compiled with -ffp-contract=off, so they give the same bits.  The views of a call are grid dimension y; their
 // pointers and table rows arrive by value.
 //
-// The sums of a view: a lane adds its terms in double; after its last tile the lanes of a wave are added by a shuffle butterfly,
-// the four waves in wave order in LDS, and the workgroup leaves one row of 8 doubles.  A view has depth_prior_slots(H, W)
-// workgroups whatever the number of views, and the finalize kernel adds its rows in a fixed order: a view's loss, count, stats and
-// gradients are the same bits in a 16-view call and in a call of its own.  No atomics, no memset.
-#include "bags_common.h"
+// The sums of a view: a lane adds its terms in double; after its last tile the workgroup adds its lanes (ordered_sum.h) and leaves
+// one row of 8 doubles, the columns it has no sum for written as zeros.  A view has depth_prior_slots(H, W) workgroups whatever the
+// number of views, and the finalize kernel adds its rows in row order (ordered_sum.h): a view's loss, count, stats and gradients are
+// the same bits in a 16-view call and in a call of its own.  No atomics, no memset.
+#include "ordered_sum.h"
 
 #define DP_BLOCK BAGS_DEPTH_PRIOR_BLOCK
 #define DP_ROW 8                                     // doubles per partial row and per stats row
@@ -46,37 +46,16 @@ struct DpDev {
     float* g_weights[BAGS_MAX_POSE_ROWS];
 };
 
-// n elements (1..4) from p; the rest of d is 0
-template <bool VEC> __device__ __forceinline__ void dp_load4(const float* __restrict__ p, const int n, float (&d)[4])
-{
-    if (VEC) {
-        const float4 t = *reinterpret_cast<const float4*>(p);
-        d[0] = t.x; d[1] = t.y; d[2] = t.z; d[3] = t.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) d[j] = (j < n) ? p[j] : 0.0f;
-    }
-}
-template <bool VEC> __device__ __forceinline__ void dp_store4(float* __restrict__ p, const int n, const float (&d)[4])
-{
-    if (VEC) {
-        *reinterpret_cast<float4*>(p) = make_float4(d[0], d[1], d[2], d[3]);
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) if (j < n) p[j] = d[j];
-    }
-}
-
 // the four maps of a quad; a lane past the end of a short quad has D = 0: not valid
 template <bool VEC> struct DpQuad {
     float D[4], A[4], p[4], m[4];
     __device__ __forceinline__ void load(const DpDev& a, const int v, const size_t at, const int n)
     {
-        dp_load4<VEC>(a.depth[v] + at, n, D);
-        dp_load4<VEC>(a.weights[v] + at, n, A);
-        dp_load4<VEC>(a.prior[v] + at, n, p);
+        osum::load4<VEC>(a.depth[v] + at, n, D);
+        osum::load4<VEC>(a.weights[v] + at, n, A);
+        osum::load4<VEC>(a.prior[v] + at, n, p);
         const float* __restrict__ mk = a.mask[v];
-        if (mk) dp_load4<VEC>(mk + at, n, m);                                                // uniform
+        if (mk) osum::load4<VEC>(mk + at, n, m);                                             // uniform
         else {
 #pragma unroll
             for (int j = 0; j < 4; ++j) m[j] = 1.0f;
@@ -93,7 +72,6 @@ __device__ __forceinline__ void dp_ab(const DpDev& a, const int v, double& ca, d
     ca = 1.0; cb = 0.0;
     if (a.table) { ca = (double)a.table[2 * (size_t)a.rows[v]]; cb = (double)a.table[2 * (size_t)a.rows[v] + 1]; }
 }
-__device__ __forceinline__ double dp_sign(const double r) { return (double)((r > 0.0) - (r < 0.0)); }
 
 // Workgroup `slot` of view v walks the tiles slot, slot + nslots, ... and leaves one row of partials:
 //     n, then  sum wx, sum wp, sum wx^2, sum wp^2, sum wxp  (pearson)   or   sum w|r|, sum w sign(r) p, sum w sign(r)  (L1)
@@ -101,7 +79,7 @@ template <bool VEC, bool L1>
 __global__ void __launch_bounds__(DP_BLOCK) depth_prior_sums_kernel(const DpDev a, double* __restrict__ partials)
 {
     constexpr int NV = L1 ? 4 : 6;
-    __shared__ double wsum[DP_BLOCK / 64][DP_ROW];
+    __shared__ double sh[DP_BLOCK / 64 * DP_ROW];
     const int v = blockIdx.y;
     double ca, cb;
     dp_ab(a, v, ca, cb);
@@ -113,7 +91,7 @@ __global__ void __launch_bounds__(DP_BLOCK) depth_prior_sums_kernel(const DpDev 
         const unsigned q = tile * DP_BLOCK + threadIdx.x;
         if (q >= a.nquads) continue;
         const int y = (int)(q / (unsigned)a.Q), x0 = 4 * (int)(q - (unsigned)y * (unsigned)a.Q);
-        const int n = min(4, a.W - x0);
+        const int n = VEC ? 4 : min(4, a.W - x0);                                            // (VEC: W % 4 == 0)
         DpQuad<VEC> Qd;
         Qd.load(a, v, (size_t)y * a.W + x0, n);
 #pragma unroll
@@ -124,7 +102,7 @@ __global__ void __launch_bounds__(DP_BLOCK) depth_prior_sums_kernel(const DpDev 
             acc[0] += w;
             if (L1) {
                 const double r = x - (ca * p + cb);
-                const double ws = w * dp_sign(r);
+                const double ws = w * osum::sign(r);
                 acc[1] += w * fabs(r); acc[2] += ws * p; acc[3] += ws;
             } else {
                 const double wx = w * x, wp = w * p;
@@ -132,43 +110,21 @@ __global__ void __launch_bounds__(DP_BLOCK) depth_prior_sums_kernel(const DpDev 
             }
         }
     }
-    // every lane is here: lanes -> wave (the butterfly leaves the same total in every lane), waves -> workgroup in wave order
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int t = 0; t < NV; ++t) {
-        double s = acc[t];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d);
-        if (lane == 0) wsum[wave][t] = s;
-    }
-    __syncthreads();
+    osum::block_sum<NV>(acc, sh);                                                            // every lane is here
     if (threadIdx.x < DP_ROW)
-        partials[((size_t)v * gridDim.x + blockIdx.x) * DP_ROW + threadIdx.x] =
-            ((int)threadIdx.x < NV) ? ((wsum[0][threadIdx.x] + wsum[1][threadIdx.x]) + wsum[2][threadIdx.x]) + wsum[3][threadIdx.x] : 0.0;
+        partials[((size_t)v * gridDim.x + blockIdx.x) * DP_ROW + threadIdx.x] = ((int)threadIdx.x < NV) ? osum::block_total<NV>(sh, threadIdx.x) : 0.0;
 }
 
-// One workgroup per view: its nslots partial rows added in slot order -- thread i takes slots i, i + 256, ..., a fixed shuffle
-// tree, the waves in wave order -- then loss, count and the stats row.
+// One workgroup per view: its nslots partial rows added in slot order (ordered_sum.h), then loss, count and the stats row.
 __global__ void __launch_bounds__(256) depth_prior_finalize_kernel(const int l1, const int nslots, const double* __restrict__ partials,
                                                                    float* __restrict__ loss, float* __restrict__ count,
                                                                    double* __restrict__ stats)
 {
-    __shared__ double wsum[DP_ROW][4];
+    __shared__ double sh[4 * DP_ROW];
     const int v = blockIdx.x;
-    const double* __restrict__ rows = partials + (size_t)v * nslots * DP_ROW;
-#pragma unroll
-    for (int c = 0; c < 6; ++c) {
-        double acc = 0.0;
-        for (int s = threadIdx.x; s < nslots; s += 256) acc += rows[(size_t)s * DP_ROW + c];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d);
-        if ((threadIdx.x & 63) == 0) wsum[c][threadIdx.x >> 6] = acc;
-    }
-    __syncthreads();
-    if (threadIdx.x != 0) return;
     double S[6];
-#pragma unroll
-    for (int c = 0; c < 6; ++c) S[c] = ((wsum[c][0] + wsum[c][1]) + wsum[c][2]) + wsum[c][3];
+    osum::ordered_rows_sum<6>(partials + (size_t)v * nslots * DP_ROW, nslots, DP_ROW, sh, S);
+    if (threadIdx.x != 0) return;
     const double n = S[0];
     const double inv_n = n > 0.0 ? 1.0 / n : 0.0;
     double out[DP_ROW] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0};
@@ -209,7 +165,7 @@ __global__ void __launch_bounds__(DP_BLOCK) depth_prior_bwd_kernel(const DpDev a
     double ca, cb;
     dp_ab(a, v, ca, cb);
     const int y = (int)(q / (unsigned)a.Q), x0 = 4 * (int)(q - (unsigned)y * (unsigned)a.Q);
-    const int n = min(4, a.W - x0);
+    const int n = VEC ? 4 : min(4, a.W - x0);
     const size_t at = (size_t)y * a.W + x0;
     DpQuad<VEC> Qd;
     Qd.load(a, v, at, n);
@@ -222,7 +178,7 @@ __global__ void __launch_bounds__(DP_BLOCK) depth_prior_bwd_kernel(const DpDev a
         const float xf = numf / denf;                                                         // the forward's x
         const double x = (double)xf, p = (double)Qd.p[j], w = (double)Qd.m[j];
         double gx;
-        if (L1) gx = (w * dp_sign(x - (ca * p + cb))) * inv_n;
+        if (L1) gx = (w * osum::sign(x - (ca * p + cb))) * inv_n;
         else gx = -(w * inv_n) * ((p - pbar) * k1 - k2 * (x - xbar));
         gx *= g;
         const double num = (double)numf, den = (double)denf;
@@ -232,8 +188,8 @@ __global__ void __launch_bounds__(DP_BLOCK) depth_prior_bwd_kernel(const DpDev a
     }
     float* __restrict__ gD = a.g_depth[v];
     float* __restrict__ gA = a.g_weights[v];
-    if (gD) dp_store4<VEC>(gD + at, n, dD);                                                   // uniform
-    if (gA) dp_store4<VEC>(gA + at, n, dA);
+    if (gD) osum::store4<VEC>(gD + at, n, dD);                                                // uniform
+    if (gA) osum::store4<VEC>(gA + at, n, dA);
 }
 
 // The dense (N,2) gradient of the L1 table, every element: row rows[v] gets g_v * (-sum w sign(r) p / n, -sum w sign(r) / n) from

@@ -16,9 +16,9 @@
 // (bags_raster/gaussian_normals.py), which spells the same operations in the same order.  The backward recomputes the forward
 // (nothing is saved), holds dL/dc summed over the views in registers and writes dL/dq once; the 9 V view-matrix terms are reduced
 // wave -> workgroup -> one slab row per workgroup, and a second small launch adds the rows in double in a fixed order
-// (bags_common.h: slab_column_sum) and writes the zeros of the fourth row and column.  No atomics: two runs give the same bits, and
+// (ordered_sum.h: slab_column_sum) and writes the zeros of the fourth row and column.  No atomics: two runs give the same bits, and
 // a view's sums are formed from its own terms alone, so they do not depend on its neighbours in the call.
-#include "bags_common.h"
+#include "ordered_sum.h"
 
 #define GN_BLOCK 256
 #define GN_VIEW 12               // staged floats per view: V[i,j], i = 0..3, j = 0..2, at 3 i + j

@@ -17,12 +17,12 @@
 // in double, each gradient rounded once.
 //
 // Forward: workgroup b takes the GR_ROWS rows from b * GR_ROWS on, thread t the rows t, t + 256, ... of them; a lane adds its rows
-// in double, the lanes of a wave by a shuffle butterfly, the four waves in wave order in LDS, and the workgroup leaves one record
-// of 8 doubles (six sums, the count, 0).  The finish kernel adds the records in a fixed order and writes terms (6), count and the
-// stats record (the six raw sums, n, 0).  No atomics, no memset.  Backward: a thread per row, every element of both outputs written
+// in double, the workgroup adds its lanes (ordered_sum.h) and leaves one record of 8 doubles (six sums, the count, and a 0 it
+// writes).  The finish kernel adds the records in index order (ordered_sum.h) and writes terms (6), count and the stats record
+// (the six raw sums, n, 0).  No atomics, no memset.  Backward: a thread per row, every element of both outputs written
 // (an unselected row: zeros); either output may be NULL.  The (P,3) rows are read and written as activations.hip does, element by
 // element: no access is wider than 4 bytes, so any 4-byte-aligned tensor takes the one path there is.
-#include "bags_common.h"
+#include "ordered_sum.h"
 
 #define GR_BLOCK BAGS_GAUSSIAN_REG_BLOCK
 #define GR_ROWS BAGS_GAUSSIAN_REG_ROWS
@@ -117,7 +117,7 @@ __device__ __forceinline__ bool gr_selected(const GrDev& a, const size_t i) { re
 template <bool FILTER>
 __global__ void __launch_bounds__(GR_BLOCK) gaussian_reg_sums_kernel(const GrDev a, double* __restrict__ records)
 {
-    __shared__ double wsum[GR_BLOCK / 64][GR_REC];
+    __shared__ double sh[GR_BLOCK / 64 * GR_REC];
     double acc[GR_N + 1];
 #pragma unroll
     for (int t = 0; t <= GR_N; ++t) acc[t] = 0.0;
@@ -138,40 +138,20 @@ __global__ void __launch_bounds__(GR_BLOCK) gaussian_reg_sums_kernel(const GrDev
             if (w.big[k]) acc[4] += (double)(w.s[k] - a.max_scale);
         if (w.entropy) acc[5] -= (double)w.o * (double)logf(w.o) + (double)w.q * (double)logf(w.q);
     }
-    // every lane is here: lanes -> wave (the butterfly leaves the same total in every lane), waves -> workgroup in wave order
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int t = 0; t <= GR_N; ++t) {
-        double s = acc[t];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d);
-        if (lane == 0) wsum[wave][t] = s;
-    }
-    __syncthreads();
+    osum::block_sum<GR_N + 1>(acc, sh);                                                      // every lane is here
     if (threadIdx.x < GR_REC)
-        records[(size_t)blockIdx.x * GR_REC + threadIdx.x] =
-            ((int)threadIdx.x <= GR_N) ? ((wsum[0][threadIdx.x] + wsum[1][threadIdx.x]) + wsum[2][threadIdx.x]) + wsum[3][threadIdx.x] : 0.0;
+        records[(size_t)blockIdx.x * GR_REC + threadIdx.x] = ((int)threadIdx.x <= GR_N) ? osum::block_total<GR_N + 1>(sh, threadIdx.x) : 0.0;
 }
 
-// One workgroup: the nrec records added in index order -- thread i takes records i, i + 256, ..., a fixed shuffle tree, the waves in
-// wave order -- then the six terms, the count and the stats record.  nrec == 0 (P == 0): zeros.
+// One workgroup: the nrec records added in index order (ordered_sum.h), then the six terms, the count and the stats record.
+// nrec == 0 (P == 0): zeros.
 __global__ void __launch_bounds__(256) gaussian_reg_finish_kernel(const int nrec, const double* __restrict__ records, float* __restrict__ terms,
                                                                   float* __restrict__ count, double* __restrict__ stats)
 {
-    __shared__ double wsum[GR_N + 1][4];
-#pragma unroll
-    for (int c = 0; c <= GR_N; ++c) {
-        double acc = 0.0;
-        for (int s = threadIdx.x; s < nrec; s += 256) acc += records[(size_t)s * GR_REC + c];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d);
-        if ((threadIdx.x & 63) == 0) wsum[c][threadIdx.x >> 6] = acc;
-    }
-    __syncthreads();
-    if (threadIdx.x != 0) return;
+    __shared__ double sh[4 * (GR_N + 1)];
     double S[GR_N + 1];
-#pragma unroll
-    for (int c = 0; c <= GR_N; ++c) S[c] = ((wsum[c][0] + wsum[c][1]) + wsum[c][2]) + wsum[c][3];
+    osum::ordered_rows_sum<GR_N + 1>(records, nrec, GR_REC, sh, S);
+    if (threadIdx.x != 0) return;
     const double n = S[GR_N];
     const double inv_n = n > 0.0 ? 1.0 / n : 0.0, inv_3n = n > 0.0 ? 1.0 / (3.0 * n) : 0.0;
     terms[0] = (float)(S[0] * inv_n);

@@ -12,10 +12,9 @@
 // The shape is depth_prior.hip's: a thread takes a quad of four consecutive pixels of one image row, as one float4 per plane where
 // W % 4 == 0 and every base is 16-byte aligned, element by element otherwise (the same operations, and -ffp-contract=off: the same
 // bits).  The views of a call are grid dimension y.  A view has depth_prior_slots(H, W) workgroups whatever the number of views;
-// each leaves one row of 2 doubles (cnt, sum w l), the lanes of a wave added by a shuffle butterfly and the four waves in wave
-// order, and the finalize kernel adds a view's rows in a fixed order: a view's loss, count and gradients are the same bits in a
-// 16-view call and in a call of its own.  No atomics, no memset.
-#include "bags_common.h"
+// each leaves one row of 2 doubles (cnt, sum w l), and the finalize kernel adds a view's rows in row order (both: ordered_sum.h): a
+// view's loss, count and gradients are the same bits in a 16-view call and in a call of its own.  No atomics, no memset.
+#include "ordered_sum.h"
 
 #define NM_BLOCK BAGS_DEPTH_PRIOR_BLOCK
 #define NM_ROW BAGS_NORMAL_MAP_STATS                 // doubles per partial row (cnt, sum w l) and per stats row (1/cnt or 0, unused)
@@ -34,30 +33,6 @@ struct NmDev {
     float* g_normal[BAGS_MAX_POSE_ROWS];             // backward: any of them NULL
 };
 
-// n elements (1..4) from p; the rest of d is 0
-template <bool VEC> __device__ __forceinline__ void nm_load4(const float* __restrict__ p, const int n, float (&d)[4])
-{
-    if (VEC) {
-        const float4 t = *reinterpret_cast<const float4*>(p);
-        d[0] = t.x; d[1] = t.y; d[2] = t.z; d[3] = t.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) d[j] = (j < n) ? p[j] : 0.0f;
-    }
-}
-template <bool VEC> __device__ __forceinline__ void nm_store4(float* __restrict__ p, const int n, const float (&d)[4])
-{
-    if (VEC) {
-        *reinterpret_cast<float4*>(p) = make_float4(d[0], d[1], d[2], d[3]);
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) if (j < n) p[j] = d[j];
-    }
-}
-
-__device__ __forceinline__ double nm_sign(const double r) { return (double)((r > 0.0) - (r < 0.0)); }
-__device__ __forceinline__ bool nm_finite(const double x) { return x - x == 0.0; }
-
 // the maps of a quad; a lane past the end of a short quad has A = 0 and N = 0: not valid (min_weight > 0)
 template <bool VEC> struct NmQuad {
     float N[3][4], A[4], p[3][4], m[4];
@@ -65,12 +40,12 @@ template <bool VEC> struct NmQuad {
     {
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            nm_load4<VEC>(a.normal[v] + c * a.plane + at, n, N[c]);
-            nm_load4<VEC>(a.prior[v] + c * a.plane + at, n, p[c]);
+            osum::load4<VEC>(a.normal[v] + c * a.plane + at, n, N[c]);
+            osum::load4<VEC>(a.prior[v] + c * a.plane + at, n, p[c]);
         }
-        nm_load4<VEC>(a.weights[v] + at, n, A);
+        osum::load4<VEC>(a.weights[v] + at, n, A);
         const float* __restrict__ mk = a.mask[v];
-        if (mk) nm_load4<VEC>(mk + at, n, m);                                                // uniform
+        if (mk) osum::load4<VEC>(mk + at, n, m);                                             // uniform
         else {
 #pragma unroll
             for (int j = 0; j < 4; ++j) m[j] = 1.0f;
@@ -82,7 +57,7 @@ template <bool VEC> struct NmQuad {
         const double n0 = (double)N[0][j], n1 = (double)N[1][j], n2 = (double)N[2][j];
         const double p0 = (double)p[0][j], p1 = (double)p[1][j], p2 = (double)p[2][j];
         const double nn = n0 * n0 + n1 * n1 + n2 * n2, pp = p0 * p0 + p1 * p1 + p2 * p2;
-        const bool ok = A[j] >= a.min_weight && nm_finite(nn) && nn > a.min_norm_sq && m[j] > 0.0f && nm_finite(pp) && pp > NM_PRIOR_MIN_SQ;
+        const bool ok = A[j] >= a.min_weight && osum::finite(nn) && nn > a.min_norm_sq && m[j] > 0.0f && osum::finite(pp) && pp > NM_PRIOR_MIN_SQ;
         if (!ok) return false;
         const double ln = sqrt(nn), lp = sqrt(pp);
         nh[0] = n0 / ln; nh[1] = n1 / ln; nh[2] = n2 / ln;
@@ -96,7 +71,7 @@ template <bool VEC> struct NmQuad {
 template <bool VEC, bool L1>
 __global__ void __launch_bounds__(NM_BLOCK) normal_map_sums_kernel(const NmDev a, double* __restrict__ partials)
 {
-    __shared__ double wsum[NM_BLOCK / 64][NM_ROW];
+    __shared__ double sh[NM_BLOCK / 64 * NM_ROW];
     const int v = blockIdx.y;
     double acc[NM_ROW] = {0.0, 0.0};
 
@@ -104,7 +79,7 @@ __global__ void __launch_bounds__(NM_BLOCK) normal_map_sums_kernel(const NmDev a
         const unsigned q = tile * NM_BLOCK + threadIdx.x;
         if (q >= a.nquads) continue;
         const int y = (int)(q / (unsigned)a.Q), x0 = 4 * (int)(q - (unsigned)y * (unsigned)a.Q);
-        const int n = min(4, a.W - x0);
+        const int n = VEC ? 4 : min(4, a.W - x0);                                            // (VEC: W % 4 == 0)
         NmQuad<VEC> Qd;
         Qd.load(a, v, (size_t)y * a.W + x0, n);
 #pragma unroll
@@ -118,42 +93,21 @@ __global__ void __launch_bounds__(NM_BLOCK) normal_map_sums_kernel(const NmDev a
             acc[0] += w; acc[1] += w * l;
         }
     }
-    // every lane is here: lanes -> wave (the butterfly leaves the same total in every lane), waves -> workgroup in wave order
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int t = 0; t < NM_ROW; ++t) {
-        double s = acc[t];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d);
-        if (lane == 0) wsum[wave][t] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < NM_ROW)
-        partials[((size_t)v * gridDim.x + blockIdx.x) * NM_ROW + threadIdx.x] =
-            ((wsum[0][threadIdx.x] + wsum[1][threadIdx.x]) + wsum[2][threadIdx.x]) + wsum[3][threadIdx.x];
+    osum::block_sum<NM_ROW>(acc, sh);                                                        // every lane is here
+    if (threadIdx.x < NM_ROW) partials[((size_t)v * gridDim.x + blockIdx.x) * NM_ROW + threadIdx.x] = osum::block_total<NM_ROW>(sh, threadIdx.x);
 }
 
-// One workgroup per view: its nslots partial rows added in slot order -- thread i takes slots i, i + 256, ..., a fixed shuffle
-// tree, the waves in wave order -- then loss, count and the stats row.
+// One workgroup per view: its nslots partial rows added in slot order (ordered_sum.h), then loss, count and the stats row.
 __global__ void __launch_bounds__(256) normal_map_finalize_kernel(const int nslots, const double* __restrict__ partials,
                                                                   float* __restrict__ loss, float* __restrict__ count,
                                                                   double* __restrict__ stats)
 {
-    __shared__ double wsum[NM_ROW][4];
+    __shared__ double sh[4 * NM_ROW];
     const int v = blockIdx.x;
-    const double* __restrict__ rows = partials + (size_t)v * nslots * NM_ROW;
-#pragma unroll
-    for (int c = 0; c < NM_ROW; ++c) {
-        double acc = 0.0;
-        for (int s = threadIdx.x; s < nslots; s += 256) acc += rows[(size_t)s * NM_ROW + c];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d);
-        if ((threadIdx.x & 63) == 0) wsum[c][threadIdx.x >> 6] = acc;
-    }
-    __syncthreads();
+    double S[NM_ROW];
+    osum::ordered_rows_sum<NM_ROW>(partials + (size_t)v * nslots * NM_ROW, nslots, NM_ROW, sh, S);
     if (threadIdx.x != 0) return;
-    const double cnt = ((wsum[0][0] + wsum[0][1]) + wsum[0][2]) + wsum[0][3];
-    const double sum = ((wsum[1][0] + wsum[1][1]) + wsum[1][2]) + wsum[1][3];
+    const double cnt = S[0], sum = S[1];
     const double inv = cnt > 0.0 ? 1.0 / cnt : 0.0;                                           // (a NaN count: no valid pixel)
     loss[v] = (float)(cnt > 0.0 ? sum * inv : 0.0);
     count[v] = (float)(cnt > 0.0 ? cnt : 0.0);
@@ -175,7 +129,7 @@ __global__ void __launch_bounds__(NM_BLOCK) normal_map_bwd_kernel(const NmDev a,
     const double inv = stats[(size_t)v * NM_ROW];
     const double g = (double)g_loss[v];
     const int y = (int)(q / (unsigned)a.Q), x0 = 4 * (int)(q - (unsigned)y * (unsigned)a.Q);
-    const int n = min(4, a.W - x0);
+    const int n = VEC ? 4 : min(4, a.W - x0);
     const size_t at = (size_t)y * a.W + x0;
     NmQuad<VEC> Qd;
     Qd.load(a, v, at, n);
@@ -187,14 +141,14 @@ __global__ void __launch_bounds__(NM_BLOCK) normal_map_bwd_kernel(const NmDev a,
         if (!(inv > 0.0) || !Qd.unit(a, j, nh, ph, inv_len)) continue;
         double u[3];
 #pragma unroll
-        for (int c = 0; c < 3; ++c) u[c] = L1 ? nm_sign(nh[c] - ph[c]) : -ph[c];
+        for (int c = 0; c < 3; ++c) u[c] = L1 ? osum::sign(nh[c] - ph[c]) : -ph[c];
         const double nu = nh[0] * u[0] + nh[1] * u[1] + nh[2] * u[2];
         const double k = (g * ((double)Qd.m[j] * inv)) * inv_len;
 #pragma unroll
         for (int c = 0; c < 3; ++c) d[c][j] = (float)(k * (u[c] - nh[c] * nu));
     }
 #pragma unroll
-    for (int c = 0; c < 3; ++c) nm_store4<VEC>(gN + c * a.plane + at, n, d[c]);
+    for (int c = 0; c < 3; ++c) osum::store4<VEC>(gN + c * a.plane + at, n, d[c]);
 }
 
 static NmDev nm_dev(const BagsNormalMap& a, float* const* g_normal)

@@ -30,17 +30,17 @@
 // bound by their double arithmetic, and a double division costs some ten multiplies.  The views of a call are grid dimension z;
 // their pointers and pinholes arrive by value.  The file is compiled with -ffp-contract=off: only the operations it spells.
 //
-// The sums of a view: a lane adds w l and w of its one pixel in double; the lanes of a wave are added by a shuffle butterfly, the
-// four waves in wave order in LDS, and the workgroup leaves one row of 2 doubles.  A view has tiles_x * tiles_y workgroups whatever
-// the number of views, and the finalize kernel adds its rows in a fixed order: a view's loss, count, stats and gradients are the
-// same bits in a 16-view call and in a call of its own.  No atomics, no memset.
-#include "bags_common.h"
+// The sums of a view: a lane holds w l and w of its one pixel in double, and the workgroup adds its lanes and leaves one row of 2
+// doubles.  A view has tiles_x * tiles_y workgroups whatever the number of views, and the finalize kernel adds its rows in row order
+// (both: ordered_sum.h): a view's loss, count, stats and gradients are the same bits in a 16-view call and in a call of its own.  No
+// atomics, no memset.
+#include "ordered_sum.h"
 
 #define NP_TW BAGS_NORMAL_PRIOR_TILE_W
 #define NP_TH BAGS_NORMAL_PRIOR_TILE_H
 #define NP_BLOCK (NP_TW * NP_TH)
 #define NP_ROW BAGS_NORMAL_PRIOR_STATS               // doubles per partial row and per stats row: (sum w l, sum w) / (1/cnt, cnt)
-static_assert(NP_BLOCK == 256, "four waves: the wave-order sums below name them");
+static_assert(NP_BLOCK == 256, "four waves: block_sum's default");
 
 struct NpDev {
     int H, W;
@@ -127,8 +127,6 @@ __device__ __forceinline__ bool np_prior(const NpDev& a, const int view, const i
     return true;
 }
 
-__device__ __forceinline__ double np_sign(const double r) { return (double)((r > 0.0) - (r < 0.0)); }
-
 // Workgroup (bx, by) of view bz leaves the row (sum w l, sum w) of its tile.
 template <bool L1>
 __global__ void __launch_bounds__(NP_BLOCK) normal_prior_sums_kernel(const NpDev a, double* __restrict__ partials)
@@ -136,7 +134,7 @@ __global__ void __launch_bounds__(NP_BLOCK) normal_prior_sums_kernel(const NpDev
     constexpr int SW = NP_TW + 2;
     __shared__ float zs[SW * (NP_TH + 2)];
     __shared__ double rx[NP_TW + 2], ry[NP_TH + 2];
-    __shared__ double wsum[NP_BLOCK / 64][NP_ROW];
+    __shared__ double sh[NP_BLOCK / 64 * NP_ROW];
     const int view = blockIdx.z;
     const int x0 = blockIdx.x * NP_TW, y0 = blockIdx.y * NP_TH;
     np_stage_tile<1>(zs, rx, ry, a.depth[view], a.weights[view], a.H, a.W, a.min_weight, a.pinhole[view], x0, y0);
@@ -159,49 +157,22 @@ __global__ void __launch_bounds__(NP_BLOCK) normal_prior_sums_kernel(const NpDev
             acc[0] = w * l; acc[1] = w;
         }
     }
-    // every lane is here: lanes -> wave (the butterfly leaves the same total in every lane), waves -> workgroup in wave order
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int t = 0; t < NP_ROW; ++t) {
-        double s = acc[t];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d);
-        if (lane == 0) wsum[wave][t] = s;
-    }
-    __syncthreads();
+    osum::block_sum<NP_ROW>(acc, sh);                                                        // every lane is here
     if (threadIdx.x < NP_ROW) {
         const size_t tile = (size_t)blockIdx.y * gridDim.x + blockIdx.x, ntiles = (size_t)gridDim.x * gridDim.y;
-        partials[((size_t)view * ntiles + tile) * NP_ROW + threadIdx.x] =
-            ((wsum[0][threadIdx.x] + wsum[1][threadIdx.x]) + wsum[2][threadIdx.x]) + wsum[3][threadIdx.x];
+        partials[((size_t)view * ntiles + tile) * NP_ROW + threadIdx.x] = osum::block_total<NP_ROW>(sh, threadIdx.x);
     }
 }
 
-// One workgroup per view: its ntiles partial rows added in tile order -- thread i takes tiles i, i + 256, ..., a fixed shuffle
-// tree, the waves in wave order -- then loss, count and the stats row.
+// One workgroup per view: its ntiles partial rows added in tile order (ordered_sum.h), then loss, count and the stats row.
 __global__ void __launch_bounds__(256) normal_prior_finalize_kernel(const int ntiles, const double* __restrict__ partials, float* __restrict__ loss,
                                                                     float* __restrict__ count, double* __restrict__ stats)
 {
-    __shared__ double wsum[NP_ROW][4];
+    __shared__ double sh[4 * NP_ROW];
     const int v = blockIdx.x;
-    static_assert(NP_ROW == 2, "a partial row is one 16-byte load");
-    const double2* __restrict__ rows = reinterpret_cast<const double2*>(partials) + (size_t)v * ntiles;      // 16-byte aligned (api.hip)
-    double acc[NP_ROW] = {0.0, 0.0};
-#pragma unroll 4
-    for (int s = threadIdx.x; s < ntiles; s += 256) {
-        const double2 r = rows[s];
-        acc[0] += r.x; acc[1] += r.y;
-    }
-#pragma unroll
-    for (int c = 0; c < NP_ROW; ++c) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) acc[c] += __shfl_xor(acc[c], d);
-        if ((threadIdx.x & 63) == 0) wsum[c][threadIdx.x >> 6] = acc[c];
-    }
-    __syncthreads();
-    if (threadIdx.x != 0) return;
     double S[NP_ROW];
-#pragma unroll
-    for (int c = 0; c < NP_ROW; ++c) S[c] = ((wsum[c][0] + wsum[c][1]) + wsum[c][2]) + wsum[c][3];
+    osum::ordered_rows_sum<NP_ROW>(partials + (size_t)v * ntiles * NP_ROW, ntiles, NP_ROW, sh, S);
+    if (threadIdx.x != 0) return;
     const double cnt = S[1];
     const double inv = cnt > 0.0 ? 1.0 / cnt : 0.0;
     loss[v] = (float)(cnt > 0.0 ? S[0] * inv : 0.0);
@@ -242,7 +213,7 @@ __global__ void __launch_bounds__(NP_BLOCK) normal_prior_bwd_kernel(const NpDev 
                 const double n[3] = {g.N[0] * rs, g.N[1] * rs, g.N[2] * rs};
                 double gl[3];
 #pragma unroll
-                for (int k = 0; k < 3; ++k) gl[k] = L1 ? np_sign(n[k] - ph[k]) : -ph[k];
+                for (int k = 0; k < 3; ++k) gl[k] = L1 ? osum::sign(n[k] - ph[k]) : -ph[k];
                 const double ng = (n[0] * gl[0] + n[1] * gl[1]) + n[2] * gl[2];
                 const double s = w * scale;
                 double G[3];

@@ -10,7 +10,7 @@
 //      tiny kernel adds the rows in fp64, so pose gradients are deterministic and do not lose bits to a
 //      half-million-term fp32 chain.
 // The forward quantities are recomputed from the inputs (cheaper than 100+ B/Gaussian of saved state).
-#include "bags_common.h"
+#include "ordered_sum.h"
 #include "sh_basis.h"
 #include "projection.h"
 #include "sh_rows.h"
@@ -547,7 +547,7 @@ preprocess_bwd_kernel(int P, int M, int deg, int W, int H, float tanfovx, float 
     }
 }
 
-// rows -> the five pose tensors, summed in fp64 in a fixed order (bags_common.h: slab_column_sum).  One workgroup per slab column
+// rows -> the five pose tensors, summed in fp64 in a fixed order (ordered_sum.h: slab_column_sum).  One workgroup per slab column
 // (35 used).  (One 1024-thread workgroup for all 40 columns took 10.5 us: 78 dependent-latency-bound loads per thread; here every
 // thread has its 8 loads in flight at once.)
 __global__ void __launch_bounds__(256)

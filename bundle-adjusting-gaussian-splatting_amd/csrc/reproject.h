@@ -1,16 +1,17 @@
 // reproject.h -- what the two losses that carry a pixel of one view into another share (correspondence.hip, warp.hip): the relative
-// transform of an ordered pair and its staging in LDS, the pixel's x_i / x_j / proj, the ordered sums of a workgroup and of a pair, the
-// forward's finalize, the pixel's way back from dL/dproj to dL/dD, dL/dA and the twelve sums, and the chain from those sums to the two
+// transform of an ordered pair and its staging in LDS, the pixel's x_i / x_j / proj, the forward's finalize and the store of a
+// workgroup's twelve sums (the order of every sum: ordered_sum.h), the pixel's way back from dL/dproj to dL/dD, dL/dA and the twelve sums, and the chain from those sums to the two
 // matrix gradients.  One statement each, so that the two losses round every one of them the same way; the formulas are in the header
 // comment of correspondence.hip.  A `Dev` is a kernel's by-value argument struct: H, W, min_weight, min_depth, pin_src, pin_dst, depth,
-// weights, view_src, view_dst (CoDev, WpDev).  Both files are compiled with -ffp-contract=off: only the operations spelled here.
+// weights, view_src, view_dst (CoDev, WpDev).  Both files are compiled with -ffp-contract=off: only the operations spelled here and
+// in ordered_sum.h.
 #pragma once
-#include "bags_common.h"
+#include "ordered_sum.h"
 
 #define RP_CHUNK BAGS_CORRESPONDENCE_CHUNK
 #define RP_ROW BAGS_CORRESPONDENCE_STATS             // doubles per forward partial row and per stats row: (sum w rho, sum w) / (1/cnt, cnt)
 #define RP_SUMS BAGS_CORRESPONDENCE_SUMS             // backward partial sums per workgroup: G_M (9, row-major), g_c (3)
-static_assert(RP_CHUNK == 256, "four waves: the wave-order sums below name them");
+static_assert(RP_CHUNK == 256, "four waves: block_sum's default, and ordered_rows_sum's 256 threads");
 static_assert(RP_SUMS == 12, "G_M and g_c");
 
 struct RpViewGrads {
@@ -110,61 +111,14 @@ __device__ __forceinline__ void rp_project(const double* __restrict__ pin, const
     y = (pin[1] * p.xj[1]) * iz + pin[3];
 }
 
-// N doubles per lane -> N doubles per workgroup in out[0..N) of the first N threads' registers: lanes by a butterfly (the same total in
-// every lane), waves in wave order through LDS.  Every lane of the workgroup calls it.
-template <int N>
-__device__ __forceinline__ void rp_block_sum(double (&acc)[N], double (*wsum)[N])
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int t = 0; t < N; ++t) {
-        double s = acc[t];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d);
-        if (lane == 0) wsum[wave][t] = s;
-    }
-    __syncthreads();
-}
-
-// `n` doubles at `rows` with stride 1 added in a fixed order by a workgroup of 256: thread i takes i, i + 256, ..., a fixed shuffle
-// tree, the waves in wave order; the total is returned to thread 0 (other threads: unspecified).  wsum: 4 doubles of LDS.
-__device__ __forceinline__ double rp_ordered_sum(const double* __restrict__ rows, const int n, double* __restrict__ wsum)
-{
-    double acc = 0.0;
-#pragma unroll 4
-    for (int s = threadIdx.x; s < n; s += 256) acc += rows[s];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d);
-    __syncthreads();                                                                          // wsum of the call before is read
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    return ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
-}
-
 // The forward's second kernel, a workgroup of 256 per pair k: its nchunks partial rows (sum w rho, sum w) added in chunk order, then
-// loss, count and the stats row (1/cnt, cnt).  wsum: RP_ROW x 4 doubles of LDS.
+// loss, count and the stats row (1/cnt, cnt).  sh: 4 * RP_ROW doubles of LDS.
 __device__ __forceinline__ void rp_finalize(const int k, const int nchunks, const double* __restrict__ partials, float* __restrict__ loss,
-                                            float* __restrict__ count, double* __restrict__ stats, double (*wsum)[4])
+                                            float* __restrict__ count, double* __restrict__ stats, double* __restrict__ sh)
 {
-    static_assert(RP_ROW == 2, "a partial row is one 16-byte load");
-    const double2* __restrict__ rows = reinterpret_cast<const double2*>(partials) + (size_t)k * nchunks;       // 16-byte aligned (api.hip)
-    double acc[RP_ROW] = {0.0, 0.0};
-#pragma unroll 4
-    for (int s = threadIdx.x; s < nchunks; s += 256) {
-        const double2 r = rows[s];
-        acc[0] += r.x; acc[1] += r.y;
-    }
-#pragma unroll
-    for (int c = 0; c < RP_ROW; ++c) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) acc[c] += __shfl_xor(acc[c], d);
-        if ((threadIdx.x & 63) == 0) wsum[c][threadIdx.x >> 6] = acc[c];
-    }
-    __syncthreads();
-    if (threadIdx.x != 0) return;
     double S[RP_ROW];
-#pragma unroll
-    for (int c = 0; c < RP_ROW; ++c) S[c] = ((wsum[c][0] + wsum[c][1]) + wsum[c][2]) + wsum[c][3];
+    osum::ordered_rows_sum<RP_ROW>(partials + (size_t)k * nchunks * RP_ROW, nchunks, RP_ROW, sh, S);
+    if (threadIdx.x != 0) return;
     const double cnt = S[1];
     const double inv = cnt > 0.0 ? 1.0 / cnt : 0.0;
     loss[k] = (float)(cnt > 0.0 ? S[0] * inv : 0.0);
@@ -199,24 +153,28 @@ __device__ __forceinline__ void rp_pixel_back(const RpPoint& pt, const double* _
     }
 }
 
-// The workgroup's twelve sums into sums[(pair * 12 + t) * nchunks + chunk].  Every lane of the workgroup calls it.
-__device__ __forceinline__ void rp_store_sums(double (&acc)[RP_SUMS], double (*wsum)[RP_SUMS], const int pair, double* __restrict__ sums)
+// The workgroup's twelve sums into sums[(pair * 12 + t) * nchunks + chunk].  Every lane of the workgroup calls it.  sh: 4 * RP_SUMS
+// doubles of LDS.
+__device__ __forceinline__ void rp_store_sums(const double (&acc)[RP_SUMS], double* __restrict__ sh, const int pair, double* __restrict__ sums)
 {
-    rp_block_sum<RP_SUMS>(acc, wsum);
-    if (threadIdx.x < RP_SUMS)
-        sums[((size_t)pair * RP_SUMS + threadIdx.x) * gridDim.x + blockIdx.x] =
-            ((wsum[0][threadIdx.x] + wsum[1][threadIdx.x]) + wsum[2][threadIdx.x]) + wsum[3][threadIdx.x];
+    osum::block_sum<RP_SUMS>(acc, sh);
+    if (threadIdx.x < RP_SUMS) sums[((size_t)pair * RP_SUMS + threadIdx.x) * gridDim.x + blockIdx.x] = osum::block_total<RP_SUMS>(sh, threadIdx.x);
 }
 
 // The backward's second kernel, a workgroup of 256 per pair: the twelve sums of its chunks added in a fixed order, then the chain to
 // the two (4,4) gradients in double, each element rounded once.  A degenerate pair (det(Ai) zero or not finite) gets exact zeros.
-// oi / oj == nullptr: not wanted.  wsum: 4 doubles of LDS.
+// oi / oj == nullptr: not wanted.  sh: 4 doubles of LDS, used for one sum after the other.
 __device__ __forceinline__ void rp_views_chain(const float* __restrict__ Vi, const float* __restrict__ Vj, const int pair, const int nchunks,
-                                               const double* __restrict__ sums, float* __restrict__ oi, float* __restrict__ oj, double* __restrict__ wsum)
+                                               const double* __restrict__ sums, float* __restrict__ oi, float* __restrict__ oj, double* __restrict__ sh)
 {
     double S[RP_SUMS];
 #pragma unroll
-    for (int t = 0; t < RP_SUMS; ++t) S[t] = rp_ordered_sum(sums + ((size_t)pair * RP_SUMS + t) * nchunks, nchunks, wsum);
+    for (int t = 0; t < RP_SUMS; ++t) {
+        double one[1];
+        __syncthreads();                                                                      // sh of the sum before is read
+        osum::ordered_rows_sum<1>(sums + ((size_t)pair * RP_SUMS + t) * nchunks, nchunks, 1, sh, one);
+        S[t] = one[0];
+    }
     if (threadIdx.x != 0) return;
     double gVi[4][4], gVj[4][4];
 #pragma unroll

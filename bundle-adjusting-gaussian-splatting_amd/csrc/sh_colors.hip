@@ -30,7 +30,7 @@
 // sh_rows.h (shr_stage, shr_span), which preprocess_bwd.hip shares.  The direction gradient is spelled in each backward kernel: as a function of its own it compiles to other code
 // (profiles/sh_colors/NOTES.md), so a change to it is made in both.  They share statements, not kernels: the views backward stages
 // 51200 bytes of LDS and needs twice the registers of the single-view one, which is render()'s default path.
-#include "bags_common.h"
+#include "ordered_sum.h"
 #include "sh_basis.h"
 #include "sh_rows.h"
 
@@ -171,7 +171,7 @@ sh_colors_bwd_kernel(const ShcIn A, const float* __restrict__ g_rgb, float* __re
     }
 }
 
-// slab rows -> dL/dcampos in fp64, one workgroup per component (bags_common.h: slab_column_sum, pose_reduce_kernel's sum)
+// slab rows -> dL/dcampos in fp64, one workgroup per component (ordered_sum.h: slab_column_sum, pose_reduce_kernel's sum)
 __device__ __forceinline__ void shc_campos_reduce(const float* __restrict__ slab, const int nblocks, const int t, float* __restrict__ g_campos)
 {
     const double sum = slab_column_sum(slab, nblocks, SH_SLAB, t);

@@ -26,15 +26,15 @@
 // a usable value is never NaN, so that is the flag, and a stencil that leaves the image is invalid by it.  The pixel weight and the
 // guide are staged beside it as floats.  Every stencil belongs to the workgroup of its anchor (order 1) or centre (order 2).
 //
-// The sums of a view: a lane adds its two stencils in double; the lanes of a wave are added by a shuffle butterfly, the four waves
-// in wave order in LDS, and the workgroup leaves one row of 6 doubles (S, cnt, T per direction).  The finalize kernel adds a view's
-// rows in a fixed order.  The mean of `normalize` is one launch in front: smooth_mean_slots(H, W) workgroups per view each leave
+// The sums of a view: a lane holds its two stencils in double, and the workgroup adds its lanes and leaves one row of 6 doubles (S,
+// cnt, T per direction; T a zero it writes where not normalised).  The finalize kernel adds a view's rows in row order (both:
+// ordered_sum.h).  The mean of `normalize` is one launch in front: smooth_mean_slots(H, W) workgroups per view each leave
 // (sum x, n) of a contiguous run of pixels, and every workgroup of the sums kernel (and the finalize kernel) adds those rows with the
-// same tree (wave 0 alone, one barrier), so mu is the same bits everywhere.  No atomics, no memset: a view's loss, count, stats and
+// same tree (sm_mean: wave 0 alone, one barrier), so mu is the same bits everywhere.  No atomics, no memset: a view's loss, count, stats and
 // gradients are the same bits in a 16-view call and in a call of its own.  exp is evaluated in float32 (expf), everything else after the loads in double.  There is
 // one element-by-element instance of each kernel (no float4 twin); the file is compiled with -ffp-contract=off so that the decisions
 // (|N|^2 > min_norm^2, finite g) are the statement's and the backward forms the forward's t: only the operations it spells.
-#include "bags_common.h"
+#include "ordered_sum.h"
 
 #define SM_TW BAGS_SMOOTH_TILE_W
 #define SM_TH BAGS_SMOOTH_TILE_H
@@ -42,7 +42,7 @@
 #define SM_ROW BAGS_SMOOTH_PARTIALS                  // doubles per partial row: (S, cnt, T) of x, then of y
 #define SM_STATS BAGS_SMOOTH_STATS                   // doubles per stats row: 1/cnt_x, 1/cnt_y, 1/mu, n, T, cnt_x, cnt_y, mu
 #define SM_SLOTS BAGS_SMOOTH_MEAN_SLOTS
-static_assert(SM_BLOCK == 256, "four waves: the wave-order sums below name them");
+static_assert(SM_BLOCK == 256, "four waves: block_sum's default, and ordered_rows_sum's 256 threads");
 static_assert(SM_ROW == 6 && SM_STATS == 8, "the rows are spelled out below");
 
 struct SmDev {
@@ -63,8 +63,6 @@ struct SmDev {
 };
 
 __device__ __forceinline__ double sm_nan() { return __builtin_nan(""); }
-__device__ __forceinline__ bool sm_finite(const double x) { return x - x == 0.0; }
-__device__ __forceinline__ double sm_sign(const double r) { return (double)((r > 0.0) - (r < 0.0)); }
 
 // x of the pixel at `at`, which is inside the image; NaN where it is not usable
 __device__ __forceinline__ double sm_depth_x(const SmDev& a, const float* __restrict__ D, const float* __restrict__ A,
@@ -74,7 +72,7 @@ __device__ __forceinline__ double sm_depth_x(const SmDev& a, const float* __rest
     const float m = mk ? mk[at] : 1.0f;                                                       // uniform
     if (!(w >= a.min_weight && d > 0.0f && m > 0.0f)) return sm_nan();
     const float x = a.inverse ? w / d : d / w;
-    return (x - x == 0.0f) ? (double)x : sm_nan();
+    return osum::finite(x) ? (double)x : sm_nan();
 }
 
 // The tile at (x0, y0) with HL pixels in front and HR behind, row stride SM_TW + HL + HR: the field channel-major in Fs, the pixel
@@ -105,7 +103,7 @@ __device__ __forceinline__ void sm_stage(const SmDev& a, const int view, const i
             } else {
                 const double n0 = (double)fp[at], n1 = (double)fp[plane + at], n2 = (double)fp[2 * plane + at];
                 const double nn = n0 * n0 + n1 * n1 + n2 * n2;
-                if (A[at] >= a.min_weight && sm_finite(nn) && nn > a.min_norm_sq && m > 0.0f) {
+                if (A[at] >= a.min_weight && osum::finite(nn) && nn > a.min_norm_sq && m > 0.0f) {
                     const double inv = 1.0 / sqrt(nn);
                     f[0] = n0 * inv; f[C > 1 ? 1 : 0] = n1 * inv; f[C > 2 ? 2 : 0] = n2 * inv;
                 }
@@ -135,7 +133,7 @@ __device__ __forceinline__ bool sm_stencil(const SmDev& a, const double* __restr
         double g = 0.0;
         for (int k = 0; k < a.cg; ++k) g += fabs((double)gs[k * NP + hi] - (double)gs[k * NP + lo]);
         g = g * a.inv_gn;                                                                     // the mean; order 2: over two pixels
-        if (!sm_finite(g)) return false;
+        if (!osum::finite(g)) return false;
         e = (double)expf((float)(-(a.gamma * g)));
     }
     float m = fminf(ms[lo], ms[hi]);
@@ -154,44 +152,25 @@ __device__ __forceinline__ bool sm_stencil(const SmDev& a, const double* __restr
 __device__ __forceinline__ double sm_rho(const SmDev& a, const double t, double& dr)
 {
     if (a.l2) { dr = 2.0 * t; return t * t; }                                                 // uniform
-    if (a.eps == 0.0) { dr = sm_sign(t); return fabs(t); }
+    if (a.eps == 0.0) { dr = osum::sign(t); return fabs(t); }
     const double r = sqrt(t * t + a.eps * a.eps);
     dr = t / r;
     return r - a.eps;
-}
-
-// `n` doubles per lane -> the same total in every thread of the workgroup: a butterfly, then the four waves in wave order.
-// sh: [n][4] doubles of LDS; the caller's data in sh must be dead (a barrier stands in front of the write).
-template <int N>
-__device__ __forceinline__ void sm_block_sum(double (&acc)[N], double (*sh)[4])
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) acc[k] += __shfl_xor(acc[k], d);
-    }
-    __syncthreads();
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) sh[k][wave] = acc[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; ++k) acc[k] = ((sh[k][0] + sh[k][1]) + sh[k][2]) + sh[k][3];
 }
 
 // 1 / mu; 0 where the view has no usable pixel or no mean to divide by: every t is 0 then, and so are the loss and the gradients
 __device__ __forceinline__ double sm_inv_mu(const double sum, const double n, double& mu)
 {
     mu = n > 0.0 ? sum / n : 0.0;
-    return (n > 0.0 && sm_finite(mu) && mu != 0.0) ? 1.0 / mu : 0.0;
+    return (n > 0.0 && osum::finite(mu) && mu != 0.0) ? 1.0 / mu : 0.0;
 }
 
 // (1 / mu, mu, n) of a view from its mean rows, the same bits in every workgroup that calls this: lane l of wave 0 adds rows l,
-// l + 64, ..., a butterfly leaves the wave's total, and one barrier hands it to the other waves through sh (doubles of LDS whose
-// earlier contents are dead).  The rows are 16 bytes each and 16-byte aligned (api.hip).
-__device__ __forceinline__ void sm_mean(const SmDev& a, const double* __restrict__ rows, double (*sh)[4], double& inv_mu, double& mu, double& n)
+// l + 64, ..., a butterfly leaves the wave's total, and one barrier hands it to the other waves through sh (3 doubles of LDS whose
+// earlier contents are dead).  The rows are 16 bytes each and 16-byte aligned (api.hip).  Not ordered_rows_sum, on purpose: every
+// workgroup of the sums kernel runs this in front of its tile, and one wave with one barrier is what that costs least; the order
+// (64 rows apart, one wave) is this operator's own and its bits are promised.
+__device__ __forceinline__ void sm_mean(const SmDev& a, const double* __restrict__ rows, double* __restrict__ sh, double& inv_mu, double& mu, double& n)
 {
     if (threadIdx.x < 64) {
         const double2* __restrict__ r2 = reinterpret_cast<const double2*>(rows);
@@ -208,18 +187,18 @@ __device__ __forceinline__ void sm_mean(const SmDev& a, const double* __restrict
         }
         if (threadIdx.x == 0) {                                                               // the two divisions once per workgroup
             double m;
-            sh[0][0] = sm_inv_mu(acc[0], acc[1], m);
-            sh[0][1] = m; sh[0][2] = acc[1];
+            sh[0] = sm_inv_mu(acc[0], acc[1], m);
+            sh[1] = m; sh[2] = acc[1];
         }
     }
     __syncthreads();
-    inv_mu = sh[0][0]; mu = sh[0][1]; n = sh[0][2];
+    inv_mu = sh[0]; mu = sh[1]; n = sh[2];
 }
 
 // Workgroup `slot` of view blockIdx.y leaves (sum x, n) of the usable pixels among its run of mean_chunk pixels.
 __global__ void __launch_bounds__(SM_BLOCK) smooth_mean_kernel(const SmDev a, double* __restrict__ mean_rows)
 {
-    __shared__ double sh[2][4];
+    __shared__ double sh[4 * 2];
     const int view = blockIdx.y;
     const size_t HW = (size_t)a.H * a.W;
     const size_t begin = (size_t)blockIdx.x * a.mean_chunk;
@@ -232,8 +211,8 @@ __global__ void __launch_bounds__(SM_BLOCK) smooth_mean_kernel(const SmDev a, do
         const double x = sm_depth_x(a, D, A, mk, i);
         if (x == x) { acc[0] += x; acc[1] += 1.0; }
     }
-    sm_block_sum<2>(acc, sh);
-    if (threadIdx.x < 2) mean_rows[((size_t)view * a.mean_slots + blockIdx.x) * 2 + threadIdx.x] = acc[threadIdx.x];
+    osum::block_sum<2>(acc, sh);
+    if (threadIdx.x < 2) mean_rows[((size_t)view * a.mean_slots + blockIdx.x) * 2 + threadIdx.x] = osum::block_total<2>(sh, threadIdx.x);
 }
 
 // Workgroup (bx, by) of view bz leaves the row (S_x, cnt_x, T_x, S_y, cnt_y, T_y) of the stencils its tile's pixels anchor.
@@ -243,7 +222,7 @@ __global__ void __launch_bounds__(SM_BLOCK) smooth_sums_kernel(const SmDev a, co
     constexpr int HL = ORDER - 1, HR = 1, SW = SM_TW + HL + HR, SH = SM_TH + HL + HR, NP = SW * SH;
     __shared__ double Fs[C * NP];
     __shared__ float ms[NP], gs[3 * NP];
-    __shared__ double sh[SM_ROW][4];
+    __shared__ double sh[4 * SM_ROW];
     const int view = blockIdx.z;
     const int x0 = blockIdx.x * SM_TW, y0 = blockIdx.y * SM_TH;
     sm_stage<C, HL, HR>(a, view, x0, y0, Fs, ms, gs);
@@ -272,39 +251,34 @@ __global__ void __launch_bounds__(SM_BLOCK) smooth_sums_kernel(const SmDev a, co
             acc[3 * dir + 2] = we * (tt * (1.0 / (double)C));
         }
     }
+    // (sh: sm_mean's reads of it are behind the barrier above)
+    const int t = threadIdx.x;
+    double out;
     if (NORM) {
-        sm_block_sum<SM_ROW>(acc, sh);
+        osum::block_sum<SM_ROW>(acc, sh);
+        out = t < SM_ROW ? osum::block_total<SM_ROW>(sh, t) : 0.0;
     } else {                                                                                  // T is read only where normalised: zeros
-        double four[4] = {acc[0], acc[1], acc[3], acc[4]};
-        sm_block_sum<4>(four, sh);
-        acc[0] = four[0]; acc[1] = four[1]; acc[2] = 0.0; acc[3] = four[2]; acc[4] = four[3]; acc[5] = 0.0;
+        const double four[4] = {acc[0], acc[1], acc[3], acc[4]};
+        osum::block_sum<4>(four, sh);
+        out = (t < SM_ROW && t % 3 != 2) ? osum::block_total<4>(sh, t - t / 3) : 0.0;         // columns 0, 1, 3, 4
     }
-    if (threadIdx.x < SM_ROW) {
+    if (t < SM_ROW) {
         const size_t tile = (size_t)blockIdx.y * gridDim.x + blockIdx.x, ntiles = (size_t)gridDim.x * gridDim.y;
-        double out = acc[0];
-#pragma unroll
-        for (int k = 1; k < SM_ROW; ++k) out = (int)threadIdx.x == k ? acc[k] : out;
-        partials[((size_t)view * ntiles + tile) * SM_ROW + threadIdx.x] = out;
+        partials[((size_t)view * ntiles + tile) * SM_ROW + t] = out;
     }
 }
 
-// One workgroup per view: its ntiles partial rows added in tile order -- thread i takes tiles i, i + 256, ..., then the block sum --
-// and, where normalised, its mean; then loss, count and the stats row.
+// One workgroup per view: its ntiles partial rows added in tile order (ordered_sum.h) and, where normalised, its mean; then loss,
+// count and the stats row.
 __global__ void __launch_bounds__(SM_BLOCK) smooth_finalize_kernel(const SmDev a, const int ntiles, const int normalised,
                                                                    const double* __restrict__ partials, const double* __restrict__ mean_rows,
                                                                    float* __restrict__ loss, float* __restrict__ count, double* __restrict__ stats)
 {
-    __shared__ double sh[SM_ROW][4];
-    __shared__ double shm[2][4];
+    __shared__ double sh[4 * SM_ROW];
+    __shared__ double shm[2 * 4];
     const int v = blockIdx.x;
-    const double* __restrict__ rows = partials + (size_t)v * ntiles * SM_ROW;
-    double acc[SM_ROW] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-#pragma unroll 4
-    for (int s = threadIdx.x; s < ntiles; s += SM_BLOCK) {
-#pragma unroll
-        for (int k = 0; k < SM_ROW; ++k) acc[k] += rows[(size_t)s * SM_ROW + k];
-    }
-    sm_block_sum<SM_ROW>(acc, sh);
+    double acc[SM_ROW];
+    osum::ordered_rows_sum<SM_ROW>(partials + (size_t)v * ntiles * SM_ROW, ntiles, SM_ROW, sh, acc);
     double inv_mu = 1.0, mu = 1.0, n = 0.0;
     if (normalised)                                                                           // uniform
         sm_mean(a, mean_rows + (size_t)v * a.mean_slots * 2, shm, inv_mu, mu, n);

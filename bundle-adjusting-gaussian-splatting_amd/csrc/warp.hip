@@ -143,7 +143,7 @@ __global__ void __launch_bounds__(WP_CHUNK) warp_sums_kernel(const WpDev a, doub
 {
     __shared__ double Mc[12];
     __shared__ int ok;
-    __shared__ double wsum[WP_CHUNK / 64][WP_ROW];
+    __shared__ double sh[WP_CHUNK / 64 * WP_ROW];
     const int pair = blockIdx.y;
     rp_stage_transform(a, pair, Mc, &ok);
     const long long npix = (long long)a.H * a.W;
@@ -158,18 +158,16 @@ __global__ void __launch_bounds__(WP_CHUNK) warp_sums_kernel(const WpDev a, doub
             acc[0] = rs.w * rs.rho; acc[1] = rs.w;
         }
     }
-    rp_block_sum<WP_ROW>(acc, wsum);
-    if (threadIdx.x < WP_ROW)
-        partials[((size_t)pair * gridDim.x + blockIdx.x) * WP_ROW + threadIdx.x] =
-            ((wsum[0][threadIdx.x] + wsum[1][threadIdx.x]) + wsum[2][threadIdx.x]) + wsum[3][threadIdx.x];
+    osum::block_sum<WP_ROW>(acc, sh);
+    if (threadIdx.x < WP_ROW) partials[((size_t)pair * gridDim.x + blockIdx.x) * WP_ROW + threadIdx.x] = osum::block_total<WP_ROW>(sh, threadIdx.x);
 }
 
 // One workgroup per pair: its nchunks partial rows added in chunk order, then loss, count and the stats row.
 __global__ void __launch_bounds__(256) warp_finalize_kernel(const int nchunks, const double* __restrict__ partials, float* __restrict__ loss,
                                                             float* __restrict__ count, double* __restrict__ stats)
 {
-    __shared__ double wsum[WP_ROW][4];
-    rp_finalize(blockIdx.x, nchunks, partials, loss, count, stats, wsum);
+    __shared__ double sh[4 * WP_ROW];
+    rp_finalize(blockIdx.x, nchunks, partials, loss, count, stats, sh);
 }
 
 // dL/dD and dL/dA of every pixel of the chunk (zeros where the pixel is not valid), each rounded once from double, and -- SUMS --
@@ -181,7 +179,7 @@ __global__ void __launch_bounds__(WP_CHUNK) warp_bwd_kernel(const WpDev a, const
 {
     __shared__ double Mc[12];
     __shared__ int ok;
-    __shared__ double wsum[WP_CHUNK / 64][WP_SUMS];
+    __shared__ double sh[WP_CHUNK / 64 * WP_SUMS];
     const int pair = blockIdx.y;
     rp_stage_transform(a, pair, Mc, &ok);
     const long long npix = (long long)a.H * a.W;
@@ -208,15 +206,15 @@ __global__ void __launch_bounds__(WP_CHUNK) warp_bwd_kernel(const WpDev a, const
         if (gA) gA[p] = dA;
     }
     if (!SUMS) return;
-    rp_store_sums(acc, wsum, pair, sums);
+    rp_store_sums(acc, sh, pair, sums);
 }
 
 // One workgroup per pair: the twelve sums of its chunks, then the chain to the two (4,4) gradients (reproject.h)
 __global__ void __launch_bounds__(256) warp_views_kernel(const WpDev a, const RpViewGrads g, const int nchunks, const double* __restrict__ sums)
 {
-    __shared__ double wsum[4];
+    __shared__ double sh[4];
     const int pair = blockIdx.x;
-    rp_views_chain(a.view_src[pair], a.view_dst[pair], pair, nchunks, sums, g.src[pair], g.dst[pair], wsum);
+    rp_views_chain(a.view_src[pair], a.view_dst[pair], pair, nchunks, sums, g.src[pair], g.dst[pair], sh);
 }
 
 // The warped image (C,H,W) and valid (H,W) of the first pair: S_c where the pixel is solid, x_j.z >= min_depth, inside, visible and

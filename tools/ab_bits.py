@@ -4,7 +4,7 @@ commit's, built beforehand as tools/ab_lib.sh describes).  For a change that mus
 instruction-identical to the parent's (csrc/projection.h: the projection chain shared by K1 and K9), so that results have to carry
 what assembly identity cannot.
 
-    tools/ab_bits.py <alternative .so> [--out DIR] [--timeout SECONDS]
+    tools/ab_bits.py <alternative .so> [--out DIR] [--timeout SECONDS]        (--check-rows: the CPU checks alone)
 
 This process never touches the GPU.  It starts three fresh children one after the other, each under its own `timeout`: the
 alternative (through BAGS_RASTER_LIB) twice, then the product, and stops at the first one that does not exit 0.  Every child runs
@@ -31,7 +31,18 @@ GaussianBag.densify_and_prune (P in {63, 1001}, N = 2 and, at 1001, N = 3; the c
 generator; with and without optimizer state) and GaussianBag.add_new / relocate (P in {64, 65, 257, 4099}, SH degree 0 and 3, with
 and without state, ``sampled`` given: the multinomial draw does not repeat at large P and must not decide a comparison).  Saved:
 every parameter, both moments, the three statistics, provenance and the returned counts.  densify_and_prune at degree 0 runs on
-the product only (before row_rebuild.h the call raised there): it must run, and is not compared."""
+the product only (before row_rebuild.h the call raised there): it must run, and is not compared.
+
+Since csrc/ordered_sum.h (the ordered double sums and the quad access shared by the fused losses) the list also holds one ``kind``
+per family -- depth_prior, normal_map, appearance, alpha, normal_prior, smooth, correspondence, warp, gaussian_reg, bilagrid and
+bilagrid_tv -- each forward and backward with every gradient asked for; saved: the loss (or the output), the count, every gradient
+and, where the wrapper keeps it for its backward, the stats rows.  Inputs are the tests' case modules' (tests/*_cases.py) at shapes
+chosen for the sums: an image whose width is no multiple of 4 and whose last workgroup is partly filled, a shape whose finalize sees
+fewer than 256 partial rows and one that sees more than 256 and no multiple of 256 (checked on the CPU, against the library's own
+workspace size functions, before any child starts), the float4 and the element-by-element instance (the same case 4 bytes into its
+allocations), every template instance of a family (L1 / Pearson, the four alpha modes, smooth's C x ORDER x NORM, gaussian_reg with
+and without the filter, SUMS on and off in appearance and the reprojection backwards, both LMAX of the grid gradient), V = 1 and 3.
+alpha's finalize and smooth's mean keep orders of their own (256 rows, 512 at most) and have no such row cases."""
 import argparse
 import itertools
 import os
@@ -93,7 +104,252 @@ def case_list():
     for kind, P, deg, state in itertools.product(("add_new", "relocate"), (64, 65, 257, 4099), (0, 3), (True, False)):
         resize(kind, f"{kind}_p{P}_deg{deg}_{'state' if state else 'stateless'}", P, 120 + deg, deg=deg, state=state)
     resize("densify", "dens_p65_deg0", 65, 1, N=2, given=True, state=True, deg=0, product_only=True)
+    # csrc/ordered_sum.h: the fused losses.  `inst`: the template instance; `rows`: what the finalize must see (few / many / None)
+    SHORT, WHOLE, TILED, PIXELS = (17, 67), (37, 260), (131, 515), (259, 257)      # W % 4 != 0 | W % 4 == 0 | 17 x 17 tiles | 261 chunks
+    QUADS = (1030, 1028)                                                             # 1035 tiles of 256 quads: 259 rows
+
+    def loss(kind, name, H=0, W=0, V=1, offset=False, rows=None, **kw):
+        add(f"{kind}_{name}", 0, 0)
+        cases[-1].update(kind=kind, H=H, W=W, V=V, offset=offset, rows=rows, **kw)
+    for mode, space in (("pearson", "inverse"), ("l1", "depth")):
+        loss("depth_prior", f"{mode}_short_v3", *SHORT, 3, rows="few", mode=mode, space=space, inst=(mode, False))
+        loss("depth_prior", f"{mode}_vec_v3", *WHOLE, 3, mode=mode, space=space, inst=(mode, True))
+        loss("depth_prior", f"{mode}_offset_v1", *WHOLE, 1, offset=True, mode=mode, space=space, inst=(mode, False))
+    loss("depth_prior", "l1_many_v1", *QUADS, 1, rows="many", mode="l1", space="inverse", inst=("l1", True))
+    for mode in ("cos", "l1"):
+        loss("normal_map", f"{mode}_short_v3", *SHORT, 3, rows="few", mode=mode, inst=(mode, False))
+        loss("normal_map", f"{mode}_vec_v3", *WHOLE, 3, mode=mode, inst=(mode, True))
+        loss("normal_map", f"{mode}_offset_v1", *WHOLE, 1, offset=True, mode=mode, inst=(mode, False))
+    loss("normal_map", "cos_many_v1", *QUADS, 1, rows="many", mode="cos", inst=("cos", True))
+    for sums in (True, False):
+        tag = "table" if sums else "images_only"
+        loss("appearance", f"{tag}_short_v3", *SHORT, 3, rows="few" if sums else None, sums=sums, inst=(sums, False))
+        loss("appearance", f"{tag}_vec_v3", *WHOLE, 3, sums=sums, inst=(sums, True))
+        loss("appearance", f"{tag}_offset_v1", *WHOLE, 1, offset=True, sums=sums, inst=(sums, False))
+    loss("appearance", "table_many_v1", *QUADS, 1, rows="many", sums=True, inst=(True, True))
+    for mode in ("bce", "l1", "l2", "entropy"):                  # (515, 1028): a span of 518 quads, the second trip of a workgroup of 512
+        for H, W, V, offset in ((5, 7, 3, False), (33, 70, 3, False), (33, 70, 1, True), (515, 1028, 1, False)):
+            loss("alpha", f"{mode}_{H}x{W}_v{V}" + ("_offset" if offset else ""), H, W, V, offset=offset, mode=mode, inst=(mode, not offset))
+    for mode in ("cos", "l1"):
+        loss("normal_prior", f"{mode}_short_v3", *SHORT, 3, rows="few", mode=mode, inst=mode)
+        loss("normal_prior", f"{mode}_many_v1", *TILED, 1, rows="many", mode=mode, inst=mode)
+    for normals, order, normalize in ((False, 1, True), (False, 2, True), (False, 1, False), (False, 2, False), (True, 1, False), (True, 2, False)):
+        tag = f"{'normal' if normals else 'depth'}_o{order}" + ("_norm" if normalize else "")
+        loss("smooth", f"{tag}_short_v3", *SHORT, 3, rows="few", normals=normals, order=order, normalize=normalize, inst=(normals, order, normalize))
+        loss("smooth", f"{tag}_many_v1", *TILED, 1, rows="many", normals=normals, order=order, normalize=normalize, inst=(normals, order, normalize))
+    for sums in (True, False):
+        tag = "views" if sums else "maps_only"
+        loss("correspondence", f"{tag}_short_v3", *SHORT, 3, rows="few" if sums else None, sums=sums, delta=1.0, inst=sums)
+        loss("correspondence", f"{tag}_many_v1", *PIXELS, 1, rows="many" if sums else None, sums=sums, delta=float("inf"), inst=sums)
+        for C in (1, 3):
+            loss("warp", f"c{C}_{tag}_short_v3", *SHORT, 3, rows="few" if sums else None, sums=sums, C=C, inst=(C, sums))
+        loss("warp", f"c3_{tag}_many_v1", *PIXELS, 1, rows="many" if sums else None, sums=sums, C=3, inst=(3, sums))
+    for filtered, selected in itertools.product((False, True), repeat=2):
+        for P, rows in ((257, "few"), (3 * 1024 + 17, "few"), (256 * 1024 + 1000, "many")):
+            if rows == "few" or selected == filtered:
+                loss("gaussian_reg", f"p{P}_{'filter' if filtered else 'plain'}_{'select' if selected else 'all'}", P=P, rows=rows, filtered=filtered,
+                     selected=selected, inst=filtered)
+    for grid in ((16, 16, 8), (3, 2, 12)):                       # L <= 8 and L > 8: the two instances of the grid gradient
+        loss("bilagrid", "g%dx%dx%d_v3" % grid, *SHORT, 3, grid=grid, inst=grid[2] > 8)
+        loss("bilagrid", "g%dx%dx%d_v1" % grid, *SHORT, 1, grid=grid, inst=grid[2] > 8)
+    loss("bilagrid_tv", "n23_5x4x3", grid=(5, 4, 3), N=23, rows="few", inst=None)
+    loss("bilagrid_tv", "n4_16x16x8", grid=(16, 16, 8), N=4, rows="many", inst=None)
     return cases
+
+
+# every template instance a family has, as its cases' `inst`: a stable case of each must have run
+LOSS_INSTANCES = {
+    "depth_prior": {(m, vec) for m in ("pearson", "l1") for vec in (False, True)},               # <VEC, L1>
+    "normal_map": {(m, vec) for m in ("cos", "l1") for vec in (False, True)},                    # <VEC, L1>
+    "appearance": {(sums, vec) for sums in (False, True) for vec in (False, True)},              # the backward's <VEC, SUMS>
+    "alpha": {(m, vec) for m in ("bce", "l1", "l2", "entropy") for vec in (False, True)},        # <VEC, MODE>
+    "normal_prior": {"cos", "l1"},                                                               # <L1>
+    "smooth": {(False, 1, True), (False, 2, True), (False, 1, False), (False, 2, False), (True, 1, False), (True, 2, False)},   # (normals, ORDER, NORM)
+    "correspondence": {False, True},                                                             # the backward's <SUMS>
+    "warp": {(C, sums) for C in (1, 3) for sums in (False, True)},                               # <C, SUMS>
+    "gaussian_reg": {False, True},                                                               # <FILTER>
+    "bilagrid": {False, True},                                                                   # the grid gradient's LMAX: L > 8
+    "bilagrid_tv": {None},
+}
+LOSS_KINDS = ("depth_prior", "normal_map", "appearance", "alpha", "normal_prior", "smooth", "correspondence", "warp", "gaussian_reg", "bilagrid",
+              "bilagrid_tv")
+
+
+def loss_rows(c):
+    """(partial rows the finalize of case c adds, bytes of a row, the library's workspace size for one view) or None: from the constants
+    of include/bags_raster.h as bags_raster._lib and the tests' case modules restate them."""
+    import appearance_cases
+    import depth_prior_cases
+    import normal_prior_cases
+    from bags_raster import _lib as L
+    lib, k, H, W = L.load(), c["kind"], c["H"], c["W"]
+    for fn in ("bags_depth_prior_workspace_size", "bags_normal_map_workspace_size", "bags_appearance_workspace_size", "bags_normal_prior_workspace_size",
+               "bags_smooth_workspace_size", "bags_correspondence_workspace_size", "bags_warp_workspace_size", "bags_gaussian_reg_workspace_size",
+               "bags_bilagrid_tv_workspace_size"):
+        getattr(lib, fn).restype = __import__("ctypes").c_size_t
+    if k == "depth_prior":
+        return depth_prior_cases.slots(H, W), 8 * L.DEPTH_PRIOR_STATS, lib.bags_depth_prior_workspace_size(1, H, W)
+    if k == "normal_map":
+        return depth_prior_cases.slots(H, W), 8 * L.NORMAL_MAP_STATS, lib.bags_normal_map_workspace_size(1, H, W)
+    if k == "appearance":
+        return appearance_cases.slots(H, W), 8 * 16, lib.bags_appearance_workspace_size(1, H, W)
+    if k == "normal_prior":
+        return normal_prior_cases.tiles(H, W), 8 * L.NORMAL_PRIOR_STATS, lib.bags_normal_prior_workspace_size(1, H, W)
+    if k == "smooth":                                            # (the mean rows behind the partial rows: 512 at most, an order of their own)
+        mean = min(-(-H * W // 256), L.SMOOTH_MEAN_SLOTS)
+        return -(-W // L.SMOOTH_TILE_W) * -(-H // L.SMOOTH_TILE_H), 8 * L.SMOOTH_PARTIALS, lib.bags_smooth_workspace_size(1, H, W) - -(-mean * 16 // 256) * 256
+    if k in ("correspondence", "warp"):
+        size = lib.bags_correspondence_workspace_size(1, H, W) if k == "correspondence" else lib.bags_warp_workspace_size(1, H, W)
+        return -(-H * W // L.CORRESPONDENCE_CHUNK), 8 * L.CORRESPONDENCE_SUMS, size
+    if k == "gaussian_reg":
+        return -(-c["P"] // L.GAUSSIAN_REG_ROWS), 8 * L.GAUSSIAN_REG_STATS, lib.bags_gaussian_reg_workspace_size(c["P"])
+    if k == "bilagrid_tv":
+        Gx, Gy, Lz = c["grid"]
+        return min(-(-c["N"] * 12 * Lz * Gy * Gx // L.BILAGRID_TV_BLOCK), L.BILAGRID_TV_MAX_BLOCKS), 8 * 4, lib.bags_bilagrid_tv_workspace_size(c["N"], Gx, Gy, Lz)
+    return None
+
+
+def check_rows(cases):
+    """CPU: every case that is listed for its row count has it -- few: below 256, many: above 256 and no multiple of 256 (the second
+    trip of ordered_rows_sum's loop and its remainder) -- and the count is what the library's size function hands out."""
+    ok = True
+    for c in cases:
+        if c.get("kind") not in LOSS_KINDS or loss_rows(c) is None:
+            continue
+        rows, row_bytes, size = loss_rows(c)
+        good = size == -(-rows * row_bytes // 256) * 256
+        if c["rows"] == "few":
+            good = good and 0 < rows < 256
+        elif c["rows"] == "many":
+            good = good and rows > 256 and rows % 256 != 0
+        print(f"rows check {c['name']:44s} {rows:5d} rows of {row_bytes:3d} bytes, workspace {size:8d} bytes  wanted: {c['rows']}  {'ok' if good else 'FAIL'}")
+        ok = ok and good
+    return ok
+
+
+def run_loss(c, dev):
+    """GPU (child): one fused loss forward and backward, every gradient asked for; loss / output, count, stats and gradients are saved."""
+    k, H, W, V = c["kind"], c["H"], c["W"], c["V"]
+
+    def place(t, grad=False):                                    # at the start of an allocation, or -- offset -- 4 bytes into one
+        if t is None:
+            return None
+        n = t.numel()
+        buf = torch.empty(n + 4, dtype=t.dtype, device=dev)
+        v = (buf[1:1 + n] if c["offset"] else buf[:n]).view(t.shape)
+        v.copy_(t)
+        assert v.data_ptr() % 16 == (t.element_size() if c["offset"] else 0)
+        return v.requires_grad_(True) if grad else v
+
+    def each(ts, grad=False):
+        return [place(t, grad) for t in ts]
+    res, leaves, names, stats = {}, [], [], True
+    if k == "depth_prior":
+        import depth_prior_cases as M
+        from bags_raster import depth_prior_loss
+        m = M.make_case(H, W, V, c["mode"], c["space"])
+        Ds, As = each(m["D"], True), each(m["A"], True)
+        kw = {}
+        if c["mode"] == "l1":
+            table = m["table"].to(dev).requires_grad_(True)
+            kw = dict(table=table, rows=m["rows"])
+            leaves, names = [table], ["table"]
+        out = depth_prior_loss(Ds, As, each(m["prior"]), each(m["mask"]), mode=c["mode"], space=c["space"], min_weight=M.MIN_WEIGHT, **kw)
+        leaves, names, cot = Ds + As + leaves, [f"D{v}" for v in range(V)] + [f"A{v}" for v in range(V)] + names, m["cot"]
+    elif k == "normal_map":
+        import normal_map_cases as M
+        from bags_raster import normal_map_loss
+        m = M.case("generic", H, W, V)
+        Ns = each(m["normal"], True)
+        out = normal_map_loss(Ns, each(m["weights"]), each(m["target"]), each(m["mask"]), mode=c["mode"], min_weight=M.MIN_WEIGHT, min_norm=M.MIN_NORM)
+        leaves, names, cot = Ns, [f"N{v}" for v in range(V)], M.cotangent(V)
+    elif k == "alpha":
+        import alpha_cases as M
+        from bags_raster import alpha_loss
+        m = M.case("generic", H, W, V)
+        As = each(m["weights"], True)
+        out = alpha_loss(As, None if c["mode"] == "entropy" else each(m["target"]), each(m["mask"]), mode=c["mode"], eps=m["eps"])
+        leaves, names, cot = As, [f"A{v}" for v in range(V)], M.cotangent(V)
+    elif k == "normal_prior":
+        import normal_prior_cases as M
+        from bags_raster import normal_prior_loss
+        m = M.make_case(H, W, V, c["mode"])
+        Ds, As = each(m["D"], True), each(m["A"], True)
+        out = normal_prior_loss(Ds, As, each(m["prior"]), m["pinhole"], each(m["mask"]), mode=c["mode"], min_weight=M.MIN_WEIGHT, max_jump=M.MAX_JUMP)
+        leaves, names, cot = Ds + As, [f"D{v}" for v in range(V)] + [f"A{v}" for v in range(V)], m["cot"]
+    elif k == "smooth":
+        import smooth_cases as M
+        from bags_raster import depth_smooth_loss, normal_smooth_loss
+        cfg = M.config(order=c["order"], normalize=c["normalize"], penalty="l1", eps=1e-2, guide="rgb", masked=True)
+        Fs, As, Gs, ms, kw = M.arguments("generic", H, W, V, cfg, c["normals"], torch.float32, "cpu")
+        Fs, As = each([t.detach() for t in Fs], True), each([t.detach() for t in As], not c["normals"])
+        out = (normal_smooth_loss if c["normals"] else depth_smooth_loss)(Fs, As, each(Gs), each(ms), **kw)
+        leaves = Fs + ([] if c["normals"] else As)
+        names, cot = [f"F{v}" for v in range(V)] + ([] if c["normals"] else [f"A{v}" for v in range(V)]), M.cotangent(V)
+    elif k in ("correspondence", "warp"):
+        import correspondence_cases as CC
+        import warp_cases as WC
+        from bags_raster import correspondence_loss, warp_loss
+        m = CC.make_case(H, W, V, c["delta"]) if k == "correspondence" else WC.make_case(H, W, V, c["C"], WC.EPSES[0])
+        Ds, As, Vi, Vj = each(m["D"], True), each(m["A"], True), each(m["Vi"], c["sums"]), each(m["Vj"], c["sums"])
+        if k == "correspondence":
+            out = correspondence_loss(Ds, As, Vi, Vj, each(m["match"]), m["pin_i"], m["pin_j"], each(m["conf"]), delta=c["delta"],
+                                      min_weight=CC.MIN_WEIGHT, min_depth=CC.MIN_DEPTH)
+        else:
+            dst = [[place(m[n][i]) if bool(m["has_dst"][i]) else None for i in range(V)] for n in ("D_dst", "A_dst")]
+            out = warp_loss(Ds, As, Vi, Vj, each(m["color"]), each(m["image"]), m["pin_i"], m["pin_j"], each(m["conf"]), *dst, eps=m["eps"],
+                            occlusion=WC.OCCLUSION, min_weight=WC.MIN_WEIGHT, min_depth=WC.MIN_DEPTH)
+        leaves, names = Ds + As, [f"D{v}" for v in range(V)] + [f"A{v}" for v in range(V)]
+        if c["sums"]:
+            leaves, names = leaves + Vi + Vj, names + [f"Vi{v}" for v in range(V)] + [f"Vj{v}" for v in range(V)]
+        cot = m["cot"]
+    elif k == "gaussian_reg":
+        import gaussian_reg_cases as M
+        from bags_raster import REG_TERMS, gaussian_reg_loss
+        m = M.make_case(c["P"], c["filtered"], c["selected"])
+        x, r = place(m["opacity"], True), place(m["scaling"], True)
+        out = gaussian_reg_loss(x, r, place(m["filter"]) if c["filtered"] else None, place(m["sel"]) if c["selected"] else None, REG_TERMS,
+                                M.MAX_RATIO, M.MAX_SCALE)
+        leaves, names, cot = [x, r], ["opacity", "scaling"], m["cot"]
+    elif k == "appearance":
+        import appearance_cases as M
+        from bags_raster import apply_appearance
+        m = M.make_case(H, W, V)
+        table, xs = m["table"].to(dev).requires_grad_(c["sums"]), each(m["images"], True)
+        outs = apply_appearance(xs, table, m["rows"], m["center"])
+        leaves, names = xs + ([table] if c["sums"] else []), [f"image{v}" for v in range(V)] + (["table"] if c["sums"] else [])
+        grads = torch.autograd.grad(outs, leaves, each(m["cot"]))
+        res = {f"out{v}": o.detach() for v, o in enumerate(outs)}
+        out = stats = None
+    elif k == "bilagrid":
+        import bilagrid_cases as M
+        from bags_raster import apply_bilagrid
+        m = M.make_case(c["grid"], H, W, V)
+        grids, xs = m["grids"].to(dev).requires_grad_(True), [t.to(dev).requires_grad_(True) for t in m["images"]]
+        outs = apply_bilagrid(xs, grids, m["rows"])
+        leaves, names = xs + [grids], [f"image{v}" for v in range(V)] + ["grids"]
+        grads = torch.autograd.grad(outs, leaves, [t.to(dev) for t in m["cot"]])
+        res = {f"out{v}": o.detach() for v, o in enumerate(outs)}
+        out = stats = None
+    else:
+        import bilagrid_cases as M
+        from bags_raster import bilagrid_tv_loss
+        grids = M.make_case(c["grid"], 3, 5, 1)["grids"][:c["N"]].to(dev).contiguous().requires_grad_(True)
+        tv = bilagrid_tv_loss(grids)
+        leaves, names = [grids], ["grids"]
+        grads = torch.autograd.grad(tv, leaves, torch.tensor(1.25, device=dev))
+        res = {"loss": tv.detach()}
+        out = stats = None
+    if out is not None:
+        value, count = out
+        res = {"loss": value.detach(), "count": count.detach()}
+        if stats:                                                # the wrapper's first saved tensor: the stats rows its backward reads
+            res["stats"] = value.grad_fn.saved_tensors[0].clone()
+        grads = torch.autograd.grad(value, leaves, cot.to(dev, torch.float32))
+    res.update({"grad_" + n: g for n, g in zip(names, grads)})
+    res["num_rendered"] = torch.tensor([0])
+    torch.cuda.synchronize(dev)
+    return {n: t.cpu().numpy() for n, t in res.items()}
 
 
 VIEWS = 3
@@ -282,6 +538,8 @@ def run_case(c, dev):
         return run_shc(c, dev)
     if c.get("kind") in ("densify", "add_new", "relocate"):
         return run_resize(c, dev)
+    if c.get("kind") in LOSS_KINDS:
+        return run_loss(c, dev)
     from bags_raster import GaussianRasterizer, debug_views
     from bags_raster import rasterizer as R
     from scenes import camera_tensors, hip_settings
@@ -356,6 +614,7 @@ def main():
     ap.add_argument("--timeout", type=int, default=240, help="seconds per child")
     ap.add_argument("--child", metavar="NPZ", help=argparse.SUPPRESS)
     ap.add_argument("--check-clamp", action="store_true", help="only the CPU check of the narrow camera's cases")
+    ap.add_argument("--check-rows", action="store_true", help="the CPU checks only, the loss cases' partial-row counts included")
     a = ap.parse_args()
     if a.child:
         return child(a.child)
@@ -364,6 +623,11 @@ def main():
         print("FAIL: the narrow camera does not put visible Gaussians beyond the clamp on both axes")
         return 1
     if a.check_clamp:
+        return 0
+    if not check_rows(cases):                            # (loads the library for its size functions: no GPU is touched)
+        print("FAIL: a loss case does not have the partial rows it is listed for")
+        return 1
+    if a.check_rows:
         return 0
     if not a.alternative:
         ap.error("the alternative .so is required")
@@ -410,6 +674,9 @@ def main():
         elif c.get("kind") == "shc":
             rows = ("sh_colors(_views)_bwd", c["M"], c["colour"])
             k9, tag = None, "%s K=%d %s" % rows
+        elif c.get("kind") in LOSS_KINDS:
+            rows = ("ordered_sum", c["kind"], c["inst"], c["rows"])
+            k9, tag = None, "%s instance %s rows %s" % rows[1:]
         elif c.get("kind"):
             rows = ("row_rebuild", c["kind"])
             k9, tag = None, "%s %s" % rows
@@ -418,6 +685,9 @@ def main():
             continue
         if rows:
             covered_rows.add(rows)
+            if rows[0] == "ordered_sum":
+                covered_rows.add(("ordered_sum rows", c["kind"], c["rows"]))
+                covered_rows.add(("ordered_sum instance", c["kind"], c["inst"]))
         else:
             covered_k9.add(k9); covered_k1.add(k1)
         for k in keys:
@@ -431,11 +701,17 @@ def main():
     want_rows = {("sh_grad_from_views", (16, "packed")), ("sh_grad_from_views", (16, "split")), ("sh_grad_from_views", 9), ("sh_grad_from_views", 4)}
     want_rows |= {("sh_colors(_views)_bwd", K, col) for K in (16, 9, 4) for col in ("packed", "split")} | {("sh_colors(_views)_bwd", 1, "packed")}
     want_rows |= {("row_rebuild", kind) for kind in ("densify", "add_new", "relocate")}
+    # csrc/ordered_sum.h: every instance of every family and both row counts, spelled out above, and every listed combination
+    want_rows |= {("ordered_sum instance", k, inst) for k in LOSS_KINDS for inst in LOSS_INSTANCES[k]}
+    want_rows |= {("ordered_sum", c["kind"], c["inst"], c["rows"]) for c in cases if c.get("kind") in LOSS_KINDS}
+    want_rows |= {("ordered_sum rows", k, r) for k in LOSS_KINDS for r in ((None,) if k in ("alpha", "bilagrid") else ("few", "many"))}
     miss_rows = sorted(map(str, want_rows - covered_rows))
     print(f"instances covered by stable cases: preprocess_bwd_kernel {len(covered_k9)} of 16, K1 {len(covered_k1)} of 4, "
           f"sh_grad_from_views {sum(r[0] == 'sh_grad_from_views' for r in covered_rows)} of 4, "
           f"colour backwards {sum(r[0] == 'sh_colors(_views)_bwd' for r in covered_rows)} of 7, "
-          f"resized sets {sum(r[0] == 'row_rebuild' for r in covered_rows)} of 3")
+          f"resized sets {sum(r[0] == 'row_rebuild' for r in covered_rows)} of 3, "
+          f"loss families {len({r[1] for r in covered_rows if r[0] == 'ordered_sum'})} of {len(LOSS_KINDS)} "
+          f"in {sum(r[0] == 'ordered_sum' for r in covered_rows)} combinations of instance and row count")
     if miss9 or miss1 or miss_rows:
         print("FAIL: not covered:", miss9, miss1, miss_rows)
         return 1
